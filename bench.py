@@ -22,8 +22,14 @@ GPU 0 per frame-set, pipelined as submit(k+1); wait(k). It works however the scr
 torch.distributed.run (rank 0 does the work, the other ranks exit at once). `ranks`: one process per GPU, the exchange
 through torch.distributed (pointcloud_stitching_amd/stitch.py); needs torch.distributed.run — launched plain it re-executes
 itself under it.
-Rank 0 prints ONE JSON line. At N = 1 it also carries the other kernels' legs (ordered compaction, K frame-sets per
-launch, the batched a2 twin), each with its own algorithmic byte model, and the CPU baseline.
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and prints it; nothing else. `--full` adds what the
+headline does not need: the oracle check of ring slots 0 and 1 before timing, and at N = 1 the other kernels' legs (ordered compaction,
+K frame-sets per launch, the batched a2 twin, ...), each with its own algorithmic byte model, the long sample, the per-launch and
+host-API figures and the CPU baseline; at N > 1 the shard-only figure. (The node route and `--workload config5` are other
+configurations chosen explicitly; `--full` does not change them.)
+`--dump-outputs DIR` (N = 1, route ranks, stitch workload, fixed-size modes): after the timed steps, what the last step wrote
+(benchlegs/common.py: write_outputs). The ring position of the first warm-up step is fixed (pre-heat ends on a whole turn of the ring),
+so the same arguments give the same last step, and the same inputs, from run to run.
 
 Layout: this file parses the command line, picks the route, measures the headline and assembles the ONE line; the rig (ring of
 frame-sets, launch forms) is benchlegs/rig.py, every other leg is a function in benchlegs/legs_*.py that returns its object and
@@ -42,10 +48,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from benchlegs.common import (ALGO_BYTES_PER_POINT, PACK_BYTES_PER_POINT, HBM_PEAK_GBS, INFINITY_CACHE_BYTES, PG_TIMEOUT, POLICY,      # noqa: E402,F401
-                              Leg, cpu_baseline, emit, flush_c_stdio, run_leg)
+                              Leg, cpu_baseline, emit, flush_c_stdio, run_leg, write_outputs)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
@@ -100,7 +106,14 @@ def parse():
                          "~10 ms after idle run ~15 %% slower on MI355X)")
     ap.add_argument("--traffic", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass; default: profiles/traffic.json")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the oracle check before timing; at N = 1 the other legs, the "
+                         "long sample, the per-launch and host-API figures and the CPU baseline (each --no-* option still drops its "
+                         "part); at N > 1 the shard-only figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/*.npy (float32 / float64, < 64 MB): a "
+                         "fixed sample of its payload records and per-stream column sums of all of them")
+    return ap.parse_args(argv)
 
 
 
@@ -180,7 +193,7 @@ def headline(args, g, world, elapsed, gpu_ms, shard_gpu_ms, long_sample, traffic
                    "ring_inputs_between_rereads_mbytes": round((R - 1) * g.in_bytes_per_set / 1e6, 1),
                    "ring_cold": bool(g.ring_cold),
                    "gather_to_rank0": bool(gather), "parallelism": f"streams sharded {S}/GPU x {world}"},
-        "check": {"oracle_compared": {"slots": checked_slots, "streams": S, "records": "all"}},
+        "check": {"oracle_compared": {"slots": checked_slots, "streams": S, "records": "all"} if checked_slots else None},
         "parity": "bit-exact against this build's own restatement of the -m path (oracle/); the reference cannot be compiled here "
                   "(no librealsense): unpinned",
         "per_stream_fps": round(args.steps * sets_per_launch / elapsed, 1),
@@ -229,6 +242,10 @@ def main():
         except Exception:       # noqa: BLE001
             return 0
     route = choose_route(args.route, args.gpus, args.node_devices, args.debug_backend, world, os.environ, visible)
+    if args.dump_outputs is not None:
+        why = dump_refusal(args, route)
+        if why:
+            raise SystemExit(f"--dump-outputs: {why}")
     if route == "node":
         if int(os.environ.get("RANK", "0")) != 0:
             return 0                     # under torch.distributed.run: rank 0's process drives every GPU of the node
@@ -253,7 +270,7 @@ def main():
     # The CPU samples run FIRST, in child processes, while this process has not yet created a HIP context or a stream:
     # nothing of the GPU legs (runtime helper threads, pinned-memory traffic, thermal state of the host) can move them.
     cpu_first, cpu_first_error, cpu_single = None, None, None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu_first = cpu_baseline(args.width, args.height, args.streams, args.cpu_seconds)
         except Exception as e:       # noqa: BLE001 — a leg must never cost the line
@@ -342,14 +359,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # parity check against the oracle before timing (bench must not time a wrong kernel): EVERY stream of ring slots 0 and 1
-    # (distinct frames), on the very buffers the timed region uses
+    # --full: parity check against the oracle before timing: EVERY stream of ring slots 0 and 1 (distinct frames), on the very
+    # buffers the timed region uses
     g.counter = 0
-    launch(); torch.cuda.synchronize(dev)
-    if sets_per_launch == 1 and R > 1:
-        launch(); torch.cuda.synchronize(dev)          # slot 1 (the batched modes covered it with the first launch)
-    checked_slots = [0, 1] if (R > 1 and (sets_per_launch == 1 or KB >= 2)) else [0]
-    from oracle import pcs_oracle as O
+    checked_slots = []
+    if args.full:
+        from oracle import pcs_oracle as O
+        launch(); torch.cuda.synchronize(dev)
+        if sets_per_launch == 1 and R > 1:
+            launch(); torch.cuda.synchronize(dev)          # slot 1 (the batched modes covered it with the first launch)
+        checked_slots = [0, 1] if (R > 1 and (sets_per_launch == 1 or KB >= 2)) else [0]
     for slot in checked_slots:
         hd, hc = (g.host0, g.host1)[slot]
         if args.mode in ("pack", "pack_batch"):
@@ -361,6 +380,9 @@ def main():
                              f"({int((got != want).any(axis=1).sum())} of {want.shape[0]} records)")
 
     g.preheat(launch, args.preheat_ms)
+    period = ring_period(args, g)
+    while g.counter % period:            # pre-heat ends on a whole turn of the ring: the warm-up starts on slot 0 every run
+        launch()
     gather_error = None
     if gather:
         # The exchange cannot be exercised on the single-GPU development boxes; if RCCL refuses it here the run
@@ -399,11 +421,13 @@ def main():
     drain(); barrier()
     elapsed = time.perf_counter() - t0
     gpu_ms = ctx.timer_elapsed_ms()
+    if args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, last_step_payloads(args, g), S)
 
-    # The driver's --steps 20 makes the contract bracket 0.5 ms long. The SAME launch loop for >= 50 ms, printed beside it
+    # --full: the driver's --steps 20 makes the contract bracket 0.5 ms long. The SAME launch loop for >= 50 ms, printed beside it
     # (roofline.long_sample_ms), says whether a low contract figure is the box or the run length.
     long_sample = None
-    if world == 1:
+    if world == 1 and args.full:
         n_long = max(int(50.0 / max(gpu_ms / args.steps, 1e-3)) + 1, args.steps)
         long_ms = g.timed(launch, n_long)
         torch.cuda.synchronize(dev)
@@ -415,7 +439,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        if gather:
+        if gather and args.full:
             # the same K steps without the exchange: what the kernels alone sustain when streams are only sharded
             barrier()
             t1 = time.perf_counter()
@@ -452,7 +476,7 @@ def main():
         if gather_error:
             out["gather_error"] = gather_error
             out["config"]["gather_to_rank0"] = False
-        if shard_only is not None:
+        if gather:
             total_points = set_points * sets_per_launch * world * args.steps
             peer_bytes = (sum(last_counts[0][1:]) * 10 / max(world - 1, 1)) if variable else payload_shorts * 2
             gb = (world - 1) * peer_bytes * args.steps / elapsed / 1e9
@@ -462,13 +486,14 @@ def main():
                              "counts_per_rank": last_counts[0] if variable else None,
                              "note": "value includes one RCCL gather of every rank's payload to rank 0 per step "
                                      "(double-buffered against the next kernel); it is bound by the peers' xGMI links "
-                                     "into the root, not by the kernel",
-                             "shard_only_value": round(total_points / shard_only / 1e6, 1),
-                             "shard_only_ms_per_step": round(shard_only * 1e3 / args.steps, 5)}
+                                     "into the root, not by the kernel"}
+            if shard_only is not None:           # --full: the same K steps without the exchange
+                out["gather"].update({"shard_only_value": round(total_points / shard_only / 1e6, 1),
+                                      "shard_only_ms_per_step": round(shard_only * 1e3 / args.steps, 5)})
 
         # ---- the other legs: each a function that returns its object, run under the guard (benchlegs/common.py: run_leg) ----------
         from benchlegs import legs_dense as LD
-        extra = world == 1 and args.mode == "dense" and not args.no_extra_legs
+        extra = world == 1 and args.full and args.mode == "dense" and not args.no_extra_legs
         if extra:
             from benchlegs.legs_single import single_stream
             run_leg(out, "single_stream", single_stream, g)
@@ -485,15 +510,15 @@ def main():
             if not args.no_general_rotation:
                 run_leg(out, "general_rotation", LD.general_rotation, g)
                 run_leg(out, "color_1080p", LD.color_1080p, g)
-        if world == 1 and args.mode in ("dense", "drop_invalid", "cutoff"):
+        if world == 1 and args.full and args.mode in ("dense", "drop_invalid", "cutoff"):
             run_leg(out, "per_launch_ms", LD.per_launch_ms, g, into=out["roofline"])
-        if world == 1 and args.mode == "dense" and not args.no_host_api:
+        if world == 1 and args.full and args.mode == "dense" and not args.no_host_api:
             from benchlegs import legs_host as LH
             run_leg(out, "host_api", LH.host_api, g)
             run_leg(out, "host_api_single", LH.host_api_single, g, cpu_single)
         if extra:
             run_leg(out, "per_kernel_unprofiled_us", per_kernel_unprofiled_us, out, kern_ms, S)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             def cpu_leg():
                 if cpu_first is None:
                     raise RuntimeError(cpu_first_error or "cpu baseline did not run")
@@ -505,6 +530,33 @@ def main():
     g.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_refusal(args, route):
+    """Why --dump-outputs cannot be honoured for these arguments (None: it can). Asked before anything touches a GPU."""
+    if route == "node" or args.workload != "stitch" or args.gpus != 1:
+        return "only the one-GPU stitch workload (--gpus 1, route ranks) writes its outputs"
+    if args.mode in ("drop_invalid", "cutoff", "batch_drop_invalid"):
+        return f"--mode {args.mode}: the kept counts stay on the device; only the fixed-size modes write their outputs"
+    return None
+
+
+def ring_period(args, g):
+    """Launches per turn of the ring the launch form walks (its slot = launch counter % period)."""
+    if args.mode in ("batch", "batch_drop_invalid"):
+        return len(g.batch_args)
+    if args.mode in ("pack", "pack_batch"):
+        return g.build_pack_ring()["R"]
+    return g.R
+
+
+def last_step_payloads(args, g):
+    """The payload(s) the most recent launch wrote, each `payload_shorts` int16 words (one per frame-set of the launch)."""
+    k = g.counter - 1
+    if args.mode in ("batch", "batch_drop_invalid"):
+        grp = k % len(g.batch_args)
+        return [g.d_out[grp * g.KB + i][:g.payload_shorts] for i in range(g.KB)]
+    return [g.d_out[k % ring_period(args, g)][:g.payload_shorts]]
 
 
 def per_kernel_unprofiled_us(out, kern_ms, S):

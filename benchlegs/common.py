@@ -95,6 +95,30 @@ def run_leg(out, name, fn, *a, key=None, into=None, **kw):
     return None
 
 
+DUMP_RECORDS = 1 << 20      # records of the --dump-outputs sample: 20 MiB of float32 (+ 8 MiB of float64 indices)
+DUMP_SEED = 0x5EED
+
+
+def write_outputs(directory, payloads, streams):
+    """--dump-outputs: what the timed path's last step handed its caller. `payloads` = one int16 tensor per frame-set of the launch,
+    each the camera-order records [x y z R|G<<8 B] of `streams` streams of equal size. Written to `directory`:
+      payload_records.npy       float32 (n, 5): the record words of a fixed sample (every record when there are at most
+                                DUMP_RECORDS; otherwise DUMP_RECORDS drawn with DUMP_SEED, in index order)
+      payload_record_index.npy  float64 (n,): where each sampled record stands in the concatenated payloads
+      payload_column_sums.npy   float64 (sets * streams, 5): per stream, each record word summed over ALL its records (exact)
+    The sample depends on the record count alone, so two builds run with the same arguments compare file for file."""
+    import numpy as np
+    from pointcloud_stitching_amd.types import POINT_SHORTS
+    recs = np.concatenate([p.reshape(-1).cpu().numpy() for p in payloads]).reshape(-1, POINT_SHORTS)
+    sums = recs.reshape(len(payloads) * streams, -1, POINT_SHORTS).sum(axis=1, dtype=np.int64)
+    n = recs.shape[0]
+    idx = np.arange(n) if n <= DUMP_RECORDS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_RECORDS, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "payload_records.npy"), recs[idx].astype(np.float32))
+    np.save(os.path.join(directory, "payload_record_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "payload_column_sums.npy"), sums.astype(np.float64))
+
+
 def frac_of_hbm(algo_bytes, ms):
     """(GB/s, fraction of the HBM peak) for algo_bytes moved in ms milliseconds."""
     gbs = algo_bytes / (ms * 1e-3) / 1e9

@@ -1,4 +1,4 @@
-"""BASELINE configs[4] on ONE GPU, riding on the default line."""
+"""BASELINE configs[4] on ONE GPU, riding on the --full line."""
 import hashlib
 import json
 import os

@@ -1,10 +1,11 @@
-"""bench.py's output contract: ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline`."""
+"""bench.py's output contract: ONE JSON line with the driver's keys plus `roofline`; with --full also `cpu_baseline` and the legs."""
 import json
 import os
 import py_compile
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +27,7 @@ def test_bench_refuses_to_run_without_a_gpu(gpu_present):
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_keys():
-    r = subprocess.run([sys.executable, BENCH, "--steps", "30", "--warmup", "5", "--preheat-ms", "50", "--cpu-seconds", "1"],
+    r = subprocess.run([sys.executable, BENCH, "--full", "--steps", "30", "--warmup", "5", "--preheat-ms", "50", "--cpu-seconds", "1"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -49,7 +50,7 @@ def test_bench_line_has_the_contract_keys():
     assert cb["kind"] == "port" and cb["unit"] == "Mpoints/s" and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
     assert cb["host_physical_cores"] >= 1 and cb["host_logical_cpus"] >= cb["host_physical_cores"]
     assert cb["host_logical_cpus"] == len(os.sched_getaffinity(0)) and cb["statistic"] == "median" and cb["passes"] >= 30
-    # the other kernels' legs ride on the default line, each with its own byte model
+    # the other kernels' legs ride on the --full line, each with its own byte model
     comp = d["compaction"]
     assert 0.85 < comp["kept_fraction"] < 0.95 and abs(comp["algorithmic_bytes_per_point"] - (5 + 10 * comp["kept_fraction"])) < 1e-2
     assert comp["frac"] > 0.2 and d["batched_dense"]["frac"] > 0.3 and d["pack_twin"]["batched_frac"] > 0.2
@@ -67,7 +68,7 @@ def test_bench_line_has_the_contract_keys():
     assert 0.2 < c1080["frac"] < d["general_rotation"]["frac"] and "1920x1080" in c1080["workload"]
     # two clocks on one region, both on the line: the event bracket (frac) and the wall clock value is computed from (frac_wall)
     assert abs(rf["frac_wall"] - rf["algorithmic_bytes_per_launch"] / (d["ms_per_step"] * 1e-3) / 1e9 / rf["peak"]) < 2e-3 and "clocks" in rf
-    assert "unpinned" in d["parity"]
+    assert "unpinned" in d["parity"] and d["check"]["oracle_compared"]["slots"] == [0, 1]
     # BASELINE configs[1]: ONE 720p stream, device-resident, cold ring, oracle-checked, with its own roofline
     ss = d["single_stream"]
     assert "configs[1]" in ss["workload"] and ss["ring_cold"] is True and ss["check"]["oracle_compared"]["slots"] == [0, 1]
@@ -192,6 +193,81 @@ def test_node_route_config5_pipelined_matches_the_digest():
 def test_ranks_route_launched_plain_reexecutes_itself_under_torchrun():
     d = _bench_line("--gpus", "2", "--debug-backend", "gloo", "--steps", "4", "--warmup", "1", "--preheat-ms", "10")
     assert d["n_gpus"] == 2 and d["config"]["gather_to_rank0"] is True and "gloo" in d["debug"]
+
+
+DUMP_FILES = ["payload_column_sums.npy", "payload_record_index.npy", "payload_records.npy"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_its_last_step(tmp_path, oracle):
+    """A plain run sets up, warms up, times --steps launches and prints the line: no oracle check, legs, long sample or CPU sample.
+    --dump-outputs writes what the last timed step computed. Pre-heat ends on a whole turn of the ring, so the last of W + K launches
+    read ring slot (W + K - 1) % R, whose frame-set is host set slot % 4 (benchlegs/rig.py: DISTINCT): the dumped records are the
+    oracle's records of that set, and a second run writes the same files."""
+    W, K = 5, 23
+    a = _bench_line("--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path / "a"))
+    for k in CONTRACT_KEYS:
+        assert k in a, k
+    assert a["steps"] == K and a["warmup"] == W and a["dtype"] == "f32" and a["check"]["oracle_compared"] is None
+    assert abs(a["value"] - 8 * 1280 * 720 / (a["ms_per_step"] * 1e-3) / 1e6) / a["value"] < 0.01
+    for k in ("cpu_baseline", "speedup_vs_cpu_baseline", "compaction", "batched_dense", "config5_one_gpu", "single_stream", "host_api",
+              "host_api_single", "per_kernel_unprofiled_us", "leg_errors"):
+        assert k not in a, k
+    assert a["roofline"]["long_sample_ms"] is None and "per_launch_ms" not in a["roofline"]
+    b = _bench_line("--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path / "b"))
+    assert sorted(os.listdir(tmp_path / "a")) == DUMP_FILES
+    total = 0
+    for f in DUMP_FILES:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+        total += os.path.getsize(tmp_path / "a" / f)
+    assert total <= 64 << 20
+    from pointcloud_stitching_amd import synthetic as Syn
+    seed = Syn.SEED + 7919 * (((W + K - 1) % a["config"]["ring_frame_sets"]) % 4)
+    cfgs = [Syn.synth_stream_config(1280, 720, s) for s in range(8)]
+    dep = [Syn.synth_depth(1280, 720, s, seed=seed) for s in range(8)]
+    col = [Syn.synth_color(1280, 720, s, seed=seed) for s in range(8)]
+    want, _ = oracle.process_frames(cfgs, dep, col, 0, 1)
+    idx = np.load(tmp_path / "a" / "payload_record_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "payload_records.npy"), want[idx].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "payload_column_sums.npy"), want.reshape(8, -1, 5).sum(axis=1, dtype=np.int64))
+
+
+def test_dump_outputs_is_refused_where_it_cannot_be_honoured(tmp_path):
+    """--full and --dump-outputs are off by default; a dump that cannot be honoured is refused before anything touches a GPU."""
+    b = _load_bench_module()
+    d = b.parse([])
+    assert d.full is False and d.dump_outputs is None
+    assert b.dump_refusal(b.parse(["--dump-outputs", "x"]), "ranks") is None
+    for mode in ("batch", "pack", "pack_batch"):
+        assert b.dump_refusal(b.parse(["--dump-outputs", "x", "--mode", mode]), "ranks") is None
+    assert b.dump_refusal(b.parse(["--dump-outputs", "x", "--gpus", "2"]), "node")
+    assert b.dump_refusal(b.parse(["--dump-outputs", "x", "--route", "node"]), "node")
+    assert b.dump_refusal(b.parse(["--dump-outputs", "x", "--workload", "config5"]), "ranks")
+    assert b.dump_refusal(b.parse(["--dump-outputs", "x", "--mode", "drop_invalid"]), "ranks")
+    r = subprocess.run([sys.executable, BENCH, "--workload", "config5", "--dump-outputs", str(tmp_path / "d")],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not os.path.exists(tmp_path / "d")
+
+
+def test_written_outputs_are_a_fixed_sample_and_exact_sums(tmp_path):
+    import torch
+    from benchlegs import common as CM
+    g = torch.Generator().manual_seed(3)
+    for sets, per_stream in ((1, 1000), (2, 70_000)):
+        pay = [torch.randint(-32768, 32768, (8 * per_stream * 5,), dtype=torch.int16, generator=g) for _ in range(sets)]
+        CM.write_outputs(str(tmp_path / "a"), pay, 8)
+        CM.write_outputs(str(tmp_path / "b"), pay, 8)
+        assert sorted(os.listdir(tmp_path / "a")) == DUMP_FILES
+        recs = torch.cat(pay).view(-1, 5).numpy()
+        rec, idx = np.load(tmp_path / "a" / "payload_records.npy"), np.load(tmp_path / "a" / "payload_record_index.npy")
+        assert rec.dtype == np.float32 and idx.dtype == np.float64
+        assert len(idx) == min(recs.shape[0], CM.DUMP_RECORDS) and np.all(np.diff(idx) > 0)
+        assert np.array_equal(rec, recs[idx.astype(np.int64)].astype(np.float32))
+        sums = np.load(tmp_path / "a" / "payload_column_sums.npy")
+        assert sums.shape == (sets * 8, 5) and np.array_equal(sums, recs.reshape(sets * 8, -1, 5).sum(axis=1, dtype=np.int64))
+        for f in DUMP_FILES:
+            assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
 
 
 def _load_bench_module():

@@ -3,7 +3,7 @@
 # 16 x 1080p half of config 5); prints one line each.   tools/compaction_sweep.sh [outdir]
 OUT=${1:-gpurun_out/sweep}
 mkdir -p $OUT
-B="python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-host-api"
+B="python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-host-api"
 for geo in "8 1280 720 300" "16 1920 1080 100"; do
   set -- $geo; S=$1; W=$2; H=$3; K=$4
   for mode in drop_invalid cutoff; do

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Prints DESIGN.md section 0's kernel table from the round's committed records — `profiles/<tag>_bench.json` (one `python bench.py`
+"""Prints DESIGN.md section 0's kernel table from the round's committed records — `profiles/<tag>_bench.json` (one `python bench.py --full`
 line), `<tag>_kernel_stats.csv` (rocprofv3 --kernel-trace --stats of the same commands), `<tag>_pmc_summary.json` (separate --pmc passes),
 `<tag>_bench_config5_node1.json` / `_node8v.json` — so the document cannot quote a figure no record holds. DESIGN.md keeps the output
 between the kernels markers; tests/test_docs.py regenerates it and compares.

@@ -16,8 +16,8 @@ python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error|^E " | tail
   PCS_VOXEL_TAIL=bucket timeout $((SOAK*3)) python tools/voxel_raster_soak.py $SOAK 7107
   timeout $((SOAK*4)) python tools/node_soak.py $SOAK 7108
 } 2>&1 | grep -v -E "amdgpu.ids|RCCL version|HIP version|ROCm version|Hostname|Librccl" > $OUT/soak.log; cat $OUT/soak.log
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-python bench.py > $OUT/bench_again.json 2>/dev/null
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench_again.json 2>/dev/null
 python bench.py --workload config5 --steps 60 --warmup 5 > $OUT/bench_config5.json 2>/dev/null
 python bench.py --workload config5 --route node --gpus 1 --steps 200 --warmup 10 > $OUT/bench_config5_node1.json 2>/dev/null
 python bench.py --workload config5 --gpus 8 --node-devices 0,0,0,0,0,0,0,0 --steps 100 --warmup 5 > $OUT/bench_config5_node8v.json 2>/dev/null

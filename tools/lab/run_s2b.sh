@@ -7,4 +7,4 @@ for q in default 8 16 24; do
 done
 unset GPU_MAX_HW_QUEUES
 python tools/single_probe.py 1 5000 > $O/single_probe.txt 2>&1
-python bench.py --no-config5 --no-host-api --no-cpu-baseline > $O/bench_lite.json 2> $O/bench_lite.err
+python bench.py --full --no-config5 --no-host-api --no-cpu-baseline > $O/bench_lite.json 2> $O/bench_lite.err

@@ -41,8 +41,8 @@ RUNS[twin_single]="python $PWD/tools/single_probe.py 1 3000 twin"
 # the colour row computed per pixel (PCS_ROW_CONST=0)
 RUNS[voxel_two_ctx]="python $PWD/tools/voxel_overlap_probe.py 2 50 80"
 RUNS[voxel_one_call_norowc]="env PCS_ROW_CONST=0 python $PWD/tools/voxel_probe.py 50 80"
-# every leg of the default line (incl. centre_transform, config5_one_gpu, color_1080p): one row per kernel of the library
-RUNS[all_legs]="python $PWD/bench.py --steps $STEPS --warmup 20 --no-cpu-baseline --no-host-api"
+# every leg of the --full line (incl. centre_transform, config5_one_gpu, color_1080p): one row per kernel of the library
+RUNS[all_legs]="python $PWD/bench.py --full --steps $STEPS --warmup 20 --no-cpu-baseline --no-host-api"
 ORDER=${PROFILE_RUNS:-"dense all_legs single single_512 twin_single drop_invalid cutoff pack pack_batch batch batch_drop_invalid voxel voxel_one_call voxel_one_call_norowc voxel_one_call_cold voxel_one_call_lsd voxel_two_ctx config5 node_stitch node_config5"}
 PMC_ORDER=${PROFILE_PMC_RUNS:-"dense all_legs single voxel_one_call voxel_one_call_norowc voxel_one_call_cold voxel_one_call_lsd config5"}
 cd /tmp

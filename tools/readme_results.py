@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Prints README.md's "Results at a glance" table from ONE recorded bench line (default: profiles/r06_bench.json, the `python
-bench.py` line of the round's final build on one MI355X). README holds the output between the results markers;
+bench.py --full` line of the round's final build on one MI355X). README holds the output between the results markers;
 tests/test_bench_contract.py regenerates it and compares, so the README cannot quote a number no record holds.
 
     python tools/readme_results.py [bench.json] [--write]      # --write: replace the block in README.md
@@ -69,7 +69,7 @@ def table(d, src):
          f"median of {cb['passes']} passes, team bound, reference's own bracket",
          f"{cb['ms_per_frame_set']:.2f} ms", f"{cb['value'] / 1e3:.2f} k Mpoints/s", f"GPU = {d['speedup_vs_cpu_baseline']:.1f} ×"),
     ]
-    out = [BEGIN, f"(from `{src}`: one `python bench.py` line, inputs cold in HBM; regenerate with `python tools/readme_results.py --write`)", "",
+    out = [BEGIN, f"(from `{src}`: one `python bench.py --full` line, inputs cold in HBM; regenerate with `python tools/readme_results.py --write`)", "",
            "| workload | time | rate | of 8 TB/s HBM |", "|---|---|---|---|"]
     out += ["| " + " | ".join(x) + " |" for x in rows]
     if "parity" in d:
