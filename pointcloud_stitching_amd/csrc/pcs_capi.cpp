@@ -248,6 +248,27 @@ uint32_t cutoff_dmax(const pcs_stream_config& s, const StreamParams& p, const st
     return lo;       // 0 if even d = 1 is beyond 1.5 m: nothing is in range; the general path handles it
 }
 
+// The dense kernel's colour window for a row-constant stream (pcs_kernels.hip: dense_tile_rowc). The colour column of depth column c at
+// depth z is trunc(px + 0.5), px = (c - d_ppx) / d_fx * c_fx + c_ppx + t_x * c_fx / z. In 20.12 fixed point, lo(c) = (c * kx + bx_lo) >> 12
+// and hi(c) = (c * kx + bx_hi) >> 12 bracket it for every z at or beyond d_win, with two columns to spare for the rounding of the float
+// chain and of kx: d_win is where the shift t_x * c_fx / z reaches kWinShiftCols columns, or fewer when the two stretches of a wave
+// that straddles a row would not fit the 3 072 bytes of its window. Only speed depends on these numbers: a pixel outside the window is
+// gathered from the raster.
+constexpr double kWinShiftCols = 48.0;      // synthetic rig (f = 896 px, t_x = 15 mm): d_win = 0.28 m
+void color_window_params(const StreamParams& p, float tx, int32_t out[3])
+{
+    const double a = (double)p.c_fx / p.d_fx, b = (double)p.c_ppx - (double)p.d_ppx * a + 0.5;
+    const double room = ((3072.0 - 2 * 34) / p.bpp - 512.0 * a) / 2.0 - 4.0;
+    const double shift = std::max(0.0, std::min(kWinShiftCols, room));
+    const double lo = b - 2.0 - (tx < 0.0f ? shift : 0.0), hi = b + 2.0 + (tx > 0.0f ? shift : 0.0);
+    const double kx = std::round(a * 4096.0);
+    const double reach = kx * p.W + 4096.0 * std::max(std::fabs(lo), std::fabs(hi)) + 4096.0;
+    if (!(a > 0.0) || !(reach < 2147483647.0)) { out[0] = 0; out[1] = 0; out[2] = -4096; return; }   // (a 16-byte window: all gathered)
+    out[0] = (int32_t)kx;
+    out[1] = (int32_t)std::floor(lo * 4096.0);
+    out[2] = (int32_t)std::ceil(hi * 4096.0);
+}
+
 inline uint32_t tiles_of(uint32_t n) { return (n + kTilePoints - 1) / kTilePoints; }
 
 // One slab for all streams' rasters, carved at 256-byte granularity (see the comment at s_slab).
@@ -396,18 +417,21 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
         uint32_t mp = 0;
         for (int k = 0; k < nl; k++) { fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k]; mp = std::max(mp, c->h_params[s0 + k].n_points); }
         bool fast = true, ident = true, noovf = true;    // AND over the streams of this launch
+        bool rowc = true;                                // ... and every stream row-constant, its raster rows whole 8-pixel runs
         bool dd = false, cd = false;
         for (int k = 0; k < nl; k++) {
             const StreamParams& q = c->h_params[s0 + k];
             fast &= q.cert_fast != 0; ident &= q.ident_r != 0; noovf &= q.no_overflow != 0;
+            rowc &= q.ident_r == 2 && (q.W & 7) == 0 && q.color_bytes >= 16;
             dd |= q.ddist != 0;
             cd |= q.cdist != 0 || q.tex_half != 0;
         }
         const MathSel sel = !fast ? MathSel::Ieee
                           : noovf ? (ident ? MathSel::CertIdentRNoOvf : MathSel::CertNoOvf)
                                   : (ident ? MathSel::CertIdentR : MathSel::Cert);
-        if (dense)
-            HIPCHK(c, launch_fused_dense(c->d_params, s0, nl, mp, dd, cd, sel, fp, d_payload, c->stream));
+        if (dense)      // (the dense kernel's row-constant form: its colour window is requested beside the depth, pcs_kernels.hip)
+            HIPCHK(c, launch_fused_dense(c->d_params, s0, nl, mp, dd, cd, sel == MathSel::CertIdentRNoOvf && rowc ? MathSel::CertRowConstNoOvf : sel,
+                                         fp, d_payload, c->stream));
         else
             HIPCHK(c, launch_fused_emit(c->d_params, s0, nl, mp, c->flags, c->downsample, sel, fp, c->d_tile_prefix,
                                         c->d_stream_base, d_payload,
@@ -680,7 +704,12 @@ int pcs_create(pcs_ctx** out, const pcs_config* cfg)
             unsigned long long h = 1;
             CREATE_CHK(hipMemcpyAsync(&h, d_bad, sizeof h, hipMemcpyDeviceToHost, c->stream));
             CREATE_CHK(hipStreamSynchronize(c->stream));
-            if (h == 0) { p.ident_r = 2; any = true; }
+            if (h == 0) {
+                p.ident_r = 2; any = true;
+                int32_t win[3];
+                color_window_params(p, t[0], win);
+                CREATE_CHK(hipMemcpy(d_crow + p.H, win, sizeof win, hipMemcpyHostToDevice));    // behind the colour rows (the my LUT's spare words)
+            }
         }
         if (d_bad) (void)hipFree(d_bad);
         if (any) CREATE_CHK(hipMemcpy(c->d_params, c->h_params.data(), sizeof(StreamParams) * c->n_streams, hipMemcpyHostToDevice));

@@ -50,7 +50,8 @@ struct alignas(16) StreamParams {
     uint32_t cut_dmax;       // -c from the Z16 word alone: in range <=> 1 <= d <= cut_dmax (0 = not certified, deproject)
     int32_t  tex_half;       // PCS_FLAG_TEXCOORD_HALF_PIXEL: u = (px + 0.5)/W (handled on the CDIST code path)
     const float* mx;         // [W]  (c - ppx) / fx   — IEEE division done once on the host
-    const float* my;         // [H]  (r - ppy) / fy; behind it [H] int32: the colour row of raster row r (valid when ident_r == 2)
+    const float* my;         // [H]  (r - ppy) / fy; behind it [H] int32: the colour row of raster row r (valid when ident_r == 2),
+                             // then int32 {kx, bx_lo, bx_hi}: the dense kernel's colour window (pcs_capi.cpp: color_window_params)
 };
 
 // Per-call raster pointers, passed by value in the kernarg segment (no per-frame H2D of a table).
@@ -91,7 +92,8 @@ struct PackBatch {
 
 // Which arithmetic policy a launch may use (the AND over the streams of the launch).
 enum class MathSel { Ieee = 0, Cert = 1, CertIdentR = 2, CertNoOvf = 3, CertIdentRNoOvf = 4,
-                     CertRowConst = 5 /* voxel reader only: CertIdentR + the colour row from a per-row table (ident_r == 2) */ };
+                     CertRowConst = 5 /* voxel reader only: CertIdentR + the colour row from a per-row table (ident_r == 2) */,
+                     CertRowConstNoOvf = 6 /* dense kernel only: CertIdentRNoOvf + the row table + the colour window */ };
 
 // Launchers (defined in pcs_kernels.hip). All enqueue on `st` and return the hipError of the launch.
 hipError_t launch_fused_dense(const StreamParams* d_params, int stream0, int n_launch, uint32_t max_points,

@@ -257,6 +257,10 @@ using CertIdentNoOvf = CertMath<true, true>;
 struct CertRowConst : CertMath<true, false> {
     [[maybe_unused]] static constexpr bool kRowConst = true;
 };
+// The same over the no-overflow form: the dense kernel's policy for launches whose streams are all row-constant (dense_tile_rowc).
+struct CertRowConstNoOvf : CertMath<true, true> {
+    [[maybe_unused]] static constexpr bool kRowConst = true;
+};
 
 // a2 colour lookup (src/pcs-camera-optimized.cpp:431-452, 584-585): texcoord -> byte index of the pixel.
 __device__ __forceinline__ void color_coords(const StreamParams& P, float u, float v, float& xf, float& yf)
@@ -764,6 +768,190 @@ __device__ __forceinline__ void dense_tile(const StreamParams& P, const Src& src
 }
 
 // ------------------------------------------------------------------------------------------------
+// DENSE tile for launches whose streams are all row-constant (CertRowConstNoOvf, StreamParams::ident_r == 2): the colour
+// bytes are requested beside the depth instead of behind it.
+//
+// A pixel's colour ROW is its raster row's entry of the certified table; only its COLUMN depends on the depth, and for depths
+// beyond the stream's d_win it lies within a margin of the depth column's image (pcs_capi.cpp: color_window_params). A wave's
+// 512 pixels lie on at most two raster rows, so the wave knows — from its first and last pixel and two scalar loads of the
+// table — the one or two stretches of colour bytes its pixels will read before any depth value has arrived. It requests them
+// by LDS-DMA into the front of its own 5 120 bytes of `stage` (where its records are parked later), right after the Z16 and
+// LUT loads: the two round trips run together, and deprojection waits for the depth with the window still in flight.
+// A pixel then reads its dword from LDS when the dword lies inside the window, or pixel (0, 0)'s word — what every invalid
+// pixel carries, parked by the wave at the end of its part of `stage` — when its byte index is 0; any other pixel (a depth
+// nearer than d_win, a row the window does not cover, the raster's last pixel) takes the global gather with the exact
+// slide-back, exec-masked to its lanes. The window is a cache keyed by byte address: a wrong guess costs time, never bits.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kWaveStageBytes = 64u * kPointsPerLane * PCS_POINT_BYTES;        // 5 120: one wave's records
+constexpr uint32_t kWinPieces      = 3;                                             // 16-byte LDS-DMA requests per lane
+constexpr uint32_t kWinBytes       = kWinPieces * 64u * 16u;                        // 3 072: the wave's windows together
+constexpr uint32_t kWinZeroWord    = kWaveStageBytes - 16u;                         // pixel (0, 0)'s word, past the windows
+static_assert(kWinBytes + 8u <= kWinZeroWord, "the windows, the dword read past their end and the zero word fit one wave's stage");
+
+template <class T> using cptr = const __attribute__((address_space(4))) T*;         // read-only for the kernel's life: scalar loads
+
+// One colour stretch of a wave: the bytes of colour row `crow` that depth columns [c0, c1] can reach at depths beyond d_win,
+// 16-aligned, inside the raster's whole 16-byte pieces, at most `room` bytes. Wave-uniform (scalar) arithmetic.
+__device__ __forceinline__ void color_stretch(const StreamParams& P, const int32_t (&wp)[3], int32_t crow, int32_t c0, int32_t c1,
+                                              uint32_t room, uint32_t& ws, uint32_t& len)
+{
+    const int32_t lo = min(max((c0 * wp[0] + wp[1]) >> 12, 0), P.cW - 1);
+    const int32_t hi = min(max((c1 * wp[0] + wp[2]) >> 12, 0), P.cW - 1);
+    const uint32_t row = (uint32_t)crow * (uint32_t)P.stride;
+    ws = (row + (uint32_t)lo * (uint32_t)P.bpp) & ~15u;
+    const uint32_t we = min((row + (uint32_t)hi * (uint32_t)P.bpp + 4u + 15u) & ~15u, P.color_bytes & ~15u);
+    len = min(we > ws ? we - ws : 0u, room);
+}
+
+// The row-constant tile's vector loads, written as asm. hipcc does not wait for an LDS-DMA request by count: with one in flight it
+// waits vmcnt(0) at the first use of any load, which would hold deprojection until the colour window has landed. So the tile issues
+// its own five loads (Z16 quad, two LUT quads, my, colour row) and its three window requests here, outside the compiler's
+// bookkeeping, and waits for them itself: vmcnt(kWinPieces) before deprojection (everything but the window, naming the five
+// destinations so that nothing reads them earlier) and vmcnt(0) before the first read of the window.
+typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4v load16_asm(const void* base, uint32_t off)
+{
+    u32x4v v;
+    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(off), "s"(base));
+    return v;
+}
+__device__ __forceinline__ uint32_t load4_asm(const void* base, uint32_t off)
+{
+    uint32_t v;
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(v) : "v"(off), "s"(base));
+    return v;
+}
+// One LDS-DMA request: this lane's 16 bytes at color + off -> LDS byte lds + 16 * lane (M0 set and restored in the statement).
+__device__ __forceinline__ void window_piece(const uint8_t* color, uint32_t off, uint32_t lds)
+{
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(off), "s"(color), "s"(lds) : "memory");
+}
+
+template <class Mth, uint32_t THREADS = kBlockThreads>
+__device__ __forceinline__ void dense_tile_rowc(const StreamParams& P, const uint16_t* __restrict__ depth,
+                                                const uint8_t* __restrict__ color, uint32_t tile0, uint32_t n,
+                                                uint8_t* __restrict__ out_bytes, uint4* stage)
+{
+    static_assert(Mth::kRowConst && Mth::kCvtMode == 2, "the no-overflow row-constant policy");
+    // (src.fast(P) holds: launch_fused_dense takes this tile only for 16-aligned rasters with W % 8 == 0)
+    const uint32_t i0 = tile0 + threadIdx.x * kPointsPerLane;
+    const uint32_t ic = min(i0, n - kPointsPerLane);        // a lane past the stream's end reads its last quad; its records are not stored
+    const uint32_t r = P.w_magic ? (__umulhi(ic, P.w_magic) >> P.w_shift) : ic / (uint32_t)P.W;
+    const uint32_t c0 = ic - r * (uint32_t)P.W;
+    u32x4v dv = load16_asm(depth, ic * 2u);                 // what src.fetch() requests, in its order, then the colour row
+    u32x4v ma = load16_asm(P.mx, c0 * 4u);
+    u32x4v mb = load16_asm(P.mx, c0 * 4u + 16u);
+    uint32_t myb = load4_asm(P.my, r * 4u);
+    uint32_t crow = load4_asm(P.my, ((uint32_t)P.H + r) * 4u);
+
+    // The wave's windows (wave-uniform): the rows of its first and last pixel (lanes 0 and 63), their colour rows, the stretches.
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t iw = tile0 + wave * 64u * kPointsPerLane;
+    const uint32_t il = min(iw + 64u * kPointsPerLane, n) - 1u;
+    const uint32_t ra = __builtin_amdgcn_readfirstlane(r), rb = __builtin_amdgcn_readlane(r, 63);
+    const cptr<int32_t> tab = (cptr<int32_t>)(uintptr_t)(P.my + P.H);          // [H] colour rows, then the window constants
+    const int32_t wp[3] = {tab[P.H], tab[P.H + 1], tab[P.H + 2]};
+    const uint32_t lrel = wave * kWaveStageBytes;                                // the wave's part of stage
+    uint32_t wsa = 0, lena = 0, wsb = 0, lenb = 0;
+    if (iw < n) {    // (a wave past the stream's end has no pixel to stage)
+        color_stretch(P, wp, tab[ra], (int32_t)(iw - ra * (uint32_t)P.W), ra == rb ? (int32_t)(il - ra * (uint32_t)P.W) : P.W - 1,
+                      kWinBytes, wsa, lena);
+        if (rb != ra) color_stretch(P, wp, tab[rb], 0, (int32_t)(il - rb * (uint32_t)P.W), kWinBytes - lena, wsb, lenb);
+    }
+    // Both stretches back to back, one 16-byte piece per lane per request (piece j -> the wave's stage + 16 j); lanes past the last
+    // piece repeat it (nothing past the last piece is read).
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t pieces = max((lena + lenb) >> 4, 1u), pa = lena >> 4;     // (no window: piece 0 = the raster's first 16 bytes)
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)stage + lrel;
+#pragma unroll
+    for (uint32_t k = 0; k < kWinPieces; k++) {
+        const uint32_t j = min(k * 64u + lane, pieces - 1u);
+        window_piece(color, j < pa ? wsa + 16u * j : wsb + 16u * (j - pa), lds0 + k * 1024u);
+    }
+    if (lane == 0) *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(stage) + lrel + kWinZeroWord) = *(cptr<uint32_t>)(uintptr_t)color;
+
+    static_assert(kWinPieces == 3, "the wait below leaves the window's requests in flight");
+    asm volatile("s_waitcnt vmcnt(3)" : "+v"(dv), "+v"(ma), "+v"(mb), "+v"(myb), "+v"(crow));
+    PointIn p[8];
+    {
+        const uint32_t dw[4] = {dv.x, dv.y, dv.z, dv.w};
+        const uint32_t mxs[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint32_t d = (k & 1) ? (dw[k >> 1] >> 16) : (dw[k >> 1] & 0xFFFFu);
+            p[k] = deproject_pixel_rowc<Mth>(P, d, __uint_as_float(mxs[k]), __uint_as_float(myb), (int)crow);
+        }
+    }
+    // The record fields of make_record, and each pixel's colour byte index (the row is p.v itself: deproject_pixel_rowc).
+    FastCvt<false> cv;
+    uint32_t xy[8], zz[8], ci[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const float ax = world_mm(P.M + 0, p[k].X, p[k].Y, p[k].Z);
+        const float ay = world_mm(P.M + 4, p[k].X, p[k].Y, p[k].Z);
+        const float az = world_mm(P.M + 8, p[k].X, p[k].Y, p[k].Z);
+        xy[k] = perm((uint32_t)cv.cvt(ay), (uint32_t)cv.cvt(ax), kLoLo);
+        zz[k] = (uint32_t)cv.cvt(az);
+        const int32_t xi = cv.pixel(__fmaf_rn(p[k].u, P.c_w_f, 0.5f), P.cW - 1, P.c_wm1_f);
+        ci[k] = __umul24((uint32_t)xi, (uint32_t)P.bpp) + __umul24((uint32_t)__float_as_int(p[k].v), (uint32_t)P.stride);
+    }
+    // The colour dwords: from the lane's window (the wave's first row's or its last row's), pixel (0, 0)'s word for byte 0; a
+    // lane with any other pixel gathers those from the raster as make_record does, with the exact slide-back at its end.
+    const bool in_a = r == ra;
+    const uint32_t ws = in_a ? wsa : wsb, len = in_a ? lena : lenb;
+    const uint32_t wn = len > 3u ? len - 3u : 0u;           // a dword at ws + o lies inside for o < wn
+    const uint32_t lb = lrel + (in_a ? 0u : lena), lz = lrel + kWinZeroWord;
+    // the window has landed (after the byte indices: the wait is not to be hoisted above the arithmetic)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(ci[0]), "+v"(ci[1]), "+v"(ci[2]), "+v"(ci[3]), "+v"(ci[4]), "+v"(ci[5]), "+v"(ci[6]),
+                 "+v"(ci[7]) :: "memory");
+    uint32_t wc[8];
+    bool miss = false;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t o = ci[k] - ws;
+        const bool in = o < wn;        // a hit never needs the slide-back: the window ends inside the raster
+        const uint32_t* qa = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(stage) + (in ? (lb + o) & ~3u : lz));
+        wc[k] = __builtin_amdgcn_alignbyte(qa[1], qa[0], ci[k]);      // bytes ci .. ci+3 (window starts are 16-aligned; byte 0: the word)
+        miss |= !in && ci[k] != 0u;
+    }
+    if (__builtin_expect(miss, 0)) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (!(ci[k] - ws < wn) && ci[k] != 0u) {
+                ExactCvt exact;
+                uint32_t shift;
+                const uint32_t off = exact.window(ci[k], P.color_bytes - 4u, shift);
+                uint32_t g;
+                __builtin_memcpy(&g, color + off, 4);
+                wc[k] = g >> shift;
+            }
+        }
+    }
+    uint32_t w[20];
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) {
+        const Record a{xy[k], perm(wc[k], zz[k], kLoLo), __builtin_amdgcn_ubfe(wc[k], 16, 8)};
+        const Record b{xy[k + 1], perm(wc[k + 1], zz[k + 1], kLoLo), __builtin_amdgcn_ubfe(wc[k + 1], 16, 8)};
+        uint32_t* o = w + (k >> 1) * 5;
+        o[0] = a.xy;
+        o[1] = a.zc;
+        o[2] = perm(b.xy, a.b, kLoLo);
+        o[3] = perm(b.zc, b.xy, kHiLo);
+        o[4] = perm(b.b, b.zc, kHiLo);
+    }
+    uint4* mine = stage + threadIdx.x * 5;       // over the wave's window: the wave's reads of it are done (their values are in wc)
+#pragma unroll
+    for (int k = 0; k < 5; k++) mine[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    __syncthreads();
+
+    const uint32_t pts = min(THREADS * kPointsPerLane, n - tile0);
+    store_staged<THREADS>(reinterpret_cast<const uint8_t*>(stage), 0u, pts * PCS_POINT_BYTES,
+                          out_bytes + (size_t)tile0 * PCS_POINT_BYTES);
+}
+
+// ------------------------------------------------------------------------------------------------
 // GENERIC tile: predicate and/or downsample and/or unaligned payload. Order-preserving.
 //   g0        kept-index (within the stream) of the tile's first kept point
 //   out_first output point index (within the whole payload) of kept-index 0 of this stream
@@ -1074,8 +1262,12 @@ void pcs_fused_dense_kernel(const StreamParams* __restrict__ params, int stream0
     const uint32_t n = P.n_points;
     const uint32_t tile0 = blockIdx.x * (THREADS * kPointsPerLane);
     if (tile0 >= n) return;
-    DepthSource<DDIST, CDIST, Mth> src{fp.depth[s]};
-    dense_tile<DepthSource<DDIST, CDIST, Mth>, THREADS>(P, src, fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage);
+    if constexpr (Mth::kRowConst) {
+        dense_tile_rowc<Mth, THREADS>(P, fp.depth[s], fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage);
+    } else {
+        DepthSource<DDIST, CDIST, Mth> src{fp.depth[s]};
+        dense_tile<DepthSource<DDIST, CDIST, Mth>, THREADS>(P, src, fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage);
+    }
 }
 
 // K frame-sets of the same streams in one launch: blockIdx.z = frame-set, blockIdx.y = stream. Same tile code, same
@@ -2283,6 +2475,14 @@ hipError_t launch_fused_dense(const StreamParams* d_params, int stream0, int n_l
                                         d_params, stream0, fp, reinterpret_cast<uint8_t*>(d_payload)); \
                           else hipLaunchKernelGGL((pcs_fused_dense_kernel<DD, CD, M>), grid, dim3(kBlockThreads), 0, st, \
                                         d_params, stream0, fp, reinterpret_cast<uint8_t*>(d_payload)); } while (0)
+    if (math == MathSel::CertRowConstNoOvf) {
+        // the colour window is requested in 16-byte pieces and pixel (0, 0)'s word by a scalar load, a lane's Z16 quad by one 16-byte
+        // load (DepthSource::fast): 16-aligned rasters only; the rest of this launch's frames take CertIdentNoOvf's kernel
+        bool aligned = !any_ddist && !any_cdist;
+        for (int k = 0; k < n_launch; k++) aligned &= ((((uintptr_t)fp.color[k]) | ((uintptr_t)fp.depth[k])) & 15u) == 0;
+        if (aligned) { L(false, false, CertRowConstNoOvf); return hipGetLastError(); }
+        math = MathSel::CertIdentRNoOvf;
+    }
     if (math != MathSel::Ieee && !any_ddist) {
         const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
         const bool noovf = (math == MathSel::CertNoOvf || math == MathSel::CertIdentRNoOvf) && !any_cdist;
