@@ -77,16 +77,23 @@ int pcs_oracle_pack_scalar_variant(const pcs_stream_config* sc, const float* ver
     for (int i = 0; i < n_points; i++) {
         const float* p = vertices + 3 * (size_t)i;
         const float* uv = texcoords + 2 * (size_t)i;
-        /* :648-649 int(u*w + .5f) */
-        int32_t x = pcs_o_cvtt(uv[0] * (float)W + 0.5f);
-        int32_t y = pcs_o_cvtt(uv[1] * (float)H + 0.5f);
+        /* :648-649 int(u*w + .5f). As the reference's build compiles it (g++ -O3 -mfma, GNU C++'s default -ffp-contract=fast) the
+         * product and the sum are ONE fused multiply-add; this file is built with contraction off, so it is spelled out. */
+        int32_t x = pcs_o_cvtt(fmaf(uv[0], (float)W, 0.5f));
+        int32_t y = pcs_o_cvtt(fmaf(uv[1], (float)H, 0.5f));
         if (x < 0) x = 0; if (x > W - 1) x = W - 1;
         if (y < 0) y = 0; if (y > H - 1) y = H - 1;
         size_t idx = (size_t)x * (size_t)sc->color_bpp + (size_t)y * (size_t)sc->color_stride;
         int16_t* o = out + PCS_POINT_SHORTS * (size_t)i;
         for (int r = 0; r < 3; r++) {
-            /* :654-656 textbook order; :658-660 `* CONV_RATE` with CONV_RATE the double 1000.0 */
-            float a = M[4 * r] * p[0] + M[4 * r + 1] * p[1] + M[4 * r + 2] * p[2] + M[4 * r + 3];
+            /* :654-656 textbook order ((m0*x + m1*y) + m2*z) + t, contracted by that build into: a rounded product, two fused
+             * multiply-adds, a rounded sum (tests/test_reference_pin.py holds this to the compiled reference's bytes; with every
+             * product rounded on its own, 2 records of 3072 differ once coordinates reach tens of metres);
+             * :658-660 `* CONV_RATE` with CONV_RATE the double 1000.0 */
+            float a = M[4 * r + 1] * p[1];            /* the product it keeps is m1*y; m0*x is fused into the first sum */
+            a = fmaf(M[4 * r], p[0], a);
+            a = fmaf(M[4 * r + 2], p[2], a);
+            a = a + M[4 * r + 3];
             double s = (double)a * 1000.0;
             int32_t q = (s >= -2147483648.0 && s < 2147483648.0) ? (int32_t)s : INT32_MIN;
             o[r] = (int16_t)(uint16_t)((uint32_t)q & 0xFFFFu);

@@ -7,11 +7,10 @@
  * thing shipped.
  *
  * PARITY PIN STATUS
- *   pack path (a1/a2/a7): pinned by the eight known-answer vectors the surveyor printed from the
- *     compiled reference TU (`-m -t1`; SURVEY.md Appendix B -> tests/golden/kat_appendix_b.json).
- *     The reference ships no tests or golden vectors of its own, and its translation unit cannot
- *     be rebuilt here under the rules (it needs <librealsense2/rs.hpp>, absent from the image; no
- *     stand-in headers), so there is no oracle/_ref. Beyond those eight points: PARITY UNPINNED.
+ *   pack path (a1/a2/a3, `-c` order included): pinned to bytes written by the reference's own translation
+ *     unit, compiled with its own flags into oracle/_ref/ (oracle/ref/, oracle/ref_pin.py; never committed):
+ *     tests/golden/ref_pin/ and tests/test_reference_pin.py. The eight vectors of SURVEY.md Appendix B
+ *     (tests/golden/kat_appendix_b.json) are part of that set. a7's concatenation has no arithmetic.
  *   deprojection (a5): arithmetic lives in librealsense2 (apt package, unpinned: Dockerfile:20-23),
  *     absent from /root/reference. Restated from its published pinhole model (SURVEY.md
  *     Appendix E). No reference test pins it: PARITY UNPINNED.
@@ -44,10 +43,11 @@ void pcs_oracle_deproject_flags(const pcs_stream_config* sc, const uint16_t* dep
 int pcs_oracle_pack(const pcs_stream_config* sc, const float* vertices, const float* texcoords,
                     int n_points, const uint8_t* color, uint32_t flags, int downsample, int16_t* out);
 
-/* a3: the scalar (non -m) variant, src/pcs-camera-optimized.cpp:620-667: textbook-order affine with
- * separate roundings, then x1000 in DOUBLE. Documented variant only — NOT the parity target (it
- * differs from -m by +-1 LSB on ~2.5 % of shorts) and the reference's own result depends on the
- * compiler's contraction choices. */
+/* a3: the scalar (non -m) variant, src/pcs-camera-optimized.cpp:620-667: textbook-order affine, then
+ * x1000 in DOUBLE. Documented variant only — NOT the parity target (it differs from -m by +-1 LSB on
+ * ~2.5 % of shorts). The reference's own result depends on the compiler's contraction choices; this
+ * restates what g++ with the reference's flags does (product, two FMAs, sum; the texcoord as one FMA)
+ * and is held to that build's bytes by tests/test_reference_pin.py. */
 int pcs_oracle_pack_scalar_variant(const pcs_stream_config* sc, const float* vertices,
                                    const float* texcoords, int n_points, const uint8_t* color, int16_t* out);
 

@@ -1,0 +1,141 @@
+"""Loader and wrapper of oracle/_ref/libpcs_ref.so: the reference's own sendXYZRGBPointcloud, compiled.
+
+TEST INFRASTRUCTURE ONLY, like pcs_oracle.py: tests/ and tests/golden/make_ref_pin_golden.py use it; nothing under
+pointcloud_stitching_amd/, no smoke() and no benchmark does. The library is built by `make -C oracle ref
+REF_DIR=<reference checkout>` (oracle/Makefile; __graft_entry__.build() runs it when the checkout is there) from
+oracle/ref/ref_harness.cpp, which includes the reference translation unit by path. oracle/_ref/ is never committed.
+
+The checkout is looked for at $PCS_REFERENCE_DIR, default /root/reference.
+
+The reference keeps the raster geometry, the matrix and its switches in globals, so calls are serialised here and the
+harness resets its `initialized` latch on every call.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import fcntl
+import os
+import subprocess
+import threading
+from typing import Optional, Tuple
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+REF_LIB_DIR = os.path.join(_HERE, "_ref")
+REF_LIB_PATH = os.path.join(REF_LIB_DIR, "libpcs_ref.so")
+REF_TU_RELPATH = os.path.join("src", "pcs-camera-optimized.cpp")
+_lock = threading.Lock()
+_lib = None
+
+
+def reference_dir() -> str:
+    return os.environ.get("PCS_REFERENCE_DIR", "/root/reference")
+
+
+def reference_present() -> bool:
+    return os.path.isfile(os.path.join(reference_dir(), REF_TU_RELPATH))
+
+
+def build(verbose: bool = False) -> Optional[str]:
+    """Compile the reference into oracle/_ref/ when its checkout exists; otherwise leave oracle/_ref/ as it is.
+    Returns the library's path, or None when there is nothing to build from. Raises if the compile itself fails."""
+    if not reference_present():
+        return None
+    with open(os.path.join(_HERE, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        r = subprocess.run(["make", "-C", _HERE, "ref", "REF_DIR=" + os.path.abspath(reference_dir())],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if verbose:
+        print(r.stdout)
+    if r.returncode != 0:
+        raise RuntimeError("reference build failed:\n" + r.stdout[-4000:])
+    return REF_LIB_PATH
+
+
+def available() -> bool:
+    """The compiled reference can be loaded (it was built here, or it travelled with the tree)."""
+    try:
+        lib()
+        return True
+    except OSError:
+        return False
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        L = C.CDLL(REF_LIB_PATH)        # OSError when oracle/_ref/ is empty
+        L.pcs_ref_buf_size.restype = C.c_int
+        L.pcs_ref_compiler.restype = C.c_char_p
+        L.pcs_ref_flags.restype = C.c_char_p
+        L.pcs_ref_send.restype = C.c_int
+        L.pcs_ref_send.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib = L
+    return _lib
+
+
+def buf_size() -> int:
+    return int(lib().pcs_ref_buf_size())
+
+
+def compiler() -> dict:
+    return {"compiler": "g++ " + lib().pcs_ref_compiler().decode(), "flags": lib().pcs_ref_flags().decode()}
+
+
+def buffer_bytes(n: int) -> int:
+    """The size of the buffer send() hands to the reference for n points: it clears BUF_SIZE bytes and bounds nothing."""
+    return max(2 * buf_size(), 4 + 10 * int(n))
+
+
+def send(vertices, texcoords, color, width: int, height: int, bpp: int, stride: int, m16, *, simd: bool = True,
+         cutoff: bool = False, threads: int = 1, prefill: int = 0x5A5A) -> Tuple[np.ndarray, int]:
+    """sendXYZRGBPointcloud on caller arrays. Returns (the whole int16 buffer, prefilled with `prefill` before the
+    call; the returned payload size in bytes). The point count must be a multiple of 4 on the `-m` path."""
+    vtx = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    tex = np.ascontiguousarray(texcoords, np.float32).reshape(-1, 2)
+    col = np.ascontiguousarray(color, np.uint8).reshape(-1)
+    m = np.ascontiguousarray(np.asarray(m16, np.float32).reshape(-1))
+    n = vtx.shape[0]
+    if tex.shape[0] != n or m.size != 16:
+        raise ValueError("need n vertices, n texcoords and a 4x4 matrix")
+    if simd and n % 4:
+        raise ValueError("the reference's -m loop reads four points per step: n must be a multiple of 4 (see pack())")
+    if col.size < stride * (height - 1) + (width - 1) * bpp + 3:
+        raise ValueError("colour raster too small for the last pixel's three bytes")
+    buf = np.full((buffer_bytes(n) + 1) // 2, prefill, np.uint16).view(np.int16)
+    with _lock:
+        size = lib().pcs_ref_send(vtx.ctypes.data, tex.ctypes.data, n, col.ctypes.data, int(width), int(height),
+                                  int(bpp), int(stride), m.ctypes.data, int(bool(simd)), int(bool(cutoff)),
+                                  int(threads), buf.ctypes.data)
+    return buf, int(size)
+
+
+def pack(vertices, texcoords, color, width: int, height: int, bpp: int, stride: int, m16, *, simd: bool = True,
+         cutoff: bool = False, threads: int = 1) -> np.ndarray:
+    """The records sendXYZRGBPointcloud wrote, int16[count, 5]. Dense `-m` with n % 4 != 0: the inputs are padded with
+    zero points to a multiple of 4 and the first n records returned (a dense record depends on its own point only).
+    `-c -m` is refused for such n: the reversed mask makes point k's fate depend on point 3 - k of its group."""
+    vtx = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    tex = np.ascontiguousarray(texcoords, np.float32).reshape(-1, 2)
+    n = vtx.shape[0]
+    pad = (-n) % 4 if simd else 0
+    if pad:
+        if cutoff:
+            raise ValueError("-c -m is only driven with n % 4 == 0")
+        vtx = np.concatenate([vtx, np.zeros((pad, 3), np.float32)])
+        tex = np.concatenate([tex, np.zeros((pad, 2), np.float32)])
+    buf, size = send(vtx, tex, color, width, height, bpp, stride, m16, simd=simd, cutoff=cutoff, threads=threads)
+    assert size % 10 == 0
+    count = size // 10
+    if not cutoff:
+        assert count == n + pad
+        count = n
+    return buf[2:2 + 5 * count].reshape(-1, 5).copy()
+
+
+def pack_config(sc, vertices, texcoords, color, **kw) -> np.ndarray:
+    """pack() with the raster geometry and the matrix taken from a StreamConfig."""
+    return pack(vertices, texcoords, color, sc.color.width, sc.color.height, sc.color_bpp, sc.color_stride,
+                list(sc.cam_to_world), **kw)

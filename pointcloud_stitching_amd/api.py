@@ -241,6 +241,13 @@ class PcsContext:
         cc = (C.c_void_p * k)(*d_counts) if d_counts is not None else None
         self._check(self._lib.pcs_process_frames_device_batch(self._h, k, dp, cp, pp, payload_shorts, cc))
 
+    def copy_pointcloud_xyzrgb_to_buffer_device(self, stream: int, d_vertices: int, d_texcoords: int, n_points: int,
+                                                d_color: int, d_pc_buffer: int, d_out_points: int = 0) -> None:
+        """The a2 twin on device pointers (ints), asynchronous on the context's stream; d_out_points (optional) receives one int."""
+        self._check(self._lib.pcs_copy_pointcloud_xyzrgb_to_buffer_device(
+            self._h, int(stream), d_vertices or None, d_texcoords or None, int(n_points), d_color or None, d_pc_buffer or None,
+            d_out_points or None))
+
     def copy_pointclouds_xyzrgb_to_buffer_device(self, clouds: Sequence[Tuple[int, int, int, int, int, int]],
                                                  d_out_points: int = 0) -> None:
         """Batched a2 twin on device pointers: clouds = [(stream, n_points, d_vertices, d_texcoords, d_color, d_out)]."""

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Regenerates tests/golden/synthetic_digests.json: SHA-256 of the synthetic frames and of the oracle's
 packed output on them. Run from the repo root: python tests/golden/make_golden.py
-(The reference cannot be executed here — see oracle/pcs_oracle.h — so these digests pin the oracle
-against regressions; the reference-produced vectors are tests/golden/kat_appendix_b.json.)"""
+(These digests pin the oracle against regressions; the outputs of the compiled reference itself are
+tests/golden/ref_pin/, written by make_ref_pin_golden.py, and tests/golden/kat_appendix_b.json.)"""
 import hashlib
 import json
 import os

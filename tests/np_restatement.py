@@ -60,6 +60,18 @@ def pack_np(sc, V, T, color):
     return out
 
 
+def cutoff_keep_np(V, compat=True):
+    """The `-c` predicate on camera-frame z and x: 0 < z <= 1.5 and -2 < x <= 2 (NaN fails every comparison). With compat, as the
+    `-m` path applies it: inside each aligned group of four, point k is kept or dropped by the verdict on point 3 - k."""
+    V = np.asarray(V, np.float32)
+    with np.errstate(all="ignore"):
+        ok = (V[:, 2] > np.float32(0)) & (V[:, 2] <= np.float32(1.5)) & (V[:, 0] > np.float32(-2)) & (V[:, 0] <= np.float32(2))
+    if compat:
+        g = (ok.size // 4) * 4
+        ok = np.concatenate([ok[:g].reshape(-1, 4)[:, ::-1].reshape(-1), ok[g:]])
+    return ok
+
+
 def deproject_np(sc, depth, half_pixel=False):
     f32 = np.float32
     di, ci = sc.depth, sc.color
