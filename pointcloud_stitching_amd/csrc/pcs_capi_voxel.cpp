@@ -1,6 +1,6 @@
 // pcs_capi_voxel.cpp — the voxel-grid part of the C ABI of libpcs_hip.so (include/pcs_hip.h): the grid of a payload, of the rasters, of
 // partials (the exchange format of a multi-GPU grid) and the sink several contexts of one device pre-aggregate into. The kernels and
-// what bounds them: pcs_voxel.hip, pcs_kernels.hip (the raster / payload readers), DESIGN.md section 10. Not in the reference (it includes
+// what bounds them: pcs_voxel.hip, pcs_kernels_voxel.hip (the raster / payload readers), DESIGN.md section 10. Not in the reference (it includes
 // pcl/filters/voxel_grid.h and never instantiates it, src/pcs-multicamera-optimized.cpp:17): BASELINE configs[4] asks for it.
 
 #include <cstdarg>
@@ -74,6 +74,44 @@ int pcs_voxel_grid_device_counted(pcs_ctx* c, const int16_t* d_payload, const in
     return voxel_grid_device_impl(c, d_payload, max_points, d_n_points, leaf_mm, d_out, out_shorts, d_out_points);
 }
 
+// Which route the voxel grid of the rasters takes: true = the raster reader (launch_raster_voxel_partials), false = through the
+// stitched cloud. A stride is defined on the ORDER of the kept points, so it always takes the stitched cloud.
+// Rasters whose width is a multiple of 8 are read in square patches and the direct route wins at every leaf
+// (16 x 1080p: 0.26 vs 0.46 ms at 50 mm, 0.52 vs 0.91 ms at 25 mm, 1.64 vs 2.57 ms at 10 mm). Other rasters are read
+// in runs of 4096 consecutive pixels; below ~36 mm (on the synthetic scene) such a run holds more voxels than a
+// workgroup's LDS table takes gracefully and the payload reader, fed by the ordered compaction, is the faster route
+// (25 mm: 0.93 vs 1.11 ms). Same result either way.
+static bool voxel_reads_rasters(const pcs_ctx* c, const uint16_t* const* d_depth, int leaf_mm)
+{
+    if (c->downsample != 1) return false;
+    bool all_patch = true;
+    for (int s = 0; s < c->n_streams; s++) all_patch &= (c->h_params[s].W & 7) == 0 && ((uintptr_t)d_depth[s] & 15u) == 0;
+    return all_patch || leaf_mm >= 36;
+}
+
+// The raster reader over all streams of the context, kLaunchStreams per launch, appending to `vs`.
+static int launch_raster_voxel_partials(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* const* d_color, const VoxelStage& vs)
+{
+    const int S = c->n_streams;
+    for (int s0 = 0; s0 < S; s0 += kLaunchStreams) {
+        const int nl = std::min(kLaunchStreams, S - s0);
+        FramePtrs fp{};
+        uint32_t mp = 0, mw = 0, mh = 0;
+        bool fast = true, ident = true, rowc = true, patch_ok = true;
+        for (int k = 0; k < nl; k++) {
+            const StreamParams& q = c->h_params[s0 + k];
+            fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k];
+            mp = std::max(mp, q.n_points);
+            mw = std::max(mw, (uint32_t)q.W); mh = std::max(mh, q.n_points / (uint32_t)q.W);
+            patch_ok &= (q.W & 7) == 0 && ((uintptr_t)d_depth[s0 + k] & 15u) == 0;
+            fast &= q.cert_fast != 0; ident &= q.ident_r != 0; rowc &= q.ident_r == 2;
+        }
+        const MathSel sel = !fast ? MathSel::Ieee : (ident ? (rowc ? MathSel::CertRowConst : MathSel::CertIdentR) : MathSel::Cert);
+        HIPCHK(c, launch_fused_voxel_partials(c->d_params, s0, nl, mp, mw, mh, patch_ok, c->any_ddist || c->any_cdist, c->flags, sel, fp, vs, c->stream));
+    }
+    return PCS_OK;
+}
+
 int pcs_process_frames_voxel_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* const* d_color, int leaf_mm,
                                     int16_t* d_out, size_t out_shorts, int32_t* d_out_points)
 try {
@@ -90,17 +128,8 @@ try {
         return fail(c, PCS_ERR_CAPACITY, "output holds %zu shorts; the worst case (every pixel its own voxel) needs %zu",
                     out_shorts, cap * PCS_POINT_SHORTS);
     DeviceGuard guard(c->device);
-    // Rasters whose width is a multiple of 8 are read in square patches and the direct route wins at every leaf
-    // (16 x 1080p: 0.26 vs 0.46 ms at 50 mm, 0.52 vs 0.91 ms at 25 mm, 1.64 vs 2.57 ms at 10 mm). Other rasters are read
-    // in runs of 4096 consecutive pixels; below ~36 mm (on the synthetic scene) such a run holds more voxels than a
-    // workgroup's LDS table takes gracefully and the payload reader, fed by the ordered compaction, is the faster route
-    // (25 mm: 0.93 vs 1.11 ms). Same result either way. PCS_VOXEL_FUSED=0/1 forces one or the other.
-    static const int fused_env = [] { const char* v = getenv("PCS_VOXEL_FUSED"); return v ? atoi(v) : -1; }();
-    bool all_patch = true;
-    for (int s = 0; s < S; s++) all_patch &= (c->h_params[s].W & 7) == 0 && ((uintptr_t)d_depth[s] & 15u) == 0;
-    const bool fused = fused_env >= 0 ? fused_env != 0 : (all_patch || leaf_mm >= 36);
-    if (c->downsample != 1 || !fused) {
-        // (the stride is defined on the ORDER of the kept points: build the stitched cloud, then its voxel grid)
+    if (!voxel_reads_rasters(c, d_depth, leaf_mm)) {
+        // build the stitched cloud, then its voxel grid
         int rc = ensure(c, c->s_payload, c->s_payload_cap, cap * PCS_POINT_BYTES + 16);
         if (rc) return rc;
         rc = run_fused_device(c, d_depth, d_color, c->s_payload, cap * PCS_POINT_SHORTS, c->d_counts, true);
@@ -118,22 +147,8 @@ try {
     }
     VoxelStage vs{};
     HIPCHK(c, voxel_begin((uint32_t)cap, leaf_mm, c->s_voxel_ws, c->s_voxel_ws_cap, &c->vox_state, &vs, c->stream));
-    for (int s0 = 0; s0 < S; s0 += kLaunchStreams) {
-        const int nl = std::min(kLaunchStreams, S - s0);
-        FramePtrs fp{};
-        uint32_t mp = 0, mw = 0, mh = 0;
-        bool fast = true, ident = true, rowc = true, patch_ok = true;
-        for (int k = 0; k < nl; k++) {
-            const StreamParams& q = c->h_params[s0 + k];
-            fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k];
-            mp = std::max(mp, q.n_points);
-            mw = std::max(mw, (uint32_t)q.W); mh = std::max(mh, q.n_points / (uint32_t)q.W);
-            patch_ok &= (q.W & 7) == 0 && ((uintptr_t)d_depth[s0 + k] & 15u) == 0;
-            fast &= q.cert_fast != 0; ident &= q.ident_r != 0; rowc &= q.ident_r == 2;
-        }
-        const MathSel sel = !fast ? MathSel::Ieee : (ident ? (rowc ? MathSel::CertRowConst : MathSel::CertIdentR) : MathSel::Cert);
-        HIPCHK(c, launch_fused_voxel_partials(c->d_params, s0, nl, mp, mw, mh, patch_ok, c->any_ddist || c->any_cdist, c->flags, sel, fp, vs, c->stream));
-    }
+    rc = launch_raster_voxel_partials(c, d_depth, d_color, vs);
+    if (rc) return rc;
     HIPCHK(c, voxel_finish((uint32_t)cap, leaf_mm, c->s_voxel_ws, c->s_voxel_ws_cap, &c->vox_state, d_out, d_out_points, c->stream));
     if (c->kernel_timing) {
         HIPCHK(c, hipEventRecord(ev.second, c->stream));
@@ -151,12 +166,8 @@ static int run_voxel_frontend(pcs_ctx* c, const uint16_t* const* d_depth, const 
 {
     const int S = c->n_streams;
     const size_t cap = c->max_payload_points;
-    static const int fused_env = [] { const char* v = getenv("PCS_VOXEL_FUSED"); return v ? atoi(v) : -1; }();
-    bool all_patch = true;
-    for (int s = 0; s < S; s++) all_patch &= (c->h_params[s].W & 7) == 0 && ((uintptr_t)d_depth[s] & 15u) == 0;
-    const bool fused = fused_env >= 0 ? fused_env != 0 : (all_patch || leaf_mm >= 36);      // as pcs_process_frames_voxel_device
-    if (c->downsample != 1 || !fused) {
-        // the stride is defined on the ORDER of the kept points: build this GPU's stitched cloud, pre-aggregate that
+    if (!voxel_reads_rasters(c, d_depth, leaf_mm)) {
+        // build this GPU's stitched cloud, pre-aggregate that
         int rc = ensure(c, c->s_payload, c->s_payload_cap, cap * PCS_POINT_BYTES + 16);
         if (rc) return rc;
         rc = run_fused_device(c, d_depth, d_color, c->s_payload, cap * PCS_POINT_SHORTS, c->d_counts, true);
@@ -164,23 +175,7 @@ static int run_voxel_frontend(pcs_ctx* c, const uint16_t* const* d_depth, const 
         if (cap) HIPCHK(c, launch_payload_voxel_partials(c->s_payload, (uint32_t)cap, c->d_counts + S, vs, c->stream));
         return PCS_OK;
     }
-    for (int s0 = 0; s0 < S; s0 += kLaunchStreams) {
-        const int nl = std::min(kLaunchStreams, S - s0);
-        FramePtrs fp{};
-        uint32_t mp = 0, mw = 0, mh = 0;
-        bool fast = true, ident = true, rowc = true, patch_ok = true;
-        for (int k = 0; k < nl; k++) {
-            const StreamParams& q = c->h_params[s0 + k];
-            fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k];
-            mp = std::max(mp, q.n_points);
-            mw = std::max(mw, (uint32_t)q.W); mh = std::max(mh, q.n_points / (uint32_t)q.W);
-            patch_ok &= (q.W & 7) == 0 && ((uintptr_t)d_depth[s0 + k] & 15u) == 0;
-            fast &= q.cert_fast != 0; ident &= q.ident_r != 0; rowc &= q.ident_r == 2;
-        }
-        const MathSel sel = !fast ? MathSel::Ieee : (ident ? (rowc ? MathSel::CertRowConst : MathSel::CertIdentR) : MathSel::Cert);
-        HIPCHK(c, launch_fused_voxel_partials(c->d_params, s0, nl, mp, mw, mh, patch_ok, c->any_ddist || c->any_cdist, c->flags, sel, fp, vs, c->stream));
-    }
-    return PCS_OK;
+    return launch_raster_voxel_partials(c, d_depth, d_color, vs);
 }
 
 // ---- voxel partials (exchange format of the multi-GPU voxel grid) ------------------------------------

@@ -1,4 +1,4 @@
-// pcs_device.h — structures shared by the HIP kernels (pcs_kernels.hip) and the C-ABI host layer
+// pcs_device.h — structures shared by the HIP kernels (pcs_kernels.hip, pcs_kernels_voxel.hip, pcs_voxel.hip) and the C-ABI host layer
 // (pcs_capi.cpp). Internal; the public surface is include/pcs_hip.h.
 #pragma once
 
@@ -187,7 +187,7 @@ hipError_t launch_voxel_grid(const int16_t* d_payload, uint32_t n_points, const 
                              size_t ws_bytes, VoxelWsState* ws, int16_t* d_out, int32_t* d_out_points, hipStream_t st);
 
 // The same pipeline fed from the rasters (pcs_process_frames_voxel_device): voxel_begin carves the workspace and clears
-// the counters, launch_fused_voxel_partials (pcs_kernels.hip) appends the partials, voxel_finish sorts and reduces.
+// the counters, launch_fused_voxel_partials (pcs_kernels_voxel.hip) appends the partials, voxel_finish sorts and reduces.
 struct VoxelStage {
     unsigned long long* keys;
     unsigned int*       idx;           // nullptr with idx_bits == 0: raw keys only (exchange format)
@@ -223,7 +223,7 @@ hipError_t launch_voxel_from_partials(const unsigned long long* d_keys, const vo
                                       int16_t* d_out, int32_t* d_out_points, hipStream_t st);
 // fault injection: the next `launches` bucket-tail launches end flagged (*out_points = -1), as after a stalled workgroup
 void inject_voxel_stall(int launches);
-// the same table fed from a 16-byte aligned payload (pcs_kernels.hip; the unaligned forms stay in pcs_voxel.hip)
+// the same table fed from a 16-byte aligned payload (pcs_kernels_voxel.hip; the unaligned forms stay in pcs_voxel.hip)
 hipError_t launch_payload_voxel_partials(const int16_t* d_payload, uint32_t n_points, const int32_t* d_n_points,
                                          const VoxelStage& vs, hipStream_t st);
 // max_w / max_h: the largest raster of the launch; patch_ok: every raster's width is a multiple of 8 (square patches)

@@ -1,4 +1,4 @@
-// pcs_vox_tiling.h — how a launch of the voxel pipeline's raster reader (pcs_kernels.hip: pcs_fused_voxel_partials_kernel) cuts
+// pcs_vox_tiling.h — how a launch of the voxel pipeline's raster reader (pcs_kernels_voxel.hip: pcs_fused_voxel_partials_kernel) cuts
 // the rasters into workgroups. Plain C++ without a HIP header, so that the host logic — every square of every raster is visited
 // exactly once, whatever the geometry — is tested on the CPU (tests/test_vox_tiling.py compiles this file with g++); the kernel and
 // its launcher #include it inside their namespace.
@@ -50,7 +50,7 @@ inline VoxTiling vox_tiling_make(unsigned max_w, unsigned max_h, unsigned rows, 
 // go out as partials of their own), by the tail that follows (`regions`: a warm bucket call's workgroups end with the dearer flush
 // and gain most from fewer, larger tables) and capped so that the launch still fills the chip twice (launch_squares = the launch's
 // pixels / 4096; 3 % slack: 16 x 1080p are 8112 squares and take 8 per table). The measurements behind the thresholds:
-// pcs_kernels.hip, launch_fused_voxel_partials. force > 0 (PCS_VOXEL_ROUNDS) overrides the rule.
+// pcs_kernels_voxel.hip, launch_fused_voxel_partials. force > 0 overrides the rule (the launcher passes 0).
 struct VoxPatchShape { int squares, rx; };
 inline VoxPatchShape vox_patch_shape(unsigned leaf_mm, bool regions, unsigned long long launch_squares, int force)
 {

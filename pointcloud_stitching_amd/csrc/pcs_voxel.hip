@@ -835,7 +835,7 @@ void pcs_voxel_fixup_kernel(unsigned int* __restrict__ ctl, const BlockPiece* __
 // its share of the partials — consecutive frame-sets of a camera rig differ by sensor noise. A workspace without splitters
 // for this leaf runs a one-workgroup sample sort first (S0: 4096 evenly spaced keys, bitonic in LDS).
 // WARM CALLS: the splitters of a call are the previous call's, known before it starts. From a workspace's second bucket call on
-// the pre-aggregation (pcs_kernels.hip: vox_table_flush_regions) therefore does P1 - P3 itself: every workgroup finds its
+// the pre-aggregation (pcs_kernels_voxel.hip: vox_table_flush_regions) therefore does P1 - P3 itself: every workgroup finds its
 // partials' buckets and appends them to the buckets' REGIONS (B regions of `cap` slots in keys_r / part_r, filled through one
 // cursor per bucket; B and cap left behind by the previous call's G1 together with zeroed cursors — two sets, used alternately).
 // The tail is then G1 alone. A partial that finds its region full goes to the general list (keys_a / part, tagged with its bucket
@@ -849,7 +849,7 @@ void pcs_voxel_fixup_kernel(unsigned int* __restrict__ ctl, const BlockPiece* __
 #define PCS_BKT 1024
 #endif
 constexpr unsigned int kBkt = PCS_BKT, kBktSample = 4096;      // buckets: 256 .. 1024, a power of two
-static_assert(kBkt == kVoxBuckets, "the pre-aggregation's region flush (pcs_kernels.hip) partitions into kVoxBuckets ranges");
+static_assert(kBkt == kVoxBuckets, "the pre-aggregation's region flush (pcs_kernels_voxel.hip) partitions into kVoxBuckets ranges");
 constexpr unsigned int kBktChunk = 4096, kBktThreads = 512, kBktPer = kBktChunk / kBktThreads;     // 8 elements per lane
 constexpr unsigned int kBktGrid = 512;
 #ifndef PCS_BKT_MIN_PER
@@ -1093,7 +1093,7 @@ void pcs_vox_bkt_scatter_kernel(const unsigned long long* __restrict__ keys, con
 
 // PLACE: the warm form of P1 - P3 for CALLER-HELD partials (the root of a multi-GPU voxel grid: pcs_voxel_grid_from_partials_device on
 // a workspace whose previous call left splitters, region sizes and zeroed cursors): every (key, partial) of the list straight into its
-// bucket's region, exactly what the raster reader's flush does for its own partials (pcs_kernels.hip: vox_table_flush_regions) — the
+// bucket's region, exactly what the raster reader's flush does for its own partials (pcs_kernels_voxel.hip: vox_table_flush_regions) — the
 // bucket by binary search in the splitters (8 KiB of LDS per workgroup, ten dependent LDS reads per key, a lane's keys side by side), a
 // returning LDS add ranks the element among its chunk's for that bucket, ONE returning global add per bucket a chunk touches reserves
 // the slots. An element that finds its region full goes to the general list (keys_l / part_l, its bucket in bucket_of, counted in
@@ -1908,18 +1908,15 @@ hipError_t plan_for(uint32_t n_points, int leaf_mm, void* d_ws, size_t ws_bytes,
     // one 64-bit word per element when the packed key and the partial's index fit together
     pl.idx_bits = 1;
     while ((1ull << pl.idx_bits) < (unsigned long long)n_points) pl.idx_bits++;
-    static const int pack_ok = [] { const char* v = getenv("PCS_VOXEL_PACKED"); return v ? atoi(v) : 1; }();
-    if (!pack_ok || 3u * pl.bits + pl.idx_bits > 64u) pl.idx_bits = 0;
+    if (3u * pl.bits + pl.idx_bits > 64u) pl.idx_bits = 0;
     // A pass is skipped when the varying bits fit one digit less than the key's 3 * bits. A scene some 8 m across has
     // 3 * log2(8 m / leaf) varying bits: 30 of 39 at 10 mm (3 passes instead of 4: 16 x 1080p from the rasters 1.36 -> 1.22
     // ms), 27 of 36 at 20 mm (0.65 -> 0.61 ms), 24 of 33 at 50 mm (3 of 3: nothing to gain), 21 of 30 at 100 mm (2 of 3).
     // Recording the bits costs the raster reader ~9 us per 16 x 1080p frame-set and a skipped pass is still three (empty)
     // launches, so it only pays where a pass is long: it is asked for when the key needs four or more passes (leaves below
     // 33 mm) — at 100 / 200 mm, where the sort handles ~0.1 M partials, it measured +5 us. A decision about speed only:
-    // without the record every bit counts as varying. PCS_VOXEL_TRACK=0/1 overrides.
-    static const int track_env = [] { const char* v = getenv("PCS_VOXEL_TRACK"); return v ? atoi(v) : -1; }();
+    // without the record every bit counts as varying.
     pl.track_bits = 3u * pl.bits > 3u * kRadixBits;
-    if (track_env >= 0) pl.track_bits = track_env != 0;
     pl.bucket = takes_bucket_tail(n_points, leaf_mm, ws);
     if (pl.bucket) {
         pl.idx_bits = 0;              // raw keys, as in the exchange format: the bucket tail moves the partials themselves
@@ -2064,10 +2061,8 @@ hipError_t launch_voxel_grid(const int16_t* d_payload, uint32_t n_points, const 
     const Workspace& w = pl.w;
     const unsigned int per_block = (unsigned)kAggThreads * (unsigned)kAggPerLane;
     const dim3 agg_grid((n_points + per_block - 1) / per_block);
-    static const int wide_ok = [] { const char* v = getenv("PCS_VOXEL_WIDE"); return v ? atoi(v) : 1; }();
-    static const int lane8_ok = [] { const char* v = getenv("PCS_VOXEL_LANE8"); return v ? atoi(v) : 1; }();
-    if (lane8_ok && ((uintptr_t)d_payload & 15u) == 0u) {
-        // 16-byte aligned payload: the reader that shares its table code with the raster reader (pcs_kernels.hip)
+    if (((uintptr_t)d_payload & 15u) == 0u) {
+        // 16-byte aligned payload: the reader that shares its table code with the raster reader (pcs_kernels_voxel.hip)
         VoxelStage vs{};
         vs.keys = w.keys_a; vs.idx = pl.bucket ? nullptr : w.idx_a; vs.part = w.part; vs.n_runs = w.ctl;
         vs.leaf = (uint32_t)leaf_mm; vs.div_inv = pl.dv.inv; vs.div_c = pl.dv.c; vs.bits = pl.bits; vs.idx_bits = pl.idx_bits;
@@ -2080,7 +2075,7 @@ hipError_t launch_voxel_grid(const int16_t* d_payload, uint32_t n_points, const 
         // counts, no pass is skipped; nor do they fill regions
         pl.track_bits = false;
         pl.regions = false;
-        if (wide_ok && n_points >= 2 && ((uintptr_t)d_payload & 3u) == 0u)
+        if (n_points >= 2 && ((uintptr_t)d_payload & 3u) == 0u)
             hipLaunchKernelGGL(pcs_voxel_partials_kernel<true>, agg_grid, dim3(kAggThreads), 0, st, d_payload, n_points, d_n_points, pl.dv,
                                pl.bits, pl.idx_bits, w.keys_a, w.idx_a, w.part, w.ctl);
         else
@@ -2090,7 +2085,7 @@ hipError_t launch_voxel_grid(const int16_t* d_payload, uint32_t n_points, const 
     return finish_call(*ws, sort_and_reduce(pl, n_points, d_out, d_out_points, st), pl.bucket ? leaf_mm : 0);
 }
 
-// Raster source (pcs_kernels.hip: launch_fused_voxel_partials fills the stage between these two calls).
+// Raster source (pcs_kernels_voxel.hip: launch_fused_voxel_partials fills the stage between these two calls).
 hipError_t voxel_begin(uint32_t capacity_points, int leaf_mm, void* d_ws, size_t ws_bytes, VoxelWsState* ws, VoxelStage* stage,
                        hipStream_t st)
 {

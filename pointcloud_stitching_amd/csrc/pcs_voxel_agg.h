@@ -1,5 +1,5 @@
 // pcs_voxel_agg.h — the pieces of the voxel pre-aggregation that both its sources share: the payload reader
-// (pcs_voxel.hip) and the raster reader that never materialises the stitched payload (pcs_kernels.hip).
+// (pcs_voxel.hip) and the raster reader that never materialises the stitched payload (pcs_kernels_voxel.hip).
 // Device code; #included INSIDE each translation unit's anonymous namespace.
 
 // What one workgroup of the pre-aggregation kernel knows about one voxel: the sums over its (<= 8192) points

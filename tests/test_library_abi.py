@@ -59,6 +59,27 @@ def test_product_does_not_use_the_oracle():
     assert "oracle" not in nm
 
 
+def test_integration_md_lists_exactly_the_environment_variables_the_sources_read():
+    """INTEGRATION.md section 7's table and the getenv("PCS_...") calls of the libraries and the CLIs name the same variables
+    (PCS_LIB_PATH is read by lib.py, not by them)."""
+    pkg = os.path.dirname(os.path.dirname(L.LIB_PATH))
+    read = set()
+    for sub in ("csrc", "cli"):
+        for root, _, files in os.walk(os.path.join(pkg, sub)):
+            for f in files:
+                if f.endswith((".cpp", ".hip", ".h", ".c", ".py")):
+                    read |= set(re.findall(r'getenv\("(PCS_[A-Z0-9_]+)"', open(os.path.join(root, f), errors="ignore").read()))
+    assert len(read) >= 10, sorted(read)
+    doc = open(os.path.join(os.path.dirname(pkg), "INTEGRATION.md")).read()
+    section = doc[doc.index("## 7. Environment variables"):]
+    rows = [l for l in section.splitlines() if l.startswith("| `PCS_")]
+    listed = set()
+    for row in rows:
+        first = re.split(r"(?<!\\)\|", row)[1]
+        listed |= set(re.findall(r"PCS_[A-Z0-9_]+", first))
+    assert listed - {"PCS_LIB_PATH"} == read, (sorted(read - listed), sorted(listed - read - {"PCS_LIB_PATH"}))
+
+
 def test_strerror_and_create_without_gpu(gpu_present):
     lib = L.load()
     assert lib.pcs_strerror(0) == b"ok"

@@ -102,5 +102,5 @@ def test_every_square_is_visited_exactly_once(tmp_path):
 
 
 def test_the_kernel_and_the_launcher_use_this_header():
-    src = open(os.path.join(os.path.dirname(HEADER), "pcs_kernels.hip")).read()
+    src = open(os.path.join(os.path.dirname(HEADER), "pcs_kernels_voxel.hip")).read()
     assert '#include "pcs_vox_tiling.h"' in src and "PCS_VOX_TILING_DECODE(tl, lin, gridDim.y" in src and "vox_tiling_make(max_w, max_h, kVoxRows" in src and "vox_patch_shape(vs.leaf" in src

@@ -7,8 +7,8 @@
 // divisor; fuzzed shared-denominator quotients).
 //
 // build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-//        tools/kernel_lab.hip -o tools/kernel_lab
-#include "../pointcloud_stitching_amd/csrc/pcs_kernels.hip"
+//        tools/lab/kernel_lab.hip -o tools/lab/kernel_lab
+#include "../../pointcloud_stitching_amd/csrc/pcs_kernels.hip"
 
 #include <chrono>
 #include <cmath>
@@ -51,7 +51,7 @@ void lab_fused_dense(const StreamParams* __restrict__ params, FramePtrs fp, uint
     const uint32_t tile0 = blockIdx.x * kTilePoints;
     if (tile0 >= n) return;
     DepthSource<false, false, Mth> src{fp.depth[s]};
-    dense_tile(P, src, fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage, nullptr);
+    dense_tile(P, src, fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage);
 }
 
 // PERSISTENT form of the product kernel: a workgroup walks tiles g, g + G, g + 2G ... (flat tile index over all
@@ -132,7 +132,7 @@ void lab_fused_dense_stagger(const StreamParams* __restrict__ params, FramePtrs 
     if ((blockIdx.x & mask) && blockIdx.y * gridDim.x + blockIdx.x < 1792u)      // first resident generation only
         for (int k = 0; k < units; k++) __builtin_amdgcn_s_sleep(127);
     DepthSource<false, false, Mth> src{fp.depth[s]};
-    dense_tile(P, src, fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage, nullptr);
+    dense_tile(P, src, fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage);
 }
 
 template <class Mth, int WAVES>
@@ -146,7 +146,7 @@ void lab_fused_dense_lb(const StreamParams* __restrict__ params, FramePtrs fp, u
     const uint32_t tile0 = blockIdx.x * kTilePoints;
     if (tile0 >= n) return;
     DepthSource<false, false, Mth> src{fp.depth[s]};
-    dense_tile(P, src, fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage, nullptr);
+    dense_tile(P, src, fp.color[s], tile0, n, payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage);
 }
 
 // Memory skeleton: the same loads (uint4 depth, 8 colour dwords at the identity mapping) and the same
@@ -297,9 +297,9 @@ void lab_fused_dense_2tiles(const StreamParams* __restrict__ params, FramePtrs f
     PointIn pa[8], pb[8];
     const uint32_t tA = (blockIdx.x * 2u) * kTilePoints, tB = tA + kTilePoints;
     if (tA >= n) return;
-    src.load8(P, tA + threadIdx.x * 8, n, pa, nullptr);
+    src.load8(P, tA + threadIdx.x * 8, n, pa);
     const bool hasB = tB < n;
-    if (hasB) src.load8(P, tB + threadIdx.x * 8, n, pb, nullptr);
+    if (hasB) src.load8(P, tB + threadIdx.x * 8, n, pb);
     auto emit = [&](PointIn (&p)[8], uint4* st) {
         uint32_t w[20];
         LazyCvt lazy;
