@@ -1157,15 +1157,18 @@ try {
         return fail(c, PCS_ERR_CAPACITY, "payload buffers hold %zu shorts, %zu needed", payload_shorts,
                     c->max_payload_points * PCS_POINT_SHORTS);
     bool fast = true, ident = true, noovf = true, dd = false, cd = false;
+    bool rowc = true;                                    // every stream row-constant, as in run_fused_device
     for (int s = 0; s < S; s++) {
         const StreamParams& q = c->h_params[s];
         fast &= q.cert_fast != 0; ident &= q.ident_r != 0; noovf &= q.no_overflow != 0;
+        rowc &= q.ident_r == 2 && (q.W & 7) == 0 && q.color_bytes >= 16;
         dd |= q.ddist != 0;
         cd |= q.cdist != 0 || q.tex_half != 0;
     }
-    const MathSel sel = !fast ? MathSel::Ieee
-                      : noovf ? (ident ? MathSel::CertIdentRNoOvf : MathSel::CertNoOvf)
-                              : (ident ? MathSel::CertIdentR : MathSel::Cert);
+    MathSel sel = !fast ? MathSel::Ieee
+                : noovf ? (ident ? MathSel::CertIdentRNoOvf : MathSel::CertNoOvf)
+                        : (ident ? MathSel::CertIdentR : MathSel::Cert);
+    if (sel == MathSel::CertIdentRNoOvf && rowc) sel = MathSel::CertRowConstNoOvf;      // (the row-constant tile: pcs_kernels.hip)
     std::pair<hipEvent_t, hipEvent_t> ev{};
     if (c->kernel_timing) {
         int rc = acquire_event_pair(c, ev);

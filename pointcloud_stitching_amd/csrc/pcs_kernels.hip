@@ -254,6 +254,29 @@ __device__ __forceinline__ void window_piece(const uint8_t* color, uint32_t off,
                  : "=&s"(keep) : "v"(off), "s"(color), "s"(lds) : "memory");
 }
 
+// deproject_pixel_rowc (pcs_kernels_common.h; the other kernels keep it) in this tile's own form: X, Y, Z and the texture column u of
+// EVERY pixel, a hole's included, and no row. The tile reads u for the colour column alone and selects a hole's byte index to 0
+// afterwards: one select per pixel instead of one on u and one on the row. A hole's u is whatever 0 / 0 gives (NaN); FastCvt<false>
+// clamps and converts it (v_med3_f32, v_cvt_i32_f32: no trap, no flag read anywhere) and keeps no state — it has no redo() in this
+// tile — so nothing but the discarded index depends on it.
+template <class Mth>
+__device__ __forceinline__ PointIn deproject_pixel_win(const StreamParams& P, uint32_t d, float mx, float my)
+{
+    const float z = __fmul_rn(P.depth_scale, (float)d);
+    PointIn p;
+    p.X = __fmul_rn(z, mx);
+    p.Y = __fmul_rn(z, my);
+    p.Z = z;
+    const float P0 = __fadd_rn(p.X, P.t[0]);
+    const float P2 = p.Z;                                // z + t_z: a row-constant stream has t_z = +-0 (pcs_capi.cpp), so this is z for every z != 0
+    float x, y_unused;
+    Mth::div2(P0, P0, P2, x, y_unused);                  // (the second quotient is dead code)
+    const float px = __fadd_rn(__fmul_rn(x, P.c_fx), P.c_ppx);
+    p.u = Mth::div_const(px, P.c_w_f, P.c_rw);
+    p.v = 0.0f;
+    return p;
+}
+
 template <class Mth, uint32_t THREADS = kBlockThreads>
 __device__ __forceinline__ void dense_tile_rowc(const StreamParams& P, const uint16_t* __restrict__ depth,
                                                 const uint8_t* __restrict__ color, uint32_t tile0, uint32_t n,
@@ -296,7 +319,16 @@ __device__ __forceinline__ void dense_tile_rowc(const StreamParams& P, const uin
         window_piece(color, j < pa ? wsa + 16u * j : wsb + 16u * (j - pa), lds0 + k * 1024u);
     }
     if (lane == 0) *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(stage) + lrel + kWinZeroWord) = *(cptr<uint32_t>)(uintptr_t)color;
-
+    // The constants read after the depth has arrived, asked for HERE and held in SGPRs across the wait: the wait is an asm statement,
+    // which kept hipcc from issuing their scalar loads before it — every wave paid that round trip between its depth and its first
+    // arithmetic. Now it runs beside the Z16 one.
+    float M[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) M[k] = P.M[k];
+    float c_wm1_f = P.c_wm1_f;
+    uint32_t bpp = (uint32_t)P.bpp, stride = (uint32_t)P.stride;
+    asm volatile("" : "+s"(M[0]), "+s"(M[1]), "+s"(M[2]), "+s"(M[3]), "+s"(M[4]), "+s"(M[5]), "+s"(M[6]), "+s"(M[7]), "+s"(M[8]),
+                      "+s"(M[9]), "+s"(M[10]), "+s"(M[11]), "+s"(c_wm1_f), "+s"(bpp), "+s"(stride));
     static_assert(kWinPieces == 3, "the wait below leaves the window's requests in flight");
     asm volatile("s_waitcnt vmcnt(3)" : "+v"(dv), "+v"(ma), "+v"(mb), "+v"(myb), "+v"(crow));
     PointIn p[8];
@@ -306,21 +338,22 @@ __device__ __forceinline__ void dense_tile_rowc(const StreamParams& P, const uin
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const uint32_t d = (k & 1) ? (dw[k >> 1] >> 16) : (dw[k >> 1] & 0xFFFFu);
-            p[k] = deproject_pixel_rowc<Mth>(P, d, __uint_as_float(mxs[k]), __uint_as_float(myb), (int)crow);
+            p[k] = deproject_pixel_win<Mth>(P, d, __uint_as_float(mxs[k]), __uint_as_float(myb));
         }
     }
-    // The record fields of make_record, and each pixel's colour byte index (the row is p.v itself: deproject_pixel_rowc).
+    // The record fields of make_record, and each pixel's colour byte index: 0 for a hole (what u = v = 0 gives in make_record).
     FastCvt<false> cv;
     uint32_t xy[8], zz[8], ci[8];
+    const uint32_t row_off = __umul24(crow, stride);     // the lane's colour row, in bytes: one product for its 8 pixels
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const float ax = world_mm(P.M + 0, p[k].X, p[k].Y, p[k].Z);
-        const float ay = world_mm(P.M + 4, p[k].X, p[k].Y, p[k].Z);
-        const float az = world_mm(P.M + 8, p[k].X, p[k].Y, p[k].Z);
+        const float ax = world_mm(M + 0, p[k].X, p[k].Y, p[k].Z);
+        const float ay = world_mm(M + 4, p[k].X, p[k].Y, p[k].Z);
+        const float az = world_mm(M + 8, p[k].X, p[k].Y, p[k].Z);
         xy[k] = perm((uint32_t)cv.cvt(ay), (uint32_t)cv.cvt(ax), kLoLo);
         zz[k] = (uint32_t)cv.cvt(az);
-        const int32_t xi = cv.pixel(__fmaf_rn(p[k].u, P.c_w_f, 0.5f), P.cW - 1, P.c_wm1_f);
-        ci[k] = __umul24((uint32_t)xi, (uint32_t)P.bpp) + __umul24((uint32_t)__float_as_int(p[k].v), (uint32_t)P.stride);
+        const int32_t xi = cv.pixel(__fmaf_rn(p[k].u, P.c_w_f, 0.5f), P.cW - 1, c_wm1_f);
+        ci[k] = p[k].Z != 0.0f ? __umul24((uint32_t)xi, bpp) + row_off : 0u;
     }
     // The colour dwords: from the lane's window (the wave's first row's or its last row's), pixel (0, 0)'s word for byte 0; a
     // lane with any other pixel gathers those from the raster as make_record does, with the exact slide-back at its end.
@@ -674,8 +707,12 @@ void pcs_fused_dense_batch_kernel(const StreamParams* __restrict__ params, Batch
     const uint32_t n = P.n_points;
     const uint32_t tile0 = blockIdx.x * kTilePoints;
     if (tile0 >= n) return;
-    DepthSource<DDIST, CDIST, Mth> src{bp.depth[e]};
-    dense_tile(P, src, bp.color[e], tile0, n, bp.payload[blockIdx.z] + (size_t)P.out_base * PCS_POINT_BYTES, stage);
+    if constexpr (Mth::kRowConst) {
+        dense_tile_rowc<Mth>(P, bp.depth[e], bp.color[e], tile0, n, bp.payload[blockIdx.z] + (size_t)P.out_base * PCS_POINT_BYTES, stage);
+    } else {
+        DepthSource<DDIST, CDIST, Mth> src{bp.depth[e]};
+        dense_tile(P, src, bp.color[e], tile0, n, bp.payload[blockIdx.z] + (size_t)P.out_base * PCS_POINT_BYTES, stage);
+    }
 }
 
 // Count pass: kept points per tile. (Folding the per-stream scan into this launch through a last-arriver
@@ -1371,6 +1408,13 @@ hipError_t launch_fused_dense_batch(const StreamParams* d_params, int n_streams,
     if (n_streams * n_sets > kBatchEntries || n_sets > kBatchSets) return hipErrorInvalidValue;
     const dim3 grid((max_points + kTilePoints - 1) / kTilePoints, (unsigned)n_streams, (unsigned)n_sets);
 #define L(DD, CD, M) hipLaunchKernelGGL((pcs_fused_dense_batch_kernel<DD, CD, M>), grid, dim3(kBlockThreads), 0, st, d_params, bp)
+    if (math == MathSel::CertRowConstNoOvf) {
+        // as in launch_fused_dense: 16-aligned rasters only, every set's; otherwise CertIdentNoOvf's kernel
+        bool aligned = !any_ddist && !any_cdist;
+        for (int k = 0; k < n_streams * n_sets; k++) aligned &= ((((uintptr_t)bp.color[k]) | ((uintptr_t)bp.depth[k])) & 15u) == 0;
+        if (aligned) { L(false, false, CertRowConstNoOvf); return hipGetLastError(); }
+        math = MathSel::CertIdentRNoOvf;
+    }
     if (math != MathSel::Ieee && !any_ddist) {
         const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
         const bool noovf = (math == MathSel::CertNoOvf || math == MathSel::CertIdentRNoOvf) && !any_cdist;
