@@ -110,6 +110,13 @@ typedef struct pcs_stream_config {
 #define PCS_FLAG_TEXCOORD_HALF_PIXEL 0x10u /* deprojection: u = (px + 0.5)/W, v = (py + 0.5)/H as older librealsense
                                          releases computed texture coordinates; default is
                                          u = px/W, v = py/H. The reference's +0.5 and clamp (:434-444) follow either way */
+#define PCS_FLAG_SCALAR_ARITH   0x20u /* the reference's DEFAULT (no -m) arithmetic, copyPointCloudXYZRGBToBuffer :620-667, bit for
+                                         bit as its build compiles it: m1*y rounded, m0*x and m2*z fused, + t rounded, * 1000.0 in
+                                         double, cvttsd2si. With CUTOFF its loop (:640-646): record i stays in slot i, a skipped
+                                         slot is not written (a1 / a2 twins) or reads as ten zero bytes (fused calls), the count
+                                         is n_points; CUTOFF_COMPAT changes nothing. Fixed for the life of the context. Not with
+                                         DROP_INVALID; the _batch, _counted, voxel, partials, sink and payload re-transform calls
+                                         return PCS_ERR_UNSUPPORTED on such a context (it returns these bytes or fails) */
 
 typedef struct pcs_config {
     int32_t                  device;      /* HIP device ordinal */

@@ -46,10 +46,11 @@ static void print_usage()
     printf("\nUsage: pcs-camera-optimized -f <synth:WxH | frames.pcsraw | recording.bag> [-m] [-t n] [-c] [-s] [-n streams] [-g gpu]\n"
            "  -f <src>  frame source (synthetic generator or raw dump)\n"
            "  -s        send data to central camera server if available (TCP push on port 8000)\n"
-           "  -m        use the MI355X HIP path (the reference's SIMD switch)\n"
+           "  -m        the reference's SIMD arithmetic; without it, its default scalar arithmetic - both on the GPU\n"
            "  -t <n>    OpenMP threads of the reference path; accepted, inert on the HIP path\n"
            "  -c        cutoff 0<z<=1.5, -2<x<=2 with compaction, exactly as the reference's -c -m computes it (point k of an\n"
            "            aligned group of four is gated by point 3-k's test)   -C  every point by its own test\n"
+           "            without -m, the default loop's -c: z != 0, x != 0, z <= 1.5, nothing compacted (a skipped point is a zero record)\n"
            "  -i        drop invalid-depth pixels   -d <n> keep every n-th point   -n <N> camera streams\n"
            "  -g <dev>  GPU ordinal   -r <frames>   -o <file> dump last stitched buffer   -p <port>\n"
            "  -P        serve frames on 'Z' pull requests (the live server's protocol) instead of pushing them\n"
@@ -179,9 +180,6 @@ int main(int argc, char** argv)
     if (!src.open(filename)) { std::cerr << "cannot open frame source " << filename << std::endl; return 2; }
     std::cout << "Camera Info: synthetic D400-like stream x" << n_streams << " FW ver:n/a" << std::endl;
     if (num_of_threads) std::cout << "OpenMP Threads: " << num_of_threads << std::endl;
-    if (!use_hip)
-        std::cout << "note: without -m the reference runs its scalar loop; this build has no CPU path and uses the HIP path "
-                     "(the scalar variant differs from -m by +-1 LSB and is not reproduced)" << std::endl;
 
     if (extrinsics_path) {      // replaces editing tf_mat / transform[i] in source (:64-67)
         FILE* f = fopen(extrinsics_path, "r");
@@ -206,7 +204,8 @@ int main(int argc, char** argv)
     memset(&cfg, 0, sizeof cfg);
     cfg.device = device; cfg.n_streams = n_streams; cfg.streams = src.cfg.data(); cfg.downsample = downsample;
     cfg.flags = (cutoff ? PCS_FLAG_CUTOFF : 0u) | (cutoff_compat ? PCS_FLAG_CUTOFF_COMPAT : 0u) | (drop_invalid ? PCS_FLAG_DROP_INVALID : 0u) |
-                (half_pixel ? PCS_FLAG_TEXCOORD_HALF_PIXEL : 0u);
+                (half_pixel ? PCS_FLAG_TEXCOORD_HALF_PIXEL : 0u) |
+                (use_hip ? 0u : PCS_FLAG_SCALAR_ARITH);      // no -m: copyPointCloudXYZRGBToBuffer's arithmetic (:620-667, 688-694)
     pcs_ctx* ctx = nullptr;
     int rc = pcs_create(&ctx, &cfg);
     if (rc != PCS_OK) { std::cerr << "pcs_create: " << pcs_strerror(rc) << ": " << pcs_last_error(nullptr) << std::endl; return 1; }

@@ -429,7 +429,10 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
         const MathSel sel = !fast ? MathSel::Ieee
                           : noovf ? (ident ? MathSel::CertIdentRNoOvf : MathSel::CertNoOvf)
                                   : (ident ? MathSel::CertIdentR : MathSel::Cert);
-        if (dense)      // (the dense kernel's row-constant form: its colour window is requested beside the depth, pcs_kernels.hip)
+        if (scalar_arith(c))   // a3: the dense / general launch over ScalarArith, -c a per-point select in it (no count, no scan)
+            HIPCHK(c, launch_fused_scalar(c->d_params, s0, nl, mp, dense, scalar_cut(c), c->downsample, fast ? MathSel::Cert : MathSel::Ieee,
+                                          fp, d_payload, c->stream));
+        else if (dense) // (the dense kernel's row-constant form: its colour window is requested beside the depth, pcs_kernels.hip)
             HIPCHK(c, launch_fused_dense(c->d_params, s0, nl, mp, dd, cd, sel == MathSel::CertIdentRNoOvf && rowc ? MathSel::CertRowConstNoOvf : sel,
                                          fp, d_payload, c->stream));
         else
@@ -516,8 +519,11 @@ int pcs_create(pcs_ctx** out, const pcs_config* cfg)
         return fail(nullptr, PCS_ERR_INVALID_ARG, "n_streams %d outside 1..%d", cfg->n_streams, PCS_MAX_STREAMS);
     if (cfg->downsample < 1) return fail(nullptr, PCS_ERR_INVALID_ARG, "downsample %d < 1", cfg->downsample);
     if (cfg->flags & ~(PCS_FLAG_CUTOFF | PCS_FLAG_CUTOFF_COMPAT | PCS_FLAG_DROP_INVALID | PCS_FLAG_FORCE_IEEE |
-                       PCS_FLAG_TEXCOORD_HALF_PIXEL))
+                       PCS_FLAG_TEXCOORD_HALF_PIXEL | PCS_FLAG_SCALAR_ARITH))
         return fail(nullptr, PCS_ERR_INVALID_ARG, "unknown flag bits 0x%x", cfg->flags);
+    if ((cfg->flags & PCS_FLAG_SCALAR_ARITH) && (cfg->flags & PCS_FLAG_DROP_INVALID))
+        return fail(nullptr, PCS_ERR_UNSUPPORTED, "PCS_FLAG_SCALAR_ARITH with PCS_FLAG_DROP_INVALID: dropping invalid pixels is this "
+                    "library's extension and the reference's default loop has no bytes for it");
     if ((cfg->flags & PCS_FLAG_CUTOFF_COMPAT) && !(cfg->flags & PCS_FLAG_CUTOFF))
         return fail(nullptr, PCS_ERR_INVALID_ARG, "PCS_FLAG_CUTOFF_COMPAT needs PCS_FLAG_CUTOFF");
     for (int s = 0; s < cfg->n_streams; s++) {
@@ -807,6 +813,17 @@ int pcs_copy_pointcloud_xyzrgb_to_buffer_device(pcs_ctx* c, int stream, const fl
     }
     const bool pred = has_pred(c->flags);
     VertexPtrs vp{d_vertices, d_texcoords, d_color, (uint32_t)n_points};
+    if (scalar_arith(c)) {     // a3: every record in its own slot; under -c a skipped slot keeps the buffer's bytes, the count is n_points
+        if (scalar_cut(c)) {
+            HIPCHK(c, launch_pack_scalar_cut(c->d_params, stream, vp, d_pc_buffer, c->stream));
+        } else {
+            PackBatch pb{};
+            pb.v[0] = vp; pb.out[0] = reinterpret_cast<uint8_t*>(d_pc_buffer); pb.stream[0] = stream;
+            HIPCHK(c, launch_pack_scalar(c->d_params, pb, 1, (uint32_t)n_points, ((uintptr_t)d_pc_buffer & 15u) == 0, c->stream));
+        }
+        if (d_out_points) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)d_out_points, n_points, 1, c->stream));
+        return PCS_OK;
+    }
     if (!pred) {
         if (((uintptr_t)d_pc_buffer & 15u) == 0)
             HIPCHK(c, launch_pack_dense(c->d_params, stream, vp, d_pc_buffer, c->stream));
@@ -848,7 +865,7 @@ int pcs_copy_pointclouds_xyzrgb_to_buffer_device(pcs_ctx* c, int n_clouds, const
             return fail(c, PCS_ERR_INVALID_ARG, "cloud %d: misaligned device pointer", i);
     }
     DeviceGuard guard(c->device);
-    if (has_pred(c->flags)) {
+    if (has_pred(c->flags) || scalar_cut(c)) {     // (a3's -c: one cloud per launch, its skipped slots kept)
         for (int i = 0; i < n_clouds; i++) {
             const pcs_cloud_desc& q = clouds[i];
             int rc = pcs_copy_pointcloud_xyzrgb_to_buffer_device(c, q.stream, q.vertices, q.texcoords, q.n_points, q.color,
@@ -876,7 +893,8 @@ int pcs_copy_pointclouds_xyzrgb_to_buffer_device(pcs_ctx* c, int n_clouds, const
             mp = std::max(mp, (uint32_t)q.n_points);
             aligned &= ((uintptr_t)q.pc_buffer & 15u) == 0;
         }
-        HIPCHK(c, launch_pack_batch(c->d_params, pb, nb, mp, aligned, c->stream));
+        if (scalar_arith(c)) HIPCHK(c, launch_pack_scalar(c->d_params, pb, nb, mp, aligned, c->stream));
+        else                 HIPCHK(c, launch_pack_batch(c->d_params, pb, nb, mp, aligned, c->stream));
     }
     if (d_out_points)
         for (int i = 0; i < n_clouds; i++)
@@ -988,6 +1006,8 @@ int pcs_copy_pointcloud_xyzrgb_to_buffer(pcs_ctx* c, int stream, const float* ve
     HIPCHK(c, hipMemcpyAsync(c->s_vertices, vertices, vb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->s_texcoords, texcoords, tb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->s_color[stream], color, P.color_bytes, hipMemcpyHostToDevice, c->stream));
+    if (scalar_cut(c))      // a3's -c does not write the slots it skips: they keep the caller's bytes, which go up first
+        HIPCHK(c, hipMemcpyAsync(c->s_payload, pc_buffer, ob, hipMemcpyHostToDevice, c->stream));
     rc = pcs_copy_pointcloud_xyzrgb_to_buffer_device(c, stream, c->s_vertices, c->s_texcoords, n_points,
                                                      c->s_color[stream], c->s_payload, nullptr);
     if (rc) return rc;
@@ -1015,17 +1035,23 @@ int pcs_send_xyzrgb_pointcloud(pcs_ctx* c, int stream, const float* vertices, co
     if (buffer_shorts < need)
         return fail(c, PCS_ERR_CAPACITY, "buffer holds %zu shorts, %zu needed (the reference's BUF_SIZE of %d shorts "
                     "overflows beyond 999 999 points)", buffer_shorts, need, PCS_REF_BUF_SIZE);
+    const size_t clear_end = std::min<size_t>(PCS_REF_BUF_SIZE, buffer_shorts * sizeof(int16_t));
+    uint8_t* b = reinterpret_cast<uint8_t*>(buffer);
+    // a3's -c (:640-646) skips slots inside the payload: the memset of :673 comes first, as in the reference, so that a skipped slot
+    // reads 0 below BUF_SIZE and keeps the caller's bytes beyond it
+    const bool a3_cut = scalar_cut(c);
+    if (a3_cut) std::memset(b, 0, clear_end);
     int count = 0;
     int rc = pcs_copy_pointcloud_xyzrgb_to_buffer(c, stream, vertices, texcoords, n_points, color,
                                                   buffer + PCS_HEADER_SHORTS, &count);
     if (rc) return rc;
     const int32_t size = (int32_t)((size_t)count * PCS_POINT_BYTES);                     // :697
     // :673 — everything below BUF_SIZE bytes that the payload does not cover reads as zero
-    const size_t clear_end = std::min<size_t>(PCS_REF_BUF_SIZE, buffer_shorts * sizeof(int16_t));
-    uint8_t* b = reinterpret_cast<uint8_t*>(buffer);
-    std::memset(b, 0, std::min<size_t>(4, clear_end));
     const size_t pay_end = 4 + (size_t)size;
-    if (pay_end < clear_end) std::memset(b + pay_end, 0, clear_end - pay_end);
+    if (!a3_cut) {
+        std::memset(b, 0, std::min<size_t>(4, clear_end));
+        if (pay_end < clear_end) std::memset(b + pay_end, 0, clear_end - pay_end);
+    }
     if (write_header) std::memcpy(b, &size, sizeof size);                                 // :718
     if (out_size_bytes) *out_size_bytes = size;
     return PCS_OK;
@@ -1051,6 +1077,7 @@ int pcs_process_frames_device_counted(pcs_ctx* c, const uint16_t* const* d_depth
                                       const uint32_t* d_tile_kept, int16_t* d_payload, size_t payload_shorts, int32_t* d_counts)
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_process_frames_device_counted");
     if (!d_depth || !d_color || !d_payload || !d_tile_kept) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     if ((uintptr_t)d_tile_kept & 3u) return fail(c, PCS_ERR_INVALID_ARG, "d_tile_kept must be 4-byte aligned");
     for (int s = 0; s < c->n_streams; s++) {
@@ -1077,6 +1104,7 @@ int pcs_process_frames_device_batch(pcs_ctx* c, int n_sets, const uint16_t* cons
                                     int16_t* const* d_payload, size_t payload_shorts, int32_t* const* d_counts)
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_process_frames_device_batch");
     if (n_sets < 0) return fail(c, PCS_ERR_INVALID_ARG, "n_sets %d < 0", n_sets);
     if (n_sets == 0) return PCS_OK;
     if (!d_depth || !d_color || !d_payload) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
@@ -1446,6 +1474,7 @@ int pcs_transform_payloads_device(pcs_ctx* c, int n_cams, const pcs_payload_desc
                                   int16_t* d_stitched_payload, size_t stitched_shorts, int* points_per_cam, int* total_points)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_transform_payloads_device");
     if (n_cams < 0 || (n_cams > 0 && (!cams || !d_stitched_payload))) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     if (downsample < 1) return fail(c, PCS_ERR_INVALID_ARG, "downsample %d < 1", downsample);
     size_t need = 0;

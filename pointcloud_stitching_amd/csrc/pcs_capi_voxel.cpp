@@ -21,6 +21,7 @@ static int voxel_grid_device_impl(pcs_ctx* c, const int16_t* d_payload, int n_po
                                   int16_t* d_out, size_t out_shorts, int32_t* d_out_points)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_voxel_grid_device");
     if (n_points < 0) return fail(c, PCS_ERR_INVALID_ARG, "n_points %d < 0", n_points);
     if (leaf_mm < 1 || leaf_mm > 32767) return fail(c, PCS_ERR_INVALID_ARG, "leaf_mm %d outside 1..32767", leaf_mm);
     if (n_points > 0 && (!d_payload || !d_out)) return fail(c, PCS_ERR_INVALID_ARG, "NULL device pointer");
@@ -116,6 +117,7 @@ int pcs_process_frames_voxel_device(pcs_ctx* c, const uint16_t* const* d_depth, 
                                     int16_t* d_out, size_t out_shorts, int32_t* d_out_points)
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_process_frames_voxel_device");
     if (!d_depth || !d_color || !d_out) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     if (leaf_mm < 1 || leaf_mm > 32767) return fail(c, PCS_ERR_INVALID_ARG, "leaf_mm %d outside 1..32767", leaf_mm);
     const int S = c->n_streams;
@@ -184,6 +186,7 @@ int pcs_process_frames_voxel_partials_device(pcs_ctx* c, const uint16_t* const* 
                                              int32_t* d_n_partials)
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_process_frames_voxel_partials_device");
     if (!d_depth || !d_color || !d_keys || !d_partials || !d_n_partials) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     if (leaf_mm < 1 || leaf_mm > 32767) return fail(c, PCS_ERR_INVALID_ARG, "leaf_mm %d outside 1..32767", leaf_mm);
     if (((uintptr_t)d_keys & 7u) || ((uintptr_t)d_partials & 31u))
@@ -215,6 +218,7 @@ int pcs_voxel_grid_from_partials_device(pcs_ctx* c, const uint64_t* d_keys, cons
                                         int32_t* d_out_points)
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_voxel_grid_from_partials_device");
     if (n_partials < 0) return fail(c, PCS_ERR_INVALID_ARG, "n_partials %d < 0", n_partials);
     if (((uintptr_t)d_n_partials & 3u) || ((uintptr_t)d_out_points & 3u))
         return fail(c, PCS_ERR_INVALID_ARG, "d_n_partials / d_out_points must be 4-byte aligned");
@@ -255,6 +259,7 @@ constexpr uint32_t kSinkMagic = 0x50435356u;      // "PCSV"
 int pcs_voxel_sink_begin(pcs_ctx* c, size_t capacity_points, int leaf_mm, pcs_voxel_sink* sink)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_voxel_sink_begin");
     if (!sink) return fail(c, PCS_ERR_INVALID_ARG, "sink is NULL");
     if (leaf_mm < 1 || leaf_mm > 32767) return fail(c, PCS_ERR_INVALID_ARG, "leaf_mm %d outside 1..32767", leaf_mm);
     if (capacity_points < 1 || capacity_points > 0xFFFFFFF0ull)
@@ -283,6 +288,7 @@ int pcs_process_frames_voxel_into_sink_device(pcs_ctx* c, const uint16_t* const*
                                               const pcs_voxel_sink* sink)
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_process_frames_voxel_into_sink_device");
     if (!d_depth || !d_color || !sink) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     SinkBlob b;
     std::memcpy(&b, sink->opaque, sizeof b);
@@ -306,6 +312,7 @@ try {
 int pcs_voxel_sink_finish(pcs_ctx* c, const pcs_voxel_sink* sink, int16_t* d_out, size_t out_shorts, int32_t* d_out_points)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_voxel_sink_finish");
     if (!sink || !d_out) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     if ((uintptr_t)d_out_points & 3u) return fail(c, PCS_ERR_INVALID_ARG, "d_out_points must be 4-byte aligned");
     SinkBlob b;
@@ -325,6 +332,7 @@ int pcs_voxel_grid(pcs_ctx* c, const int16_t* payload, int n_points, int leaf_mm
                    int* out_points)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_voxel_grid");
     if (n_points < 0) return fail(c, PCS_ERR_INVALID_ARG, "n_points %d < 0", n_points);
     if (n_points == 0) { if (out_points) *out_points = 0; return PCS_OK; }
     if (!payload || !out) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");

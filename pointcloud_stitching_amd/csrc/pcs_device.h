@@ -164,6 +164,16 @@ hipError_t launch_pack_emit(const StreamParams* d_params, int stream, const Vert
 hipError_t launch_pack_batch(const StreamParams* d_params, const PackBatch& pb, int n, uint32_t max_points, bool aligned,
                              hipStream_t st);
 
+// a3, PCS_FLAG_SCALAR_ARITH (the reference's default arithmetic). The fused launch: `dense` as for launch_fused_dense (stride 1,
+// 16-byte aligned payload, every stream a multiple of 8 points), otherwise the general form; `cut`: a point a3's -c loop skips gives
+// the zero record. Counts are the configuration's (nothing is compacted). The a2 twin: n clouds in one launch without -c; with it,
+// one cloud whose skipped slots keep the bytes of d_out.
+hipError_t launch_fused_scalar(const StreamParams* d_params, int stream0, int n_launch, uint32_t max_points, bool dense, bool cut,
+                               int downsample, MathSel math, const FramePtrs& fp, int16_t* d_payload, hipStream_t st);
+hipError_t launch_pack_scalar(const StreamParams* d_params, const PackBatch& pb, int n, uint32_t max_points, bool aligned,
+                              hipStream_t st);
+hipError_t launch_pack_scalar_cut(const StreamParams* d_params, int stream, const VertexPtrs& vp, int16_t* d_out, hipStream_t st);
+
 // a5 alone.
 hipError_t launch_deproject(const StreamParams* d_params, int stream, uint32_t n_points, const uint16_t* d_depth,
                             float* d_vertices, float* d_texcoords, hipStream_t st);

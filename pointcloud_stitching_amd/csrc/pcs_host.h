@@ -117,7 +117,24 @@ int fail(pcs_ctx* c, int status, const char* fmt, ...);
             return fail((c), PCS_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));   \
     } while (0)
 
-inline bool has_pred(uint32_t flags) { return (flags & (PCS_FLAG_CUTOFF | PCS_FLAG_DROP_INVALID)) != 0; }
+// A compacting predicate is active. Not under PCS_FLAG_SCALAR_ARITH: a3's -c loop leaves record i in slot i, so nothing is compacted,
+// the counts are the configuration's and the launches are the predicate-free ones with a per-point select.
+inline bool has_pred(uint32_t flags)
+{
+    return !(flags & PCS_FLAG_SCALAR_ARITH) && (flags & (PCS_FLAG_CUTOFF | PCS_FLAG_DROP_INVALID)) != 0;
+}
+inline bool scalar_arith(const pcs_ctx* c) { return (c->flags & PCS_FLAG_SCALAR_ARITH) != 0; }
+inline bool scalar_cut(const pcs_ctx* c) { return scalar_arith(c) && (c->flags & PCS_FLAG_CUTOFF) != 0; }
+
+// A context created with PCS_FLAG_SCALAR_ARITH returns a3's bytes or fails before anything is launched: no call may hand back -m bytes
+// from it. The entry points that have no a3 form refuse such a context first thing.
+#define PCS_NO_SCALAR_ARITH(c, name)                                                                                        \
+    do {                                                                                                                    \
+        if (pcs_host::scalar_arith(c))                                                                                      \
+            return pcs_host::fail((c), PCS_ERR_UNSUPPORTED, "%s is not available on a context created with "               \
+                                  "PCS_FLAG_SCALAR_ARITH: the reference's default arithmetic covers the a1 / a2 twins and " \
+                                  "pcs_process_frames, pcs_process_frames_device, pcs_submit_frames / pcs_collect_frames", name); \
+    } while (0)
 
 template <class T>
 int ensure(pcs_ctx* c, T*& p, size_t& cap, size_t bytes)

@@ -27,6 +27,16 @@
 #define EMIT_WAVES 6      // 7 fits 72 VGPRs only with scratch spills in some instantiations and measured no faster
 #endif
 
+#ifndef PCS_SCALAR_FP64
+#define PCS_SCALAR_FP64 0     // 1: a3's conversion in FP64 for every point (A/B at build time; DESIGN.md section 8 has the measurement)
+#endif
+#ifndef SCALAR_DENSE_WAVES
+#define SCALAR_DENSE_WAVES 7  // the residual form holds the dense kernel's 72 VGPRs without scratch; the FP64 form wants 95 (5)
+#endif
+#ifndef SCALAR_EMIT_CUT_WAVES
+#define SCALAR_EMIT_CUT_WAVES 5   // the general form with a3's -c select: 87-90 VGPRs; at EMIT_WAVES (80) it spills 28-32 bytes
+#endif
+
 namespace pcs {
 
 namespace {
@@ -56,22 +66,45 @@ __device__ __forceinline__ void stage_record(uint8_t* lds, uint32_t off, const R
 }
 
 // One point -> one record. short(float) (:581-583) keeps the low 16 bits of the converted value.
-template <class Cvt>
+// Arith: which of the reference's loops the world coordinates follow (pcs_kernels_common.h). Under ScalarArith the Cvt policy converts
+// the colour coordinates only; the world values take the FP32 residual form under a policy that keeps a running maximum (whose redo
+// is the exact policy) and the FP64 form under any other. With its CUT a point the loop skips gives the all-zero record.
+template <class Arith = SimdArith, class Cvt>
 __device__ __forceinline__ Record make_record(const StreamParams& P, const uint8_t* __restrict__ color,
                                               const PointIn& p, Cvt& cv)
 {
-    const float ax = world_mm(P.M + 0, p.X, p.Y, p.Z);
-    const float ay = world_mm(P.M + 4, p.X, p.Y, p.Z);
-    const float az = world_mm(P.M + 8, p.X, p.Y, p.Z);
     float xf, yf;
-    color_coords(P, p.u, p.v, xf, yf);
-    cv.note(ax, ay, az, xf, yf);
-    const uint32_t x = (uint32_t)cv.cvt(ax), y = (uint32_t)cv.cvt(ay), z = (uint32_t)cv.cvt(az);
+    uint32_t x, y, z;
+    if constexpr (Arith::kScalar) {
+        const float ax = world_scalar(P.M + 0, p.X, p.Y, p.Z);
+        const float ay = world_scalar(P.M + 4, p.X, p.Y, p.Z);
+        const float az = world_scalar(P.M + 8, p.X, p.Y, p.Z);
+        color_coords(P, p.u, p.v, xf, yf);
+        if constexpr (Cvt::kTracks && !PCS_SCALAR_FP64) {
+            constexpr float k = 131072.0f;       // 2^17: the policy's 2^31 is |a| = 2^14, the residual form's reach
+            cv.note(__fmul_rn(__builtin_fabsf(ax), k), __fmul_rn(__builtin_fabsf(ay), k), __fmul_rn(__builtin_fabsf(az), k), xf, yf);
+            x = mm_scalar_residual(ax); y = mm_scalar_residual(ay); z = mm_scalar_residual(az);
+        } else {
+            cv.note(0.0f, 0.0f, 0.0f, xf, yf);
+            x = mm_scalar_exact(ax); y = mm_scalar_exact(ay); z = mm_scalar_exact(az);
+        }
+    } else {
+        const float ax = world_mm(P.M + 0, p.X, p.Y, p.Z);
+        const float ay = world_mm(P.M + 4, p.X, p.Y, p.Z);
+        const float az = world_mm(P.M + 8, p.X, p.Y, p.Z);
+        color_coords(P, p.u, p.v, xf, yf);
+        cv.note(ax, ay, az, xf, yf);
+        x = (uint32_t)cv.cvt(ax); y = (uint32_t)cv.cvt(ay); z = (uint32_t)cv.cvt(az);
+    }
     const uint32_t w = color_fetch(P, color, cv.pixel(xf, P.cW - 1, P.c_wm1_f), cv.pixel(yf, P.cH - 1, P.c_hm1_f), cv);
     Record r;
     r.xy = perm(y, x, kLoLo);                    // short(x) | short(y) << 16  — the low 16 bits of each (:581-583)
     r.zc = perm(w, z, kLoLo);                    // short(z) | (R | G<<8) << 16
     r.b  = __builtin_amdgcn_ubfe(w, 16, 8);      // B, high byte 0 (:585)
+    if constexpr (Arith::kCut) {
+        const bool keep = scalar_cut_keeps(p.X, p.Z);
+        r.xy = keep ? r.xy : 0u; r.zc = keep ? r.zc : 0u; r.b = keep ? r.b : 0u;
+    }
     return r;
 }
 
@@ -147,7 +180,7 @@ __device__ __forceinline__ void store_staged(const uint8_t* lds, uint32_t head, 
 // ------------------------------------------------------------------------------------------------
 // THREADS: lanes per workgroup = 8-point runs per tile (kBlockThreads: 2048-point tiles; 64: one wavefront per 512-point tile, what
 // a launch that cannot fill the chip with 256-lane workgroups takes — launch_fused_dense).
-template <class Src, uint32_t THREADS = kBlockThreads>
+template <class Src, uint32_t THREADS = kBlockThreads, class Arith = SimdArith>
 __device__ __forceinline__ void dense_tile(const StreamParams& P, const Src& src, const uint8_t* __restrict__ color,
                                            uint32_t tile0, uint32_t n, uint8_t* __restrict__ out_bytes,
                                            uint4* stage)
@@ -160,8 +193,8 @@ __device__ __forceinline__ void dense_tile(const StreamParams& P, const Src& src
     auto fill = [&](auto& cv) {
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
-            const Record a = make_record(P, color, p[k], cv);
-            const Record b = make_record(P, color, p[k + 1], cv);
+            const Record a = make_record<Arith>(P, color, p[k], cv);
+            const Record b = make_record<Arith>(P, color, p[k + 1], cv);
             uint32_t* o = w + (k >> 1) * 5;
             o[0] = a.xy;
             o[1] = a.zc;
@@ -415,7 +448,7 @@ __device__ __forceinline__ void dense_tile_rowc(const StreamParams& P, const uin
 //   out_first output point index (within the whole payload) of kept-index 0 of this stream
 // A kept point with kept-index g is written iff g % ds == 0, to output point out_first + g / ds.
 // ------------------------------------------------------------------------------------------------
-template <class Src, bool PRED, bool DS1>
+template <class Src, bool PRED, bool DS1, class Arith = SimdArith>
 __device__ __forceinline__ void generic_tile(const StreamParams& P, const Src& src, const uint8_t* __restrict__ color,
                                              uint32_t tile0, uint32_t n, uint32_t flags, uint32_t ds,
                                              uint32_t g0, uint32_t out_first, uint8_t* __restrict__ payload_bytes,
@@ -444,7 +477,7 @@ __device__ __forceinline__ void generic_tile(const StreamParams& P, const Src& s
     Record rec[8];
     auto fill = [&](auto& cv) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) rec[k] = make_record(P, color, p[k], cv);
+        for (int k = 0; k < 8; k++) rec[k] = make_record<Arith>(P, color, p[k], cv);
     };
     if (Src::Math::kCvtMode == 2) {
         FastCvt<false> fast;
@@ -1231,6 +1264,106 @@ void pcs_stitch_kernel(const uint16_t* __restrict__ src, uint32_t out_points, ui
     store_staged(stage, head, pts * PCS_POINT_BYTES, gdst);
 }
 
+// ---- a3: PCS_FLAG_SCALAR_ARITH ------------------------------------------------------------------
+// The reference's default (no -m) arithmetic through the same tiles: ScalarArith in place of SimdArith (pcs_kernels_common.h). Kernels of
+// their own, so that every -m kernel keeps its name and its code. One deprojection policy per kernel — the policies give identical
+// bits: the certified general one (CertMath<false>) where every stream of the launch certifies, the IEEE one otherwise — over the
+// DepthSource<true, true> that decides about distortion once per lane. The row-constant tile carries its own copy of the transform
+// and is not selected. Under -c nothing is compacted (a3's loop, :640-646, leaves record i in slot i): the fused launches are the
+// dense / emit launch with a per-point select to the zero record, no count, no scan.
+template <class Mth, bool CUT>
+__global__ __launch_bounds__(kBlockThreads, SCALAR_DENSE_WAVES)
+void pcs_fused_dense_scalar_kernel(const StreamParams* __restrict__ params, int stream0, FramePtrs fp,
+                                   uint8_t* __restrict__ payload_bytes)
+{
+    __shared__ uint4 stage[kDenseStageBytes / 16];
+    const int s = blockIdx.y;
+    const StreamParams& P = params[stream0 + s];
+    request_constants(P, fp.depth[s], fp.color[s], payload_bytes);
+    const uint32_t n = P.n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    DepthSource<true, true, Mth> src{fp.depth[s]};
+    dense_tile<DepthSource<true, true, Mth>, kBlockThreads, ScalarArith<CUT>>(P, src, fp.color[s], tile0, n,
+                                                                             payload_bytes + (size_t)P.out_base * PCS_POINT_BYTES, stage);
+}
+
+// The general form: any stride, any payload alignment, any raster width (generic_tile without a predicate: every point of a stream is
+// in the sequence the stride runs over, a skipped one as its zero record).
+template <bool DS1, class Mth, bool CUT>
+__global__ __launch_bounds__(kBlockThreads, CUT ? SCALAR_EMIT_CUT_WAVES : EMIT_WAVES)
+void pcs_fused_emit_scalar_kernel(const StreamParams* __restrict__ params, int stream0, FramePtrs fp, uint32_t ds,
+                                  uint8_t* __restrict__ payload_bytes)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    __shared__ uint32_t wsum[4];
+    const int s = blockIdx.y;
+    const StreamParams& P = params[stream0 + s];
+    request_constants<true, Mth::kIdentR>(P, fp.depth[s], fp.color[s], payload_bytes);
+    const uint32_t n = P.n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    DepthSource<true, true, Mth> src{fp.depth[s]};
+    generic_tile<DepthSource<true, true, Mth>, false, DS1, ScalarArith<CUT>>(P, src, fp.color[s], tile0, n, 0u, ds, tile0, P.out_base,
+                                                                             payload_bytes, stage, wsum);
+}
+
+// a2 twin, no -c: blockIdx.y = cloud (one for the single-cloud calls).
+template <bool ALIGNED>
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_pack_scalar_kernel(const StreamParams* __restrict__ params, PackBatch pb)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    __shared__ uint32_t wsum[4];
+    const int e = blockIdx.y;
+    const VertexPtrs vp = pb.v[e];
+    const StreamParams& P = params[pb.stream[e]];
+    const uint32_t n = vp.n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    VertexSource src{vp.vertices, vp.texcoords};
+    if (ALIGNED)
+        dense_tile<VertexSource, kBlockThreads, ScalarArith<false>>(P, src, vp.color, tile0, n, pb.out[e], reinterpret_cast<uint4*>(stage));
+    else
+        generic_tile<VertexSource, false, true, ScalarArith<false>>(P, src, vp.color, tile0, n, 0u, 1u, tile0, 0u, pb.out[e], stage, wsum);
+}
+
+// a2 twin under -c: record i goes to slot i and a skipped slot keeps what the buffer held. The tile's own output bytes come into LDS
+// first (lane-contiguous 16-byte loads, 2-byte ones at its ragged ends: never a byte of a neighbouring tile), the kept records are
+// parked over them, and the whole range goes out again as 16-byte stores — a skipped slot is rewritten with its own bytes.
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_pack_scalar_cut_kernel(const StreamParams* __restrict__ params, int stream, VertexPtrs vp, uint8_t* __restrict__ out_bytes)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    const StreamParams& P = params[stream];
+    const uint32_t n = vp.n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    const uint32_t pts = min(kTilePoints, n - tile0);
+    uint8_t* gdst = out_bytes + (size_t)tile0 * PCS_POINT_BYTES;
+    const uint32_t head = (uint32_t)((uintptr_t)gdst & 15u);
+    load_staged(stage, head, pts * PCS_POINT_BYTES, gdst);
+    VertexSource src{vp.vertices, vp.texcoords};
+    const uint32_t i0 = tile0 + threadIdx.x * kPointsPerLane;
+    PointIn p[8];
+    src.load8(P, i0, n, p);
+    Record rec[8];
+    auto fill = [&](auto& cv) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) rec[k] = make_record<ScalarArith<false>>(P, vp.color, p[k], cv);
+    };
+    FastCvt<true> fast;
+    fill(fast);
+    if (__builtin_expect(fast.redo(), 0)) { ExactCvt exact; fill(exact); }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (i0 + k < n && scalar_cut_keeps(p[k].X, p[k].Z))
+            stage_record(stage, head + (threadIdx.x * kPointsPerLane + k) * PCS_POINT_BYTES, rec[k]);
+    __syncthreads();
+    store_staged(stage, head, pts * PCS_POINT_BYTES, gdst);
+}
+
 // Certificate of CertRowConst for one stream: row r's colour row through the IEEE chain for EVERY Z16 value 1 .. 65 535 (one workgroup
 // per raster row). crow[r] = the row for d = 1; *bad counts the (row, depth) pairs that give another one. The chain is the product's
 // own code (deproject_pixel + color_coords + the exact conversion), so the sweep cannot disagree with what the kernels would compute.
@@ -1519,6 +1652,50 @@ hipError_t launch_pack_emit(const StreamParams* d_params, int stream, const Vert
     else
         hipLaunchKernelGGL((pcs_pack_emit_kernel<false>), tile_grid(vp.n_points, 1), dim3(kBlockThreads), 0, st,
                            d_params, stream, vp, flags, d_tile_prefix, out);
+    return hipGetLastError();
+}
+
+// ---- a3: PCS_FLAG_SCALAR_ARITH ----
+hipError_t launch_fused_scalar(const StreamParams* d_params, int stream0, int n_launch, uint32_t max_points, bool dense, bool cut,
+                               int downsample, MathSel math, const FramePtrs& fp, int16_t* d_payload, hipStream_t st)
+{
+    if (n_launch <= 0 || max_points == 0) return hipSuccess;
+    const dim3 grid = tile_grid(max_points, n_launch);
+    uint8_t* out = reinterpret_cast<uint8_t*>(d_payload);
+    const bool ieee = math == MathSel::Ieee;
+#define LD(M, C) hipLaunchKernelGGL((pcs_fused_dense_scalar_kernel<M, C>), grid, dim3(kBlockThreads), 0, st, d_params, stream0, fp, out)
+#define LE(D1, M, C) hipLaunchKernelGGL((pcs_fused_emit_scalar_kernel<D1, M, C>), grid, dim3(kBlockThreads), 0, st, d_params, stream0, fp, \
+                                        (uint32_t)downsample, out)
+#define LEM(M, C) do { if (downsample == 1) LE(true, M, C); else LE(false, M, C); } while (0)
+    if (dense) {
+        if (ieee) { if (cut) LD(IeeeMath, true); else LD(IeeeMath, false); }
+        else      { if (cut) LD(CertMath<false>, true); else LD(CertMath<false>, false); }
+    } else {
+        if (ieee) { if (cut) LEM(IeeeMath, true); else LEM(IeeeMath, false); }
+        else      { if (cut) LEM(CertMath<false>, true); else LEM(CertMath<false>, false); }
+    }
+#undef LEM
+#undef LE
+#undef LD
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_scalar(const StreamParams* d_params, const PackBatch& pb, int n, uint32_t max_points, bool aligned,
+                              hipStream_t st)
+{
+    if (n <= 0 || max_points == 0) return hipSuccess;
+    if (n > kPackBatch) return hipErrorInvalidValue;
+    const dim3 grid = tile_grid(max_points, n);
+    if (aligned) hipLaunchKernelGGL((pcs_pack_scalar_kernel<true>), grid, dim3(kBlockThreads), 0, st, d_params, pb);
+    else         hipLaunchKernelGGL((pcs_pack_scalar_kernel<false>), grid, dim3(kBlockThreads), 0, st, d_params, pb);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_scalar_cut(const StreamParams* d_params, int stream, const VertexPtrs& vp, int16_t* d_out, hipStream_t st)
+{
+    if (vp.n_points == 0) return hipSuccess;
+    hipLaunchKernelGGL(pcs_pack_scalar_cut_kernel, tile_grid(vp.n_points, 1), dim3(kBlockThreads), 0, st, d_params, stream, vp,
+                       reinterpret_cast<uint8_t*>(d_out));
     return hipGetLastError();
 }
 

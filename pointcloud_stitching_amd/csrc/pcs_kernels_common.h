@@ -53,6 +53,7 @@ __device__ __forceinline__ int32_t cvt_sat(float f)
 // ignores NaN); the tile code re-does a lane's points with ExactCvt in the (practically never taken)
 // case that the maximum reached 2^31.
 struct ExactCvt {
+    [[maybe_unused]] static constexpr bool kTracks = false;              // (no running maximum: make_record's a3 branch then converts exactly)
     [[maybe_unused]] static constexpr bool kCoordsInShort = false;       // a converted coordinate may lie outside int16: the record keeps its low 16 bits
     __device__ __forceinline__ void note(float, float, float, float, float) {}
     __device__ __forceinline__ int32_t cvt(float f) const { return cvtt_x86(f); }
@@ -76,6 +77,7 @@ struct ExactCvt {
 // (pcs_capi.cpp: certify_no_overflow): then the running maximum is not needed at all.
 template <bool TRACK>
 struct FastCvt {
+    [[maybe_unused]] static constexpr bool kTracks = TRACK;
     [[maybe_unused]] static constexpr bool kCoordsInShort = false;
     float    hi = 0.0f;
     uint32_t max_idx = 0;
@@ -262,6 +264,60 @@ __device__ __forceinline__ float world_mm(const float* __restrict__ Mr, float X,
     a = __fmaf_rn(Y, Mr[1], a);
     a = __fmaf_rn(Z, Mr[2], a);
     return __fmul_rn(a, 1000.0f);
+}
+
+// a3, the reference's default (no -m) loop (src/pcs-camera-optimized.cpp:654-660), as its build compiles it (g++ -O3 -mfma, contraction
+// on; oracle/pcs_oracle.c: pcs_oracle_pack_scalar_variant restates that compile and is pinned to its bytes): the textbook order
+// ((m0*x + m1*y) + m2*z) + t with m1*y the one rounded product, m0*x and m2*z fused into the sums, + t a rounded sum; then `* CONV_RATE`
+// in DOUBLE — exact, 24 + 10 bits — and static_cast<short> of it, cvttsd2si: truncate, NaN or outside [-2^31, 2^31) -> 0x80000000.
+__device__ __forceinline__ float world_scalar(const float* __restrict__ Mr, float X, float Y, float Z)
+{
+    float a = __fmul_rn(Mr[1], Y);
+    a = __fmaf_rn(Mr[0], X, a);
+    a = __fmaf_rn(Mr[2], Z, a);
+    return __fadd_rn(a, Mr[3]);
+}
+// The conversion as written, for every a. Returns the converted value; the record keeps its low 16 bits. v_cvt_i32_f64 saturates,
+// which agrees with cvttsd2si in those bits for NaN (0 / INT_MIN) and below -2^31 (INT_MIN both) but not from 2^31 up (INT_MAX: 0xFFFF
+// where x86 leaves 0). a * 1000 >= 2^31 <=> a >= 2147483.648, and floats of that size are 0.25 apart: <=> a >= 2147483.75f — one FP32
+// compare; a NaN fails it and converts to 0.
+__device__ __forceinline__ uint32_t mm_scalar_exact(float a)
+{
+    const double s = __dmul_rn((double)a, 1000.0);
+    int32_t q;
+    asm("v_cvt_i32_f64 %0, %1" : "=v"(q) : "v"(s));
+    return a >= 2147483.75f ? 0u : (uint32_t)q;
+}
+// The same bits without FP64, for |a| < 2^14 (16 km; NaN included): with p = RN(a * 1000) and e = fma(a, 1000, -p) the product is
+// p + e exactly, so its round-towards-zero float is p itself, or — where e points back towards zero — p's neighbour on that side
+// (one less in the integer reading of its bits, either sign). |a * 1000| < 2^24, where every integer is a float: the truncation of
+// the product lies between that float and zero, so truncating the float gives it. (p * e cannot underflow to zero where it matters:
+// |p| >= 1 there and |e| >= 2^-149.) Callers take the exact form for anything larger: the Cvt policy's running maximum is told
+// |a| * 2^17, which reaches its 2^31 where |a| reaches 2^14.
+__device__ __forceinline__ uint32_t mm_scalar_residual(float a)
+{
+    const float p = __fmul_rn(a, 1000.0f);
+    const float e = __fmaf_rn(a, 1000.0f, -p);
+    const bool back = __fmul_rn(p, e) < 0.0f;
+    return (uint32_t)cvt_sat(__int_as_float(__float_as_int(p) - (int32_t)back));
+}
+
+// Pack arithmetic policies: which of the reference's two loops a record's world coordinates follow. The colour index is the same in
+// both (fma(u, W, .5f), truncate, clamp).
+//   SimdArith        -m, copyPointCloudXYZRGBToBufferSIMD (a2): world_mm and the Cvt policy's conversion. The default everywhere.
+//   ScalarArith<CUT> the default loop (a3): world_scalar and mm_scalar_residual / mm_scalar_exact. CUT: its -c test (:640-646) — a point is written iff z != 0 && x != 0 &&
+//                    !(z > 1.5) on the camera-frame floats (`-2 < x < 2` is always true; a NaN z or x passes) — there is no
+//                    compaction, so the fused tiles select a skipped point's record to zero and the a2 twin does not store it.
+struct SimdArith {
+    static constexpr bool kScalar = false, kCut = false;
+};
+template <bool CUT>
+struct ScalarArith {
+    static constexpr bool kScalar = true, kCut = CUT;
+};
+__device__ __forceinline__ bool scalar_cut_keeps(float X, float Z)
+{
+    return Z != 0.0f && X != 0.0f && !(Z > 1.5f);
 }
 
 // v_perm_b32: every result byte picks one of the 8 bytes of {hi, lo} (lo = bytes 0-3, hi = bytes 4-7).

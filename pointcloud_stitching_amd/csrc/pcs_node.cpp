@@ -597,6 +597,9 @@ int pcs_node_create_ex(pcs_node** out, int n_devices, const int* device_ids, int
     *out = nullptr;
     if (n_devices < 1 || !device_ids || streams_per_device < 1 || !streams || downsample < 1)
         return nfail(nullptr, PCS_ERR_INVALID_ARG, "bad arguments");
+    if (flags & PCS_FLAG_SCALAR_ARITH)      // a node is built from the voxel / partials / batch calls, none of which has an a3 form
+        return nfail(nullptr, PCS_ERR_UNSUPPORTED, "PCS_FLAG_SCALAR_ARITH: the reference's default arithmetic is not available on a node "
+                     "(libpcs_hip's a1 / a2 twins and pcs_process_frames take it)");
     {   // the stitched payload's byte count travels as an int32 (src/pcs-camera-optimized.cpp:697, 718;
         // src/pcs-multicamera-client.cpp:394): bound the WHOLE node's cloud, in 64 bits, before any device is touched
         uint64_t all = 0;

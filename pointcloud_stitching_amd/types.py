@@ -21,6 +21,7 @@ FLAG_CUTOFF_COMPAT = 0x2
 FLAG_DROP_INVALID = 0x4
 FLAG_FORCE_IEEE = 0x8
 FLAG_TEXCOORD_HALF_PIXEL = 0x10     # u = (px + 0.5)/W as older librealsense releases
+FLAG_SCALAR_ARITH = 0x20            # the reference's default (no -m) arithmetic, copyPointCloudXYZRGBToBuffer, bit for bit
 
 DISTORTION_NONE = 0
 DISTORTION_MODIFIED_BROWN_CONRADY = 1
