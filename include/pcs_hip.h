@@ -281,9 +281,15 @@ int pcs_stitch_device(pcs_ctx* ctx, const int16_t* const* d_cam_payload, const i
  *   x,y,z = (float)int16 / 1000.0f                     CONV_RATE is `const float CONV_RATE = 1000.0` in THAT file (:46)
  *   p'    = ((m0*x + m1*y) + m2*z) + m3 per row         pcl::transformPointCloud(cloud, cloud, transform[i]) (:289): PCL 1.8
  *                                                       transforms.hpp's expression; products and sums individually rounded
- *                                                       (the target is built without -mfma). THIRD-PARTY: parity unpinned.
+ *                                                       (the target is built without -mfma). THIRD-PARTY: this association
+ *                                                       is restated, parity with PCL unpinned.
  *   int16 = low 16 bits of cvttss2si(p' * 1000.0f)      static_cast<short>(x * CONV_RATE) (:255-257)
  *   colour: short 3 (R | G<<8) survives bit for bit, short 4 becomes B with a zero high byte (:240-242, :258-259)
+ * PINNED to the compiled reference (tests/test_reference_pin_centre.py, tests/golden/ref_centre/: both centre programs compiled
+ * against declaration-only PCL stand-ins): the decode, the encode, the stride rule, the count where the stride divides it, and the
+ * framing (header, payload at short 2). NOT pinned: PCL's association above — which does not matter for a matrix whose rows hold
+ * one entry of +-1 plus a translation (one rounding under any order; those cases are pinned end to end) — and FLOOR at
+ * n_points % downsample != 0, where the compiled reference cannot be driven (see below).
  * The round trip is LOSSY (decode, move, truncate) — it is the reference program's behaviour, not an improvement; the default
  * of the work-alike CLI stays the lossless concatenation. Cameras are written in index order into ONE stitched
  * payload (what `*stitched_cloud += *cloud_ptr[i]`, :361-364, and convertPointCloudXYZRGBToBuffer produce); all cameras of a

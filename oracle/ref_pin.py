@@ -4,6 +4,7 @@ TEST INFRASTRUCTURE ONLY, like pcs_oracle.py: tests/ and tests/golden/make_ref_p
 pointcloud_stitching_amd/, no smoke() and no benchmark does. The library is built by `make -C oracle ref
 REF_DIR=<reference checkout>` (oracle/Makefile; __graft_entry__.build() runs it when the checkout is there) from
 oracle/ref/ref_harness.cpp, which includes the reference translation unit by path. oracle/_ref/ is never committed.
+The same `make ref` builds the two centre programs' libraries, which ref_centre.py loads.
 
 The checkout is looked for at $PCS_REFERENCE_DIR, default /root/reference.
 

@@ -247,7 +247,7 @@ constexpr int kXformBatch = 16;
 struct XformCloud {
     const int16_t* in;          // the camera's payload as received
     uint8_t*       out;         // where its first kept record goes
-    uint32_t       n_out;       // records written = ceil(n_in / ds)
+    uint32_t       n_out;       // records written = floor(n_in / ds): the decoded cloud's width (:230)
     uint32_t       ds;          // keep every ds-th record (i % downsample == 0, :236)
     float          M[12];       // top three rows of transform[i], row-major
 };

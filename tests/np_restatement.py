@@ -100,24 +100,56 @@ def deproject_np(sc, depth, half_pixel=False):
     return vtx, tex
 
 
-def transform_payload_np(payload, m16, downsample=1):
-    """The centre's decode / affine / re-encode (src/pcs-multicamera-optimized.cpp:226-265, 289) in numpy float32: division by
-    1000.0f, ((m0*x + m1*y) + m2*z) + m3 with every product and sum rounded to float32, * 1000.0f, truncation, low 16 bits."""
+def decode_payload_np(payload, downsample=1):
+    """convertBufferToPointCloudXYZRGB (src/pcs-multicamera-optimized.cpp:226-248) -> (xyz float32[w, 3], rgb uint8[w, 3]):
+    every record with i % downsample == 0, at most size / downsample of them (:230), (float)short / 1000.0f, R and G the two
+    bytes of short 3, B the low byte of short 4."""
     f32 = np.float32
     d = max(int(downsample), 1)
     p = np.asarray(payload, np.int16).reshape(-1, 5)
     p = p[::d][:p.shape[0] // d]          # the cloud's width is size / downsample, rounded down (:230)
-    M = np.asarray(m16, f32).reshape(-1)
-    out = np.empty_like(p)
     with np.errstate(all="ignore"):
-        x, y, z = [(p[:, k].astype(f32) / f32(1000.0)).astype(f32) for k in range(3)]
+        xyz = (p[:, :3].astype(f32) / f32(1000.0)).astype(f32)
+    c = p[:, 3].view(np.uint16)
+    rgb = np.stack([c & 0xFF, c >> 8, p[:, 4].view(np.uint16) & 0xFF], -1).astype(np.uint8)
+    return xyz, rgb
+
+
+def affine_np(xyz, m16):
+    """pcl::transformPointCloud as PCL 1.8 evaluates it (:289; third-party, restated, unpinned): ((m0*x + m1*y) + m2*z) + m3 with
+    every product and sum rounded to float32. (PCL leaves a point with a non-finite coordinate alone when the cloud is not dense;
+    decoded coordinates are always finite.)"""
+    f32 = np.float32
+    xyz = np.asarray(xyz, f32).reshape(-1, 3)
+    M = np.asarray(m16, f32).reshape(-1)
+    x, y, z = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    out = np.empty_like(xyz)
+    with np.errstate(all="ignore"):
         for r in range(3):
             a = (M[4 * r] * x).astype(f32)
             a = (a + (M[4 * r + 1] * y).astype(f32)).astype(f32)
             a = (a + (M[4 * r + 2] * z).astype(f32)).astype(f32)
-            a = (a + M[4 * r + 3]).astype(f32)
-            a = (a * f32(1000.0)).astype(f32)
-            out[:, r] = (cvtt(a) & 0xFFFF).astype(np.uint16).view(np.int16)
-    out[:, 3] = p[:, 3]
-    out[:, 4] = (p[:, 4].view(np.uint16) & 0xFF).astype(np.int16)
+            out[:, r] = (a + M[4 * r + 3]).astype(f32)
     return out
+
+
+def encode_payload_np(xyz, rgb):
+    """convertPointCloudXYZRGBToBuffer (:251-265): static_cast<short>(coordinate * 1000.0f) = truncation, low 16 bits;
+    R + (G << 8) in short 3; B, high byte clear, in short 4."""
+    f32 = np.float32
+    xyz = np.asarray(xyz, f32).reshape(-1, 3)
+    rgb = np.asarray(rgb, np.uint8).reshape(-1, 3).astype(np.int64)
+    out = np.empty((xyz.shape[0], 5), np.int16)
+    with np.errstate(all="ignore"):
+        a = (xyz * f32(1000.0)).astype(f32)
+    out[:, :3] = (cvtt(a) & 0xFFFF).astype(np.uint16).view(np.int16)
+    out[:, 3] = ((rgb[:, 0] + (rgb[:, 1] << 8)) & 0xFFFF).astype(np.uint16).view(np.int16)
+    out[:, 4] = rgb[:, 2].astype(np.int16)
+    return out
+
+
+def transform_payload_np(payload, m16, downsample=1):
+    """The centre's decode / affine / re-encode (src/pcs-multicamera-optimized.cpp:226-265, 289) in numpy float32: division by
+    1000.0f, ((m0*x + m1*y) + m2*z) + m3 with every product and sum rounded to float32, * 1000.0f, truncation, low 16 bits."""
+    xyz, rgb = decode_payload_np(payload, downsample)
+    return encode_payload_np(affine_np(xyz, m16), rgb)

@@ -7,7 +7,8 @@ them bit for bit. No tolerance anywhere.
 
 Pinned by reference-produced bytes: a1 sendXYZRGBPointcloud (buffer layout), a2 copyPointCloudXYZRGBToBufferSIMD (`-m`, dense and
 `-c` with its reversed-mask order), a3 copyPointCloudXYZRGBToBuffer (non-`-m`, dense).
-NOT pinned here: a5 deprojection (librealsense's arithmetic), the central programs' PCL transform, the voxel grid.
+NOT pinned here: a5 deprojection (librealsense's arithmetic), the voxel grid, and the central programs, which
+test_reference_pin_centre.py pins (decode, encode, stride and framing; the association inside PCL's transform stays restated).
 
 Tiers. CPU tests run everywhere; those that call the live reference need oracle/_ref/libpcs_ref.so, which build() makes where the
 reference checkout exists. GPU tests (marked gpu) compare against the fixtures always, and against the live library when it
