@@ -140,6 +140,30 @@ const char*  pcs_last_error(const pcs_ctx* ctx);     /* detail of the last failu
 /* Replace one stream's camera->world matrix (the reference edits tf_mat in source, :64-67). */
 int          pcs_set_cam_to_world(pcs_ctx* ctx, int stream, const float m16[16]);
 
+/* ---- crop box: keep what lies inside a box in the WORLD frame (not in the reference) ----------------------------- *
+ * A context may carry one crop box: inclusive bounds lo[a] <= hi[a], int16 millimetres, world frame, axis order x, y, z. It is
+ * defined ON THE RECORD, the integer domain the voxel grid is defined in: a point is kept iff every one of its record's three
+ * shorts s_a satisfies lo[a] <= s_a <= hi[a], where s_a is what -m arithmetic writes — the low 16 bits of the converted
+ * coordinate, read as signed, i.e. AFTER the int16 wrap. A point 70 m out wraps to 4.464 m, and a box around that keeps it: the
+ * price of "cropping at the edge == cropping the same payload at the centre" (pcs_crop_payloads_device), which holds bit for bit.
+ *   - The box is ANDed with whatever the context's flags gate (CUTOFF, DROP_INVALID). CUTOFF_COMPAT's lane reversal applies to
+ *     the cutoff's own range bit only, never to the box bit.
+ *   - downsample keeps every downsample-th KEPT point per stream; output order is ascending point index per stream, streams in
+ *     index order; counts are device-known, exactly as under DROP_INVALID (the payload needs its worst-case capacity).
+ *   - Honoured by pcs_process_frames (staged and zero-copy), pcs_submit_frames / pcs_collect_frames, pcs_process_frames_device,
+ *     pcs_process_frames_device_batch and every voxel entry that starts from rasters (one call, partials, sink: they build the
+ *     cropped payload first and read that). Always count + scan + emit: PCS_COMPACT_PATH does not apply to a boxed context.
+ *   - Refused with PCS_ERR_UNSUPPORTED ("crop box" in pcs_last_error) while a box is set, nothing launched, nothing written:
+ *     pcs_process_frames_device_counted (a producer cannot know the world predicate) and the a1 / a2 twins in all forms (they
+ *     are signature twins of reference functions that have no such argument).
+ *   - pcs_stitch_device and pcs_transform_payloads_device move payloads and read no context predicate: unaffected.
+ * pcs_set_crop_box_mm: both pointers NULL clears the box; lo[a] > hi[a] or exactly one NULL is PCS_ERR_INVALID_ARG; on a
+ * PCS_FLAG_SCALAR_ARITH context PCS_ERR_UNSUPPORTED (such a context returns a3's bytes or fails). Ordering as
+ * pcs_set_cam_to_world: the context's stream is synchronised first, so no call enqueued earlier sees the change.
+ * pcs_get_crop_box_mm: 1 and the bounds if a box is set, 0 (lo / hi untouched) if not.                                            */
+int          pcs_set_crop_box_mm(pcs_ctx* ctx, const int16_t lo[3], const int16_t hi[3]);
+int          pcs_get_crop_box_mm(const pcs_ctx* ctx, int16_t lo[3], int16_t hi[3]);
+
 /* Which arithmetic the fused kernels use for `stream`: 0 = IEEE expansion, 1 = certified reduced-instruction
  * form, 2 = certified + identity depth->colour rotation shortcut; 3 / 4 = 1 / 2 plus the no-overflow certificate
  * (conversions cannot reach 2^31, so no running maximum is kept) (DESIGN.md "Certified arithmetic"). The
@@ -273,6 +297,18 @@ int pcs_deproject(pcs_ctx* ctx, int stream, const uint16_t* depth, float* vertic
  * Device pointers; *total_points is written on the HOST (counts are host-known).             */
 int pcs_stitch_device(pcs_ctx* ctx, const int16_t* const* d_cam_payload, const int* cam_points, int n_cams,
                       int downsample, int16_t* d_stitched_payload, size_t stitched_shorts, int* total_points);
+
+/* ---- the centre-side crop: the context's crop box over already packed per-camera payloads ------------------------- *
+ * For edge servers that cannot crop. Cameras are written in index order into one stitched payload; per camera the records
+ * inside the context's box (see pcs_set_crop_box_mm: the same predicate on the same shorts) are kept in order, and every
+ * downsample-th KEPT one is written (kept index % downsample == 0). Without a box every record is inside: pcs_stitch_device's
+ * bytes. d_counts: n_cams + 1 int32 on the DEVICE (written per camera, then the total) — the counts are data dependent.
+ * Inputs and output are 2-byte aligned device pointers (the reference's `buffer + 2` shorts makes them 4 mod 16);
+ * cam_points[i] == 0 is legal; n_cams <= PCS_MAX_STREAMS. stitched_shorts is checked on the host against the WORST case, the
+ * sum of ceil(cam_points[i] / downsample) records; any overlap of an input with that output range is refused.
+ * 10 B read twice + 10 B written per kept record.                                                                              */
+int pcs_crop_payloads_device(pcs_ctx* ctx, const int16_t* const* d_cam_payload, const int* cam_points, int n_cams,
+                             int downsample, int16_t* d_stitched_payload, size_t stitched_shorts, int32_t* d_counts);
 
 /* ---- the centre's re-transform of already packed payloads (src/pcs-multicamera-optimized.cpp:226-265, 289) ---------------- *
  * What the reference's pcs-multicamera-optimized does with every camera's payload before it concatenates them

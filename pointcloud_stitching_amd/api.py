@@ -109,6 +109,40 @@ class PcsContext:
         m = np.ascontiguousarray(m16, np.float32).reshape(16)
         self._check(self._lib.pcs_set_cam_to_world(self._h, stream, m.ctypes.data_as(C.POINTER(C.c_float))))
 
+    # -- crop box ------------------------------------------------------------------------------
+    def set_crop_box_mm(self, lo, hi) -> None:
+        """pcs_set_crop_box_mm: keep the points whose record lies inside lo <= (x, y, z) <= hi, int16 millimetres in the world frame
+        (after the int16 wrap; see the header). set_crop_box_mm(None, None) clears the box."""
+        if lo is None and hi is None:
+            self._check(self._lib.pcs_set_crop_box_mm(self._h, None, None))
+            return
+        def three(v):
+            if v is None:
+                return None
+            a = [int(x) for x in v]
+            if len(a) != 3 or any(x < -32768 or x > 32767 for x in a):
+                raise ValueError("a crop box bound is three int16 values (x, y, z in millimetres)")
+            return (C.c_int16 * 3)(*a)
+        self._check(self._lib.pcs_set_crop_box_mm(self._h, three(lo), three(hi)))
+
+    def crop_box_mm(self):
+        """((lo_x, lo_y, lo_z), (hi_x, hi_y, hi_z)) of the box that is set, or None."""
+        lo, hi = (C.c_int16 * 3)(), (C.c_int16 * 3)()
+        rc = self._lib.pcs_get_crop_box_mm(self._h, lo, hi)
+        if rc < 0:
+            self._check(rc)
+        return (tuple(int(x) for x in lo), tuple(int(x) for x in hi)) if rc == 1 else None
+
+    def crop_payloads_device(self, d_cam_payload: Sequence[int], cam_points: Sequence[int], downsample: int,
+                             d_stitched_payload: int, stitched_shorts: int, d_counts: int) -> None:
+        """pcs_crop_payloads_device: the context's crop box over packed per-camera payloads (device pointers), cameras in index order,
+        every downsample-th kept record written; d_counts receives len(cams) + 1 int32 on the device. Asynchronous."""
+        n = len(d_cam_payload)
+        ptrs = (C.c_void_p * max(n, 1))(*d_cam_payload)
+        cnts = (C.c_int * max(n, 1))(*cam_points)
+        self._check(self._lib.pcs_crop_payloads_device(self._h, ptrs, cnts, n, int(downsample), d_stitched_payload or None,
+                                                       stitched_shorts, d_counts or None))
+
     # -- a2 twin -----------------------------------------------------------------------------
     def copy_pointcloud_xyzrgb_to_buffer(self, stream: int, vertices, texcoords, color,
                                          pc_buffer: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:

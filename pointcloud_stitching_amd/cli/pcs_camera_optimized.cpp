@@ -7,6 +7,8 @@
 //               -r <frames>  -o <file> (dump last stitched buffer)  -p <port>
 //               -e <file> (camera-to-world matrices instead of the ones pasted into the reference's sources)
 //               -H (texture coordinates as older librealsense releases computed them: (pixel + 0.5) / size)
+//               -B <xlo,xhi,ylo,yhi,zlo,zhi> (crop box in millimetres, world frame, inclusive: an edge that crops before it sends;
+//                  pcs_set_crop_box_mm; needs -m)
 //
 //   -f takes "synth:<W>x<H>" (deterministic synthetic frames; the reference's bags are LFS stubs and
 //   need librealsense), a .pcsraw dump (see pointcloud_stitching_amd/synthetic.py: write_pcsraw) or a
@@ -27,6 +29,7 @@
 #include <unistd.h>
 
 #include "pcs_bag.h"
+#include "pcs_cropbox.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
 
@@ -39,6 +42,8 @@ static bool cutoff_compat = false, drop_invalid = false, pull_mode = false, half
 static int num_of_threads = 1, device = 0, n_streams = 1, downsample = 1, max_frames = 60, port = 8000;
 static const char* dump_path = nullptr;
 static const char* extrinsics_path = nullptr;
+static bool crop = false;
+static int16_t crop_lo[3], crop_hi[3];
 static int client_sock = 0, sockfd = 0;
 
 static void print_usage()
@@ -56,6 +61,8 @@ static void print_usage()
            "  -P        serve frames on 'Z' pull requests (the live server's protocol) instead of pushing them\n"
            "  -e <file> camera-to-world matrices, 16 row-major floats per line (python -m pointcloud_stitching_amd.calibration)\n"
            "  -H        texture coordinates as older librealsense releases: (pixel + 0.5) / size\n"
+           "  -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box: keep the points inside these inclusive bounds, millimetres in the WORLD frame\n"
+           "            (after the camera-to-world transform; ANDed with -c / -i; -d keeps every n-th KEPT point); needs -m\n"
            "  -M        hand the frames over in ordinary pageable memory, as librealsense owns them in the reference's timed region\n"
            "            (:291-293): uploads are staged then. Default: frames copied to page-locked rasters BEFORE the timer starts\n"
            "            (zero copy) - the printed times then belong to a capture pipeline that delivers page-locked frames\n\n");
@@ -64,7 +71,7 @@ static void print_usage()
 static void parseArgs(int argc, char** argv)
 {
     int c;
-    while ((c = getopt(argc, argv, "hf:vst:cmzg:n:d:iCr:o:p:e:PHM")) != -1) {
+    while ((c = getopt(argc, argv, "hf:vst:cmzg:n:d:iCr:o:p:e:PHMB:")) != -1) {
         switch (c) {
             case 'h': print_usage(); exit(0);
             case 'f': filename = optarg; break;
@@ -86,6 +93,12 @@ static void parseArgs(int argc, char** argv)
             case 'e': extrinsics_path = optarg; break;
             case 'P': pull_mode = true; send_buffer = true; break;
             case 'M': pageable = true; break;
+            case 'B': {
+                std::string why;
+                if (!pcs_cropbox::parse(optarg, crop_lo, crop_hi, why)) { std::cerr << "-B " << optarg << ": " << why << std::endl; exit(2); }
+                crop = true;
+                break;
+            }
             default: print_usage(); exit(2);
         }
     }
@@ -175,6 +188,7 @@ int main(int argc, char** argv)
                      "Use -f synth:<W>x<H>, -f <frames.pcsraw> or -f <recording.bag>." << std::endl;
         return 2;
     }
+    if (crop && !use_hip) { std::cerr << "-B needs -m: the reference's default loop (no -m) has no crop" << std::endl; return 2; }
     std::cout << "Reading Frames from File: " << filename << std::endl;
     FrameSource src;
     if (!src.open(filename)) { std::cerr << "cannot open frame source " << filename << std::endl; return 2; }
@@ -209,6 +223,10 @@ int main(int argc, char** argv)
     pcs_ctx* ctx = nullptr;
     int rc = pcs_create(&ctx, &cfg);
     if (rc != PCS_OK) { std::cerr << "pcs_create: " << pcs_strerror(rc) << ": " << pcs_last_error(nullptr) << std::endl; return 1; }
+
+    if (crop && (rc = pcs_set_crop_box_mm(ctx, crop_lo, crop_hi)) != PCS_OK) {
+        std::cerr << "pcs_set_crop_box_mm: " << pcs_strerror(rc) << ": " << pcs_last_error(ctx) << std::endl; return 1;
+    }
 
     const size_t buf_shorts = PCS_HEADER_SHORTS + pcs_max_payload_shorts(ctx);
     short* buffer = nullptr;                                               // the reference mallocs BUF_SIZE shorts (:157);

@@ -32,6 +32,10 @@
 //                      the format of pcs-camera-optimized -e) and re-encoded before the concatenation
 //                      (src/pcs-multicamera-optimized.cpp:226-265, 289; pcs_transform_payloads_device). Lossy, like the
 //                      reference's round trip; default off = pcs-multicamera-client's lossless concatenation.
+//              -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box in millimetres, world frame, inclusive (pcs_set_crop_box_mm): with -i the fused
+//                      path crops (with -V the cropped payload goes to pcs_voxel_grid_device_counted); with -c the received
+//                      payloads are cropped on the GPU (pcs_crop_payloads_device, after -T if both are given; -d is the crop
+//                      call's stride: every d-th KEPT record per camera). Not with -G: the node library has no setter.
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
@@ -46,6 +50,7 @@
 #include <getopt.h>
 #include <signal.h>
 
+#include "pcs_cropbox.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
 #include "../../include/pcs_node.h"
@@ -62,6 +67,8 @@ static const char* source = nullptr;
 static const char* cameras = nullptr;
 static const char* dump_path = nullptr;
 static const char* transform_path = nullptr;
+static bool crop = false;
+static int16_t crop_lo[3], crop_hi[3];
 
 static void usage()
 {
@@ -80,6 +87,8 @@ static void usage()
               << "                  (-R payloads: gather the packed payloads instead and downsample the stitched cloud on GPU 0)\n"
               << " -T <file>        with -c: re-transform every camera's payload by transform[i] (16 values per line) before stitching,\n"
               << "                  as the reference's pcs-multicamera-optimized does (decode, pcl::transformPointCloud, re-encode)\n"
+              << " -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box, millimetres in the world frame, inclusive: -i crops in the fused path, -c crops the\n"
+              << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
               << " -s / -v / -n     PCL viewer features of the reference; not available in this build\n";
 }
@@ -88,7 +97,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -116,6 +125,12 @@ int main(int argc, char** argv)
             case 'Z': drop_invalid = true; break;
             case 'P': pipelined = true; break;
             case 'T': transform_path = optarg; break;
+            case 'B': {
+                std::string why;
+                if (!pcs_cropbox::parse(optarg, crop_lo, crop_hi, why)) { std::cerr << "-B " << optarg << ": " << why << std::endl; return 2; }
+                crop = true;
+                break;
+            }
             case 's': case 'v': case 'n':
                 std::cerr << "-" << (char)c << " drives the reference's PCL viewer / PLY writer, which this build does not include" << std::endl;
                 return 2;
@@ -123,6 +138,7 @@ int main(int argc, char** argv)
         }
     }
     if (downsample < 1) { std::cerr << "downsample must be >= 1" << std::endl; return 2; }
+    if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
     if (!source && !cameras) source = "synth:1280x720";      // no live cameras on this node: the synthetic generator
     if (voxel_leaf < 0 || voxel_leaf > 32767) { std::cerr << "-V leaf must be 1..32767 mm" << std::endl; return 2; }
@@ -200,6 +216,10 @@ int main(int argc, char** argv)
     int rc = pcs_create(&ctx, &cfg);
     if (rc != PCS_OK) { std::cerr << "pcs_create: " << pcs_strerror(rc) << ": " << pcs_last_error(nullptr) << std::endl; return 1; }
 
+    if (crop && (rc = pcs_set_crop_box_mm(ctx, crop_lo, crop_hi)) != PCS_OK) {
+        std::cerr << "pcs_set_crop_box_mm: " << pcs_strerror(rc) << ": " << pcs_last_error(ctx) << std::endl; return 1;
+    }
+
     pcs_node* node = nullptr;
     if (n_gpus > 0) {
         if (!source) { std::cerr << "-G applies to cameras on this node (-i)" << std::endl; return 2; }
@@ -247,6 +267,19 @@ int main(int argc, char** argv)
     if (!source) {
         for (int i = 0; i < n_streams; i++) if (pcs_device_malloc(ctx, &d_cam[i], cam_cap_bytes) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
         if (pcs_device_malloc(ctx, &d_stitched, (size_t)n_streams * cam_cap_bytes + 64) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+    }
+
+    // -B with -c: the crop's output (its inputs are the cameras' buffers, or d_stitched's slices behind -T) and its device counts
+    void *d_cropped = nullptr, *d_crop_counts = nullptr;
+    if (crop && !source) {
+        if (pcs_device_malloc(ctx, &d_cropped, (size_t)n_streams * cam_cap_bytes + 64) != PCS_OK ||
+            pcs_device_malloc(ctx, &d_crop_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+    }
+    // -B with -i -V: the cropped payload and its counts stay on the device between the two calls
+    void *d_pay = nullptr, *d_pay_counts = nullptr;
+    if (crop && source && voxel_leaf) {
+        if (pcs_device_malloc(ctx, &d_pay, pcs_max_payload_shorts(ctx) * sizeof(int16_t) + 64) != PCS_OK ||
+            pcs_device_malloc(ctx, &d_pay_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
 
     // -V: device-resident rasters (with -i) and the voxel cloud
@@ -447,6 +480,15 @@ int main(int argc, char** argv)
                         pcs_memcpy_h2d(ctx, d_color[s], color[s].data(), color[s].size()) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
                 }
                 auto run_voxel = [&]() {
+                    if (crop) {     // the cropped payload, then its voxel grid: the point count never leaves the device
+                        int r = pcs_process_frames_device(ctx, reinterpret_cast<const uint16_t* const*>(d_depth.data()),
+                                                          reinterpret_cast<const uint8_t* const*>(d_color.data()), static_cast<int16_t*>(d_pay),
+                                                          pcs_max_payload_shorts(ctx), static_cast<int32_t*>(d_pay_counts));
+                        if (r != PCS_OK) return r;
+                        return pcs_voxel_grid_device_counted(ctx, static_cast<const int16_t*>(d_pay), static_cast<const int32_t*>(d_pay_counts) + n_streams,
+                                                             (int)(pcs_max_payload_shorts(ctx) / PCS_POINT_SHORTS), voxel_leaf, static_cast<int16_t*>(d_vox),
+                                                             vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
+                    }
                     return pcs_process_frames_voxel_device(ctx, reinterpret_cast<const uint16_t* const*>(d_depth.data()),
                                                            reinterpret_cast<const uint8_t* const*>(d_color.data()), voxel_leaf,
                                                            static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
@@ -481,7 +523,28 @@ int main(int argc, char** argv)
             }
             if (!ok) { std::cout << "camera stream ended" << std::endl; break; }
             int total_pts = 0;
-            if (transform_path) {       // the reference program's own semantics: decode, transform[i], re-encode, concatenate
+            const int16_t* d_result = static_cast<const int16_t*>(d_stitched);
+            if (crop) {
+                // -T first (every record, stride 1), then the box over the moved payloads with the stride -d
+                if (transform_path) {
+                    std::vector<int> per(n_streams);
+                    for (int i = 0; i < n_streams; i++) { xf[i].d_payload = dptr[i]; xf[i].n_points = pts[i]; }
+                    rc = pcs_transform_payloads_device(ctx, n_streams, xf.data(), 1, static_cast<int16_t*>(d_stitched),
+                                                       (size_t)n_streams * cam_cap_bytes / 2, per.data(), &total_pts);
+                    if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                    size_t first = 0;
+                    for (int i = 0; i < n_streams; i++) { dptr[i] = static_cast<const int16_t*>(d_stitched) + first * PCS_POINT_SHORTS; pts[i] = per[i]; first += (size_t)per[i]; }
+                }
+                rc = pcs_crop_payloads_device(ctx, dptr.data(), pts.data(), n_streams, downsample, static_cast<int16_t*>(d_cropped),
+                                              (size_t)n_streams * cam_cap_bytes / 2, static_cast<int32_t*>(d_crop_counts));
+                if (rc == PCS_OK) {
+                    std::vector<int32_t> kept(n_streams + 1, 0);
+                    rc = pcs_memcpy_d2h(ctx, kept.data(), d_crop_counts, kept.size() * sizeof(int32_t));
+                    if (rc == PCS_OK) rc = pcs_synchronize(ctx);
+                    total_pts = kept[n_streams];
+                }
+                d_result = static_cast<const int16_t*>(d_cropped);
+            } else if (transform_path) {       // the reference program's own semantics: decode, transform[i], re-encode, concatenate
                 for (int i = 0; i < n_streams; i++) { xf[i].d_payload = dptr[i]; xf[i].n_points = pts[i]; }
                 rc = pcs_transform_payloads_device(ctx, n_streams, xf.data(), downsample, static_cast<int16_t*>(d_stitched),
                                                    (size_t)n_streams * cam_cap_bytes / 2, nullptr, &total_pts);
@@ -491,14 +554,14 @@ int main(int argc, char** argv)
             if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
             if (voxel_leaf) {
                 auto run_voxel = [&]() {
-                    return pcs_voxel_grid_device(ctx, static_cast<const int16_t*>(d_stitched), total_pts, voxel_leaf, static_cast<int16_t*>(d_vox),
+                    return pcs_voxel_grid_device(ctx, d_result, total_pts, voxel_leaf, static_cast<int16_t*>(d_vox),
                                                  vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
                 };
                 rc = run_voxel();
                 if (rc != PCS_OK || !fetch_voxels(run_voxel)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
             } else {
                 size_bytes = total_pts * PCS_POINT_BYTES;
-                if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, d_stitched, (size_t)size_bytes) != PCS_OK) return 1;
+                if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, d_result, (size_t)size_bytes) != PCS_OK) return 1;
                 pcs_synchronize(ctx);
                 memcpy(stitched.data(), &size_bytes, sizeof(int));                                         // :394-395
             }
@@ -530,6 +593,7 @@ int main(int argc, char** argv)
     if (d_vox) pcs_device_free(ctx, d_vox);
     if (d_nvox) pcs_device_free(ctx, d_nvox);
     if (d_stitched) pcs_device_free(ctx, d_stitched);
+    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts}) if (p) pcs_device_free(ctx, p);
     if (node) pcs_node_destroy(node);
     stitched.release();
     pcs_destroy(ctx);

@@ -351,7 +351,8 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(ev.first, c->stream));
     }
-    const bool one_launch = pred && c->downsample == 1 && c->single_pass_ok && !force_three_pass && !d_tile_kept;
+    const bool box = has_box(c);       // a boxed context always takes count + scan + emit (PCS_COMPACT_PATH does not apply)
+    const bool one_launch = pred && !box && c->downsample == 1 && c->single_pass_ok && !force_three_pass && !d_tile_kept;
     const bool single_pass = one_launch && c->compact_path == 1;
     if (single_pass) {
         if (!c->d_ticket) {
@@ -405,7 +406,8 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
             FramePtrs fp{};
             uint32_t mp = 0;
             for (int k = 0; k < nl; k++) { fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k]; mp = std::max(mp, c->h_params[s0 + k].n_points); }
-            HIPCHK(c, launch_fused_count(c->d_params, s0, nl, mp, c->flags, fp, c->d_tile_counts, c->stream));
+            if (box) HIPCHK(c, launch_fused_count_crop(c->d_params, s0, nl, mp, c->flags, c->box, fp, c->d_tile_counts, c->stream));
+            else     HIPCHK(c, launch_fused_count(c->d_params, s0, nl, mp, c->flags, fp, c->d_tile_counts, c->stream));
         }
         // per-stream counts come from the scan; the grand total from the first emit launch (no last-arriver atomic)
         HIPCHK(c, launch_scan(c->d_params, c->n_streams, c->downsample, d_tile_kept ? d_tile_kept : c->d_tile_counts, c->d_tile_prefix,
@@ -435,6 +437,10 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
         else if (dense) // (the dense kernel's row-constant form: its colour window is requested beside the depth, pcs_kernels.hip)
             HIPCHK(c, launch_fused_dense(c->d_params, s0, nl, mp, dd, cd, sel == MathSel::CertIdentRNoOvf && rowc ? MathSel::CertRowConstNoOvf : sel,
                                          fp, d_payload, c->stream));
+        else if (box)
+            HIPCHK(c, launch_fused_emit_crop(c->d_params, s0, nl, mp, c->flags, c->box, c->downsample, sel, fp, c->d_tile_prefix,
+                                             c->d_stream_base, d_payload, (d_counts ? d_counts : c->d_counts) + c->n_streams, c->n_streams,
+                                             c->stream));
         else
             HIPCHK(c, launch_fused_emit(c->d_params, s0, nl, mp, c->flags, c->downsample, sel, fp, c->d_tile_prefix,
                                         c->d_stream_base, d_payload,
@@ -753,6 +759,8 @@ void pcs_destroy(pcs_ctx* c)
     for (auto& pr : c->ev_free) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
+    if (c->d_crop_tab) (void)hipFree(c->d_crop_tab);
+    if (c->d_crop_tiles) (void)hipFree(c->d_crop_tiles);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -769,6 +777,37 @@ int pcs_set_cam_to_world(pcs_ctx* c, int stream, const float m16[16])
     q.no_overflow = (q.cert_fast && certify_no_overflow(c->cfg[stream], c->cert[stream], m16)) ? 1 : 0;
     c->math[stream] = q.cert_fast ? ((q.ident_r ? 2 : 1) + (q.no_overflow ? 2 : 0)) : 0;
     return upload_params(c);
+}
+
+// ---- crop box ----------------------------------------------------------------------------------
+int pcs_set_crop_box_mm(pcs_ctx* c, const int16_t lo[3], const int16_t hi[3])
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (scalar_arith(c))
+        return fail(c, PCS_ERR_UNSUPPORTED, "pcs_set_crop_box_mm is not available on a context created with PCS_FLAG_SCALAR_ARITH: "
+                    "such a context returns the reference's default-arithmetic bytes or fails, and that loop has no crop");
+    if ((lo == nullptr) != (hi == nullptr)) return fail(c, PCS_ERR_INVALID_ARG, "crop box: lo and hi must both be given, or both be NULL");
+    if (lo)
+        for (int a = 0; a < 3; a++)
+            if (lo[a] > hi[a]) return fail(c, PCS_ERR_INVALID_ARG, "crop box: lo[%d] = %d > hi[%d] = %d", a, lo[a], a, hi[a]);
+    DeviceGuard guard(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // pcs_set_cam_to_world's rule: nothing enqueued earlier sees the change
+    if (!lo) {
+        c->flags &= ~PCS_KFLAG_CROP_BOX;
+        return PCS_OK;
+    }
+    for (int a = 0; a < 3; a++) { c->box_lo[a] = lo[a]; c->box_hi[a] = hi[a]; }
+    c->box = crop_box_arg(c->box_lo, c->box_hi);      // travels in the kernels' arguments: nothing to upload
+    c->flags |= PCS_KFLAG_CROP_BOX;
+    return PCS_OK;
+}
+
+int pcs_get_crop_box_mm(const pcs_ctx* c, int16_t lo[3], int16_t hi[3])
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (!has_box(c)) return 0;
+    for (int a = 0; a < 3; a++) { if (lo) lo[a] = c->box_lo[a]; if (hi) hi[a] = c->box_hi[a]; }
+    return 1;
 }
 
 int pcs_stream_points(const pcs_ctx* c, int stream)
@@ -800,6 +839,7 @@ int pcs_copy_pointcloud_xyzrgb_to_buffer_device(pcs_ctx* c, int stream, const fl
                                                 int16_t* d_pc_buffer, int* d_out_points)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_CROP_BOX(c, "pcs_copy_pointcloud_xyzrgb_to_buffer_device");
     if (stream < 0 || stream >= c->n_streams) return fail(c, PCS_ERR_INVALID_ARG, "stream %d out of range", stream);
     if (n_points < 0) return fail(c, PCS_ERR_INVALID_ARG, "n_points %d < 0", n_points);
     if (n_points > 0 && (!d_vertices || !d_texcoords || !d_color || !d_pc_buffer))
@@ -854,6 +894,7 @@ int pcs_copy_pointcloud_xyzrgb_to_buffer_device(pcs_ctx* c, int stream, const fl
 int pcs_copy_pointclouds_xyzrgb_to_buffer_device(pcs_ctx* c, int n_clouds, const pcs_cloud_desc* clouds, int* d_out_points)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_CROP_BOX(c, "pcs_copy_pointclouds_xyzrgb_to_buffer_device");
     if (n_clouds < 0 || (n_clouds > 0 && !clouds)) return fail(c, PCS_ERR_INVALID_ARG, "bad cloud list");
     for (int i = 0; i < n_clouds; i++) {
         const pcs_cloud_desc& q = clouds[i];
@@ -971,6 +1012,7 @@ int pcs_copy_pointcloud_xyzrgb_to_buffer(pcs_ctx* c, int stream, const float* ve
                                          int n_points, const uint8_t* color, int16_t* pc_buffer, int* out_points)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_CROP_BOX(c, "pcs_copy_pointcloud_xyzrgb_to_buffer");
     if (stream < 0 || stream >= c->n_streams) return fail(c, PCS_ERR_INVALID_ARG, "stream %d out of range", stream);
     if (n_points < 0) return fail(c, PCS_ERR_INVALID_ARG, "n_points %d < 0", n_points);
     if (n_points > 0 && (!vertices || !texcoords || !color || !pc_buffer))
@@ -1029,6 +1071,7 @@ int pcs_send_xyzrgb_pointcloud(pcs_ctx* c, int stream, const float* vertices, co
                                int* out_size_bytes)
 {
     if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_CROP_BOX(c, "pcs_send_xyzrgb_pointcloud");
     if (!buffer) return fail(c, PCS_ERR_INVALID_ARG, "buffer is NULL");
     if (n_points < 0) return fail(c, PCS_ERR_INVALID_ARG, "n_points %d < 0", n_points);
     const size_t need = PCS_HEADER_SHORTS + (size_t)n_points * PCS_POINT_SHORTS;
@@ -1078,6 +1121,7 @@ int pcs_process_frames_device_counted(pcs_ctx* c, const uint16_t* const* d_depth
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
     PCS_NO_SCALAR_ARITH(c, "pcs_process_frames_device_counted");
+    PCS_NO_CROP_BOX(c, "pcs_process_frames_device_counted");
     if (!d_depth || !d_color || !d_payload || !d_tile_kept) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     if ((uintptr_t)d_tile_kept & 3u) return fail(c, PCS_ERR_INVALID_ARG, "d_tile_kept must be 4-byte aligned");
     for (int s = 0; s < c->n_streams; s++) {
@@ -1164,8 +1208,12 @@ try {
                     bp.color[k * S + s] = d_color[(size_t)(k0 + k) * S + s];
                 }
             }
-            HIPCHK(c, launch_compact_batch(c->d_params, S, nk, c->max_points, c->total_tiles, c->flags, sel, bp, bc,
-                                           tcounts, tprefix, kept, c->stream));
+            if (has_box(c))
+                HIPCHK(c, launch_crop_batch(c->d_params, S, nk, c->max_points, c->total_tiles, c->flags, c->box, sel, bp, bc,
+                                            tcounts, tprefix, kept, c->stream));
+            else
+                HIPCHK(c, launch_compact_batch(c->d_params, S, nk, c->max_points, c->total_tiles, c->flags, sel, bp, bc,
+                                               tcounts, tprefix, kept, c->stream));
         }
         if (c->kernel_timing) {
             HIPCHK(c, hipEventRecord(ev.second, c->stream));
@@ -1358,6 +1406,7 @@ try {
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(sl->done, c->stream));
     sl->busy = true;
+    sl->pred = has_pred(c->flags);
     sl->ticket = c->next_ticket++;
     *ticket = sl->ticket;
     return PCS_OK;
@@ -1390,7 +1439,7 @@ try {
     HIPCHK(c, hipStreamWaitEvent(c->dl_stream, sl->done, 0));
     std::vector<int32_t> h(c->n_streams + 1);
     size_t total;
-    if (has_pred(c->flags)) {        // the payload size is data dependent: counts first
+    if (sl->pred) {                  // the payload size is data dependent: counts first (as submitted, not as the context is now)
         HIPCHK(c, hipMemcpyAsync(h.data(), sl->counts, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->dl_stream));
         HIPCHK(c, hipStreamSynchronize(c->dl_stream));
         total = (size_t)h[c->n_streams];
@@ -1467,6 +1516,59 @@ int pcs_stitch_device(pcs_ctx* c, const int16_t* const* d_cam_payload, const int
     }
     if (total_points) *total_points = (int)out;
     return PCS_OK;
+}
+
+// ---- centre-side crop of packed payloads -------------------------------------------------------
+int pcs_crop_payloads_device(pcs_ctx* c, const int16_t* const* d_cam_payload, const int* cam_points, int n_cams, int downsample,
+                             int16_t* d_stitched_payload, size_t stitched_shorts, int32_t* d_counts)
+try {
+    if (!c) return PCS_ERR_INVALID_ARG;
+    PCS_NO_SCALAR_ARITH(c, "pcs_crop_payloads_device");
+    if (n_cams < 0 || n_cams > PCS_MAX_STREAMS) return fail(c, PCS_ERR_INVALID_ARG, "n_cams %d outside 0..%d", n_cams, PCS_MAX_STREAMS);
+    if (!d_counts || (n_cams > 0 && (!d_cam_payload || !cam_points))) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
+    if ((uintptr_t)d_counts & 3u) return fail(c, PCS_ERR_INVALID_ARG, "d_counts must be 4-byte aligned");
+    if (downsample < 1) return fail(c, PCS_ERR_INVALID_ARG, "downsample %d < 1", downsample);
+    size_t need = 0, tiles = 0;
+    std::vector<uint32_t> n(n_cams > 0 ? n_cams : 0);
+    for (int i = 0; i < n_cams; i++) {
+        if (cam_points[i] < 0) return fail(c, PCS_ERR_INVALID_ARG, "camera %d: negative point count", i);
+        if (cam_points[i] > 0 && !d_cam_payload[i]) return fail(c, PCS_ERR_INVALID_ARG, "camera %d: NULL payload", i);
+        if ((uintptr_t)d_cam_payload[i] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "camera %d: payload pointer must be 2-byte aligned", i);
+        n[i] = (uint32_t)cam_points[i];
+        need += ((size_t)n[i] + downsample - 1) / downsample;       // the worst case: every record inside the box
+        tiles += tiles_of(n[i]);
+    }
+    if (need * PCS_POINT_BYTES > 0x7FFFFFFFull)
+        return fail(c, PCS_ERR_INVALID_ARG, "stitched payload of %zu points exceeds the int32 byte-count header", need);
+    if (need && !d_stitched_payload) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
+    if ((uintptr_t)d_stitched_payload & 1u) return fail(c, PCS_ERR_INVALID_ARG, "payload pointer must be 2-byte aligned");
+    if (stitched_shorts < need * PCS_POINT_SHORTS)
+        return fail(c, PCS_ERR_CAPACITY, "stitched payload holds %zu shorts; the worst case %zu is required", stitched_shorts,
+                    need * PCS_POINT_SHORTS);
+    // tiles of different cameras write while others still read: no input may meet the output's worst-case range
+    const uintptr_t o0 = (uintptr_t)d_stitched_payload, o1 = o0 + need * PCS_POINT_BYTES;
+    for (int j = 0; j < n_cams; j++) {
+        const uintptr_t i0 = (uintptr_t)d_cam_payload[j], i1 = i0 + (size_t)n[j] * PCS_POINT_BYTES;
+        if (n[j] && o0 < i1 && i0 < o1) return fail(c, PCS_ERR_INVALID_ARG, "camera %d's input overlaps the stitched output", j);
+    }
+    DeviceGuard guard(c->device);
+    if (n_cams == 0) { HIPCHK(c, hipMemsetAsync(d_counts, 0, sizeof(int32_t), c->stream)); return PCS_OK; }
+    if (!c->d_crop_tab) {
+        HIPCHK(c, hipMalloc((void**)&c->d_crop_tab, sizeof(StreamParams) * PCS_MAX_STREAMS));
+        HIPCHK(c, hipMemsetAsync(c->d_crop_tab, 0, sizeof(StreamParams) * PCS_MAX_STREAMS, c->stream));
+    }
+    const size_t tt = std::max<size_t>(tiles, 1);
+    const size_t words = 2 * tt + PCS_MAX_STREAMS;
+    if (words * sizeof(uint32_t) > c->crop_tiles_cap) HIPCHK(c, hipStreamSynchronize(c->stream));   // (the old one may be in use)
+    int rc = ensure(c, c->d_crop_tiles, c->crop_tiles_cap, words * sizeof(uint32_t));
+    if (rc) return rc;
+    static const int16_t full_lo[3] = {-32768, -32768, -32768}, full_hi[3] = {32767, 32767, 32767};
+    const CropBoxArg box = has_box(c) ? c->box : crop_box_arg(full_lo, full_hi);      // no box: every record is inside
+    HIPCHK(c, launch_crop_payloads(c->d_crop_tab, d_cam_payload, n.data(), n_cams, box, downsample, c->d_crop_tiles, c->d_crop_tiles + tt,
+                                   c->d_crop_tiles + 2 * tt, d_stitched_payload, d_counts, c->stream));
+    return PCS_OK;
+} catch (const std::exception& ex) {
+    return fail(c, PCS_ERR_NOMEM, "pcs_crop_payloads_device: host allocation failed (%s)", ex.what());
 }
 
 // ---- the centre's re-transform of packed payloads (src/pcs-multicamera-optimized.cpp:226-265, 289) ----------

@@ -85,6 +85,7 @@ int pcs_voxel_grid_device_counted(pcs_ctx* c, const int16_t* d_payload, const in
 static bool voxel_reads_rasters(const pcs_ctx* c, const uint16_t* const* d_depth, int leaf_mm)
 {
     if (c->downsample != 1) return false;
+    if (pcs_host::has_box(c)) return false;      // the box is a predicate on the record: the cropped payload first, then its reader
     bool all_patch = true;
     for (int s = 0; s < c->n_streams; s++) all_patch &= (c->h_params[s].W & 7) == 0 && ((uintptr_t)d_depth[s] & 15u) == 0;
     return all_patch || leaf_mm >= 36;

@@ -174,6 +174,34 @@ hipError_t launch_pack_scalar(const StreamParams* d_params, const PackBatch& pb,
                               hipStream_t st);
 hipError_t launch_pack_scalar_cut(const StreamParams* d_params, int stream, const VertexPtrs& vp, int16_t* d_out, hipStream_t st);
 
+// Crop box (pcs_set_crop_box_mm): the box as the three dwords the kernels take (pcs_kernels_common.h: CropBox) —
+// w[0] = lo_x | lo_y << 16, w[1] = lo_z | span_z << 16, w[2] = span_x | span_y << 16, span = hi - lo. Always count + scan + emit
+// (launch_scan is the existing one); `math` is the emit launch's policy, whose conversion ladder the count pass shares.
+// PCS_KFLAG_CROP_BOX: an internal bit of a context's flag word (never accepted from pcs_config.flags): a box is set.
+constexpr uint32_t PCS_KFLAG_CROP_BOX = 0x40000000u;
+struct CropBoxArg { uint32_t w[3]; };
+inline CropBoxArg crop_box_arg(const int16_t lo[3], const int16_t hi[3])
+{
+    const uint32_t l[3] = {(uint16_t)lo[0], (uint16_t)lo[1], (uint16_t)lo[2]};
+    const uint32_t sp[3] = {(uint32_t)(hi[0] - lo[0]), (uint32_t)(hi[1] - lo[1]), (uint32_t)(hi[2] - lo[2])};
+    return CropBoxArg{{l[0] | l[1] << 16, l[2] | sp[2] << 16, sp[0] | sp[1] << 16}};
+}
+hipError_t launch_fused_count_crop(const StreamParams* d_params, int stream0, int n_launch, uint32_t max_points, uint32_t flags,
+                                   const CropBoxArg& box, const FramePtrs& fp, uint32_t* d_tile_counts, hipStream_t st);
+hipError_t launch_fused_emit_crop(const StreamParams* d_params, int stream0, int n_launch, uint32_t max_points, uint32_t flags,
+                                  const CropBoxArg& box, int downsample, MathSel math, const FramePtrs& fp, const uint32_t* d_tile_prefix,
+                                  const uint32_t* d_stream_kept, int16_t* d_payload, int32_t* d_total_out, int n_total_streams,
+                                  hipStream_t st);
+// K frame-sets (stride 1): count, scan, emit each cover all of them, as launch_compact_batch.
+hipError_t launch_crop_batch(const StreamParams* d_params, int n_streams, int n_sets, uint32_t max_points, uint32_t total_tiles,
+                             uint32_t flags, const CropBoxArg& box, MathSel math, const BatchPtrs& bp, const BatchCounts& bc,
+                             uint32_t* d_tile_counts, uint32_t* d_tile_prefix, uint32_t* d_stream_kept, hipStream_t st);
+// Centre side (pcs_crop_payloads_device): n_cams <= PCS_MAX_STREAMS packed payloads -> one stitched payload. d_tab: n_cams table
+// entries (filled here, on the stream); d_tile_counts / d_tile_prefix: one word per input tile; d_cam_kept: n_cams; d_counts: n_cams + 1.
+hipError_t launch_crop_payloads(StreamParams* d_tab, const int16_t* const* d_in, const uint32_t* n_points, int n_cams,
+                                const CropBoxArg& box, int downsample, uint32_t* d_tile_counts, uint32_t* d_tile_prefix,
+                                uint32_t* d_cam_kept, int16_t* d_out, int32_t* d_counts, hipStream_t st);
+
 // a5 alone.
 hipError_t launch_deproject(const StreamParams* d_params, int stream, uint32_t n_points, const uint16_t* d_depth,
                             float* d_vertices, float* d_texcoords, hipStream_t st);

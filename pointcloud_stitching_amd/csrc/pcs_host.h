@@ -94,6 +94,8 @@ struct pcs_ctx {
         int32_t*               counts = nullptr;       // device, n_streams + 1
         hipEvent_t             done = nullptr;
         bool                   busy = false;
+        bool                   pred = false;           // submitted under a predicate (flags or box): the counts are on the device.
+                                                       // Kept per slot: pcs_set_crop_box_mm may change the context between submit and collect
         int                    ticket = -1;
     };
     PipeSlot                        pipe[PCS_PIPELINE_DEPTH];
@@ -102,6 +104,12 @@ struct pcs_ctx {
 
     struct ZcEntry { const void* host; size_t bytes; void* dev; int verdict; };
     std::vector<ZcEntry>            zc_cache;                  // zero-copy eligibility verdicts (host_device_view)
+
+    // pcs_set_crop_box_mm: the box (flags carries PCS_KFLAG_CROP_BOX while one is set) and pcs_crop_payloads_device's scratch
+    int16_t                         box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+    CropBoxArg                      box{};
+    StreamParams*                   d_crop_tab = nullptr;      // PCS_MAX_STREAMS entries (n_points, tile_base of each camera)
+    uint32_t*                       d_crop_tiles = nullptr; size_t crop_tiles_cap = 0;   // bytes: counts, prefixes, kept per camera
 
     std::string                     err;
 };
@@ -121,8 +129,9 @@ int fail(pcs_ctx* c, int status, const char* fmt, ...);
 // the counts are the configuration's and the launches are the predicate-free ones with a per-point select.
 inline bool has_pred(uint32_t flags)
 {
-    return !(flags & PCS_FLAG_SCALAR_ARITH) && (flags & (PCS_FLAG_CUTOFF | PCS_FLAG_DROP_INVALID)) != 0;
+    return !(flags & PCS_FLAG_SCALAR_ARITH) && (flags & (PCS_FLAG_CUTOFF | PCS_FLAG_DROP_INVALID | PCS_KFLAG_CROP_BOX)) != 0;
 }
+inline bool has_box(const pcs_ctx* c) { return (c->flags & PCS_KFLAG_CROP_BOX) != 0; }
 inline bool scalar_arith(const pcs_ctx* c) { return (c->flags & PCS_FLAG_SCALAR_ARITH) != 0; }
 inline bool scalar_cut(const pcs_ctx* c) { return scalar_arith(c) && (c->flags & PCS_FLAG_CUTOFF) != 0; }
 
@@ -134,6 +143,16 @@ inline bool scalar_cut(const pcs_ctx* c) { return scalar_arith(c) && (c->flags &
             return pcs_host::fail((c), PCS_ERR_UNSUPPORTED, "%s is not available on a context created with "               \
                                   "PCS_FLAG_SCALAR_ARITH: the reference's default arithmetic covers the a1 / a2 twins and " \
                                   "pcs_process_frames, pcs_process_frames_device, pcs_submit_frames / pcs_collect_frames", name); \
+    } while (0)
+
+// The calls that cannot honour a crop box refuse while one is set, before anything is launched or written: a producer's tile counts
+// cannot know the world predicate (pcs_process_frames_device_counted), and the a1 / a2 twins are signature twins of reference functions
+// that have no such argument.
+#define PCS_NO_CROP_BOX(c, name)                                                                                            \
+    do {                                                                                                                    \
+        if (pcs_host::has_box(c))                                                                                           \
+            return pcs_host::fail((c), PCS_ERR_UNSUPPORTED, "%s is not available while a crop box is set "                  \
+                                  "(pcs_set_crop_box_mm(ctx, NULL, NULL) clears it)", name);                                \
     } while (0)
 
 template <class T>

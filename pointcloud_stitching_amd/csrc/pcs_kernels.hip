@@ -21,6 +21,8 @@
 // off — packed FP32 measured 1-2 % slower on the HBM-bound kernels); pcs_kernels_voxel.hip is pcs_kernels_voxel.o (the raster /
 // payload voxel readers, SLP on; the reasons are at its top). What both share, bit-exactness rules included: pcs_kernels_common.h.
 
+#include <algorithm>
+
 #include "pcs_kernels_common.h"
 
 #ifndef EMIT_WAVES
@@ -1364,6 +1366,322 @@ void pcs_pack_scalar_cut_kernel(const StreamParams* __restrict__ params, int str
     store_staged(stage, head, pts * PCS_POINT_BYTES, gdst);
 }
 
+// ---- crop box: pcs_set_crop_box_mm ------------------------------------------------------------------
+// A world-frame box on the record's three shorts (CropBox, pcs_kernels_common.h), ANDed with whatever the context's flags gate. Kernels of
+// their own, so that every other kernel keeps its name and its code. Always count + scan + emit (the scan kernels are the existing ones):
+//   count  deprojects (the Z16-only shortcut of count_tiles cannot decide a world predicate), runs the three world_mm chains and the
+//          conversion through world_ints — no colour arithmetic (dead without the gather), no gather, no store;
+//   emit   generic_tile's order turned round: the records first (their colour gathers in flight), then the keep mask from them, then
+//          the wave scan; the same two barriers.
+// Both passes take a point's coordinates from world_ints under the same Cvt ladder: FastCvt<true> with its redo() into ExactCvt, the
+// ladder of every policy the emit launch selects (crop_tile asserts it). The
+// emit tile's redo is wider — a colour coordinate or the raster's last dword can send a lane through ExactCvt as well — but a lane
+// redone for those alone converts world values below 2^31, where the two conversions agree in the low 16 bits the box reads (and
+// NaN gives 0 / INT_MIN: the same 16 bits); a world value from 2^31 up sends the lane through ExactCvt in both passes.
+__device__ __forceinline__ uint32_t crop_bits8(const StreamParams& P, const PointIn (&p)[8], const CropBox& box)
+{
+    auto bits = [&](auto& cv) {
+        uint32_t m = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            float f[3];
+            uint32_t w[3];
+            world_ints(P, p[k], cv, f, w);
+            cv.note(f[0], f[1], f[2], 0.0f, 0.0f);
+            m |= (uint32_t)box_keeps(box, perm(w[1], w[0], kLoLo), w[2]) << k;
+        }
+        return m;
+    };
+    FastCvt<true> fast;
+    uint32_t m = bits(fast);
+    if (__builtin_expect(fast.redo(), 0)) { ExactCvt exact; m = bits(exact); }
+    return m;
+}
+
+__device__ __forceinline__ void crop_count_tile(const StreamParams& P, const uint16_t* __restrict__ dp, uint32_t flags, const CropBox& box,
+                                                uint32_t* __restrict__ tile_counts, uint32_t* wsum)
+{
+    const uint32_t n = P.n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    const uint32_t i0 = tile0 + threadIdx.x * kPointsPerLane;
+    DepthSource<true, false> src{dp};          // (X, Y, Z depend on the depth-side distortion alone; u, v are dead here)
+    PointIn p[8];
+    src.load8(P, i0, n, p);
+    const uint32_t keep = keep_mask8(p, i0, n, flags) & crop_bits8(P, p, box);
+    const uint32_t w = wave_sum(__popc(keep));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_counts[P.tile_base + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_fused_count_crop_kernel(const StreamParams* __restrict__ params, int stream0, FramePtrs fp, uint32_t flags, CropBox box,
+                                 uint32_t* __restrict__ tile_counts)
+{
+    __shared__ uint32_t wsum[4];
+    const int s = blockIdx.y;
+    crop_count_tile(params[stream0 + s], fp.depth[s], flags, box, tile_counts, wsum);
+}
+
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_fused_count_crop_batch_kernel(const StreamParams* __restrict__ params, BatchPtrs bp, uint32_t flags, CropBox box,
+                                       uint32_t* __restrict__ tile_counts, uint32_t total_tiles)
+{
+    __shared__ uint32_t wsum[4];
+    const int s = blockIdx.y;
+    crop_count_tile(params[s], bp.depth[blockIdx.z * gridDim.y + s], flags, box,
+                              tile_counts + (size_t)blockIdx.z * total_tiles, wsum);
+}
+
+// make_record's -m form over world_ints: the record the boxed emit tile writes, its coordinates from the very function the count
+// pass calls. (make_record itself is left as it is: routing it through world_ints moved the code of 53 existing kernels.)
+template <class Cvt>
+__device__ __forceinline__ Record make_record_box(const StreamParams& P, const uint8_t* __restrict__ color, const PointIn& p, Cvt& cv)
+{
+    float a[3], xf, yf;
+    uint32_t q[3];
+    world_ints(P, p, cv, a, q);
+    color_coords(P, p.u, p.v, xf, yf);
+    cv.note(a[0], a[1], a[2], xf, yf);
+    const uint32_t w = color_fetch(P, color, cv.pixel(xf, P.cW - 1, P.c_wm1_f), cv.pixel(yf, P.cH - 1, P.c_hm1_f), cv);
+    Record r;
+    r.xy = perm(q[1], q[0], kLoLo);
+    r.zc = perm(w, q[2], kLoLo);
+    r.b  = __builtin_amdgcn_ubfe(w, 16, 8);
+    return r;
+}
+
+// generic_tile with the box: PRED always, the keep mask after the records.
+template <class Src, bool DS1>
+__device__ __forceinline__ void crop_tile(const StreamParams& P, const Src& src, const uint8_t* __restrict__ color,
+                                          uint32_t tile0, uint32_t n, uint32_t flags, const CropBox& box, uint32_t ds,
+                                          uint32_t g0, uint32_t out_first, uint8_t* __restrict__ payload_bytes,
+                                          uint8_t* stage, uint32_t* wsum)
+{
+    if (DS1) ds = 1u;
+    const uint32_t i0 = tile0 + threadIdx.x * kPointsPerLane;
+    PointIn p[8];
+    src.load8(P, i0, n, p);
+    uint32_t keep = keep_mask8(p, i0, n, flags);      // what the flags gate (the -c reversal included): the box bit is ANDed below
+
+    Record rec[8];
+    auto fill = [&](auto& cv) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) rec[k] = make_record_box(P, color, p[k], cv);
+    };
+    static_assert(Src::Math::kCvtMode == 1, "the count pass (crop_bits8) runs this ladder and no other");
+    FastCvt<true> fast;
+    fill(fast);
+    if (__builtin_expect(fast.redo(), 0)) { ExactCvt exact; fill(exact); }
+    uint32_t in_box = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) in_box |= (uint32_t)box_keeps(box, rec[k].xy, rec[k].zc) << k;
+    keep &= in_box;
+    uint32_t wave_total;
+    const uint32_t ex = wave_exclusive_scan(__popc(keep), wave_total);
+    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = wave_total;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6;
+    uint32_t before = 0;
+    for (int w = 0; w < wave; w++) before += wsum[w];
+    const uint32_t tile_kept = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const uint32_t lane_first = before + ex;
+
+    const uint32_t q_lo = out_first + (DS1 ? g0 : (g0 + ds - 1) / ds);
+    const uint32_t q_hi = out_first + (DS1 ? g0 + tile_kept : (g0 + tile_kept + ds - 1) / ds);
+    uint8_t* gdst = payload_bytes + (size_t)q_lo * PCS_POINT_BYTES;
+    const uint32_t head = (uint32_t)((uintptr_t)gdst & 15u);
+    uint32_t g = g0 + lane_first;
+    uint32_t gq = DS1 ? g : g / ds, gr = DS1 ? 0u : g - gq * ds;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if ((keep >> k) & 1u) {
+            if (gr == 0u) stage_record(stage, head + (out_first + gq - q_lo) * PCS_POINT_BYTES, rec[k]);
+            if (DS1) gq++;
+            else if (++gr == ds) { gr = 0u; gq++; }
+        }
+    }
+    __syncthreads();
+    store_staged(stage, head, (q_hi - q_lo) * PCS_POINT_BYTES, gdst);
+}
+
+#ifndef CROP_EMIT_WAVES
+#define CROP_EMIT_WAVES EMIT_WAVES    // DESIGN.md section 8 has the VGPR / scratch figures of every instantiation
+#endif
+template <bool DS1, class Mth>
+__global__ __launch_bounds__(kBlockThreads, CROP_EMIT_WAVES)
+void pcs_fused_emit_crop_kernel(const StreamParams* __restrict__ params, int stream0, FramePtrs fp, uint32_t flags, CropBox box,
+                                uint32_t ds, const uint32_t* __restrict__ tile_prefix, const uint32_t* __restrict__ stream_kept,
+                                uint8_t* __restrict__ payload_bytes, int32_t* __restrict__ total_out, int n_total_streams)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    __shared__ uint32_t wsum[4];
+    const int s = blockIdx.y;
+    if (total_out && blockIdx.x == 0 && stream0 + s == 0 && threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (int e = 0; e < n_total_streams; e++) tot += DS1 ? stream_kept[e] : (stream_kept[e] + ds - 1) / ds;
+        *total_out = (int32_t)tot;
+    }
+    const StreamParams& P = params[stream0 + s];
+    request_constants<true, Mth::kIdentR>(P, fp.depth[s], fp.color[s], payload_bytes);
+    const uint32_t n = P.n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    DepthSource<true, true, Mth> src{fp.depth[s]};
+    const uint32_t g0 = tile_prefix[P.tile_base + blockIdx.x];
+    uint32_t out_first = 0;
+    for (int e = 0; e < stream0 + s; e++) out_first += DS1 ? stream_kept[e] : (stream_kept[e] + ds - 1) / ds;
+    crop_tile<DepthSource<true, true, Mth>, DS1>(P, src, fp.color[s], tile0, n, flags, box, ds, g0, out_first, payload_bytes, stage, wsum);
+}
+
+template <class Mth>
+__global__ __launch_bounds__(kBlockThreads, CROP_EMIT_WAVES)
+void pcs_fused_emit_crop_batch_kernel(const StreamParams* __restrict__ params, BatchPtrs bp, uint32_t flags, CropBox box,
+                                      const uint32_t* __restrict__ tile_prefix, const uint32_t* __restrict__ stream_kept,
+                                      uint32_t total_tiles, BatchCounts bc)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    __shared__ uint32_t wsum[4];
+    const int s = blockIdx.y, S = gridDim.y, z = blockIdx.z;
+    const uint32_t* __restrict__ kept = stream_kept + z * S;
+    if (blockIdx.x == 0 && s == 0 && threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (int e = 0; e < S; e++) tot += kept[e];
+        bc.counts[z][S] = (int32_t)tot;
+    }
+    const StreamParams& P = params[s];
+    const uint32_t n = P.n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    DepthSource<true, true, Mth> src{bp.depth[z * S + s]};
+    const uint32_t g0 = tile_prefix[(size_t)z * total_tiles + P.tile_base + blockIdx.x];
+    uint32_t out_first = 0;
+    for (int e = 0; e < s; e++) out_first += kept[e];
+    crop_tile<DepthSource<true, true, Mth>, true>(P, src, bp.color[z * S + s], tile0, n, flags, box, 1u, g0, out_first, bp.payload[z],
+                                                  stage, wsum);
+}
+
+// ---- centre side: pcs_crop_payloads_device ----------------------------------------------------------
+// The same box over payloads that are already packed (edge servers that cannot crop): count, the scan kernel above, emit. A tile is
+// kTilePoints input records of one camera; its bytes come into LDS at the input's 16-byte phase (load_staged: never a byte outside
+// the camera's payload), lane l takes records 8 l .. 8 l + 7 (ascending order per lane, as in generic_tile), and the kept ones are
+// parked at the OUTPUT's phase and leave through store_staged. `tab` is a table of the scan kernel's type of which only n_points and
+// tile_base are filled (pcs_crop_table_kernel): entry i = camera i.
+struct CropCams { const int16_t* in[kLaunchStreams]; };
+struct CropTable { uint32_t n_points[PCS_MAX_STREAMS]; uint32_t tile_base[PCS_MAX_STREAMS]; };
+
+__global__ __launch_bounds__(64)
+void pcs_crop_table_kernel(StreamParams* __restrict__ tab, CropTable t, int n)
+{
+    if ((int)threadIdx.x < n) { tab[threadIdx.x].n_points = t.n_points[threadIdx.x]; tab[threadIdx.x].tile_base = t.tile_base[threadIdx.x]; }
+}
+
+// unstage_record, as a copy of this section's own: with the re-transform kernel's function called from here as well, hipcc swapped the
+// operands of eight adds in THAT kernel, and every existing kernel keeps its code byte for byte (tools/isa_compare.py).
+__device__ __forceinline__ Record unstage_record_crop(const uint8_t* lds, uint32_t off)
+{
+    const bool odd = (off & 2u) != 0u;
+    const uint32_t h_off = odd ? off : off + 8u;
+    const uint32_t a_off = odd ? off + 2u : off;
+    const uint32_t h = *reinterpret_cast<const uint16_t*>(lds + h_off);
+    const uint32_t a = *reinterpret_cast<const uint32_t*>(lds + a_off);
+    const uint32_t b = *reinterpret_cast<const uint32_t*>(lds + a_off + 4u);
+    Record r;
+    r.xy = odd ? perm(a, h, kLoLo) : a;
+    r.zc = odd ? perm(b, a, kHiLo) : b;
+    r.b = odd ? (b >> 16) : h;
+    return r;
+}
+// The tile's records into registers; returns the lane's keep mask. (Ends behind a barrier: everybody holds its records.)
+__device__ __forceinline__ uint32_t crop_load_tile(const int16_t* __restrict__ in, uint32_t tile0, uint32_t n, const CropBox& box,
+                                                   uint8_t* stage, Record (&rec)[8])
+{
+    const uint32_t pts = min(kTilePoints, n - tile0);
+    const uint8_t* gsrc = reinterpret_cast<const uint8_t*>(in) + (size_t)tile0 * PCS_POINT_BYTES;
+    const uint32_t ihead = (uint32_t)((uintptr_t)gsrc & 15u);
+    load_staged(stage, ihead, pts * PCS_POINT_BYTES, gsrc);
+    __syncthreads();
+    uint32_t keep = 0;
+#pragma unroll
+    for (int k = 0; k < kPointsPerLane; k++) {
+        const uint32_t j = threadIdx.x * kPointsPerLane + (uint32_t)k;
+        rec[k] = Record{0u, 0u, 0u};
+        if (j < pts) {
+            rec[k] = unstage_record_crop(stage, ihead + j * PCS_POINT_BYTES);
+            keep |= (uint32_t)box_keeps(box, rec[k].xy, rec[k].zc) << k;
+        }
+    }
+    __syncthreads();
+    return keep;
+}
+
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_crop_count_kernel(const StreamParams* __restrict__ tab, int cam0, CropCams cc, CropBox box, uint32_t* __restrict__ tile_counts)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    __shared__ uint32_t wsum[4];
+    const int s = blockIdx.y;
+    const uint32_t n = tab[cam0 + s].n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    Record rec[8];
+    const uint32_t keep = crop_load_tile(cc.in[s], tile0, n, box, stage, rec);
+    const uint32_t w = wave_sum(__popc(keep));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_counts[tab[cam0 + s].tile_base + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+template <bool DS1>
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_crop_emit_kernel(const StreamParams* __restrict__ tab, int cam0, CropCams cc, CropBox box, uint32_t ds,
+                          const uint32_t* __restrict__ tile_prefix, const uint32_t* __restrict__ cam_kept,
+                          uint8_t* __restrict__ payload_bytes, int32_t* __restrict__ total_out, int n_cams)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
+    __shared__ uint32_t wsum[4];
+    if (DS1) ds = 1u;
+    const int s = blockIdx.y;
+    if (blockIdx.x == 0 && cam0 + s == 0 && threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (int e = 0; e < n_cams; e++) tot += (cam_kept[e] + ds - 1) / ds;
+        *total_out = (int32_t)tot;
+    }
+    const uint32_t n = tab[cam0 + s].n_points;
+    const uint32_t tile0 = blockIdx.x * kTilePoints;
+    if (tile0 >= n) return;
+    Record rec[8];
+    const uint32_t keep = crop_load_tile(cc.in[s], tile0, n, box, stage, rec);
+    uint32_t wave_total;
+    const uint32_t ex = wave_exclusive_scan(__popc(keep), wave_total);
+    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = wave_total;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6;
+    uint32_t before = 0;
+    for (int w = 0; w < wave; w++) before += wsum[w];
+    const uint32_t tile_kept = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const uint32_t g0 = tile_prefix[tab[cam0 + s].tile_base + blockIdx.x];
+    uint32_t out_first = 0;
+    for (int e = 0; e < cam0 + s; e++) out_first += (cam_kept[e] + ds - 1) / ds;
+
+    const uint32_t q_lo = out_first + (g0 + ds - 1) / ds;
+    const uint32_t q_hi = out_first + (g0 + tile_kept + ds - 1) / ds;
+    uint8_t* gdst = payload_bytes + (size_t)q_lo * PCS_POINT_BYTES;
+    const uint32_t head = (uint32_t)((uintptr_t)gdst & 15u);
+    const uint32_t g = g0 + before + ex;
+    uint32_t gq = g / ds, gr = g - gq * ds;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if ((keep >> k) & 1u) {
+            if (gr == 0u) stage_record(stage, head + (out_first + gq - q_lo) * PCS_POINT_BYTES, rec[k]);
+            if (++gr == ds) { gr = 0u; gq++; }
+        }
+    }
+    __syncthreads();
+    store_staged(stage, head, (q_hi - q_lo) * PCS_POINT_BYTES, gdst);
+}
+
 // Certificate of CertRowConst for one stream: row r's colour row through the IEEE chain for EVERY Z16 value 1 .. 65 535 (one workgroup
 // per raster row). crow[r] = the row for d = 1; *bad counts the (row, depth) pairs that give another one. The chain is the product's
 // own code (deproject_pixel + color_coords + the exact conversion), so the sweep cannot disagree with what the kernels would compute.
@@ -1729,6 +2047,94 @@ hipError_t launch_stitch(const int16_t* d_src, uint32_t src_points, int downsamp
     if (out_points == 0) return hipSuccess;
     hipLaunchKernelGGL(pcs_stitch_kernel, tile_grid(out_points, 1), dim3(kBlockThreads), 0, st,
                        reinterpret_cast<const uint16_t*>(d_src), out_points, ds, reinterpret_cast<uint8_t*>(d_dst));
+    return hipGetLastError();
+}
+
+// ---- crop box ----
+namespace {
+inline CropBox crop_box(const CropBoxArg& b) { return CropBox{b.w[0], b.w[1], b.w[2]}; }
+}  // namespace
+
+hipError_t launch_fused_count_crop(const StreamParams* d_params, int stream0, int n_launch, uint32_t max_points, uint32_t flags,
+                                   const CropBoxArg& box, const FramePtrs& fp, uint32_t* d_tile_counts, hipStream_t st)
+{
+    if (n_launch <= 0 || max_points == 0) return hipSuccess;
+    hipLaunchKernelGGL(pcs_fused_count_crop_kernel, tile_grid(max_points, n_launch), dim3(kBlockThreads), 0, st, d_params, stream0, fp,
+                       flags, crop_box(box), d_tile_counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_fused_emit_crop(const StreamParams* d_params, int stream0, int n_launch, uint32_t max_points, uint32_t flags,
+                                  const CropBoxArg& box, int downsample, MathSel math, const FramePtrs& fp, const uint32_t* d_tile_prefix,
+                                  const uint32_t* d_stream_kept, int16_t* d_payload, int32_t* d_total_out, int n_total_streams,
+                                  hipStream_t st)
+{
+    if (n_launch <= 0 || max_points == 0) return hipSuccess;
+    const dim3 grid = tile_grid(max_points, n_launch);
+    uint8_t* out = reinterpret_cast<uint8_t*>(d_payload);
+#define L(D1, M) hipLaunchKernelGGL((pcs_fused_emit_crop_kernel<D1, M>), grid, dim3(kBlockThreads), 0, st, d_params, stream0, fp, flags, \
+                                    crop_box(box), (uint32_t)downsample, d_tile_prefix, d_stream_kept, out, d_total_out, n_total_streams)
+#define LM(M) do { if (downsample == 1) L(true, M); else L(false, M); } while (0)
+    const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
+    if (math == MathSel::Ieee) LM(IeeeMath); else if (ident) LM(CertMath<true>); else LM(CertMath<false>);
+#undef LM
+#undef L
+    return hipGetLastError();
+}
+
+hipError_t launch_crop_batch(const StreamParams* d_params, int n_streams, int n_sets, uint32_t max_points, uint32_t total_tiles,
+                             uint32_t flags, const CropBoxArg& box, MathSel math, const BatchPtrs& bp, const BatchCounts& bc,
+                             uint32_t* d_tile_counts, uint32_t* d_tile_prefix, uint32_t* d_stream_kept, hipStream_t st)
+{
+    if (n_streams <= 0 || n_sets <= 0 || max_points == 0) return hipSuccess;
+    if (n_streams * n_sets > kBatchEntries || n_sets > kBatchSets) return hipErrorInvalidValue;
+    const uint32_t tiles = (max_points + kTilePoints - 1) / kTilePoints;
+    const dim3 grid(tiles, (unsigned)n_streams, (unsigned)n_sets);
+    hipLaunchKernelGGL(pcs_fused_count_crop_batch_kernel, grid, dim3(kBlockThreads), 0, st, d_params, bp, flags, crop_box(box),
+                       d_tile_counts, total_tiles);
+    hipLaunchKernelGGL(pcs_scan_batch_kernel, dim3((unsigned)n_streams, (unsigned)n_sets), dim3(1024), 0, st, d_params,
+                       d_tile_counts, d_tile_prefix, d_stream_kept, total_tiles, bc);
+#define L(M) hipLaunchKernelGGL((pcs_fused_emit_crop_batch_kernel<M>), grid, dim3(kBlockThreads), 0, st, d_params, bp, flags, crop_box(box), \
+                                d_tile_prefix, d_stream_kept, total_tiles, bc)
+    const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
+    if (math == MathSel::Ieee) L(IeeeMath); else if (ident) L(CertMath<true>); else L(CertMath<false>);
+#undef L
+    return hipGetLastError();
+}
+
+hipError_t launch_crop_payloads(StreamParams* d_tab, const int16_t* const* d_in, const uint32_t* n_points, int n_cams,
+                                const CropBoxArg& box, int downsample, uint32_t* d_tile_counts, uint32_t* d_tile_prefix,
+                                uint32_t* d_cam_kept, int16_t* d_out, int32_t* d_counts, hipStream_t st)
+{
+    if (n_cams <= 0 || n_cams > PCS_MAX_STREAMS) return hipErrorInvalidValue;
+    CropTable t{};
+    uint32_t tb = 0;
+    for (int i = 0; i < n_cams; i++) { t.n_points[i] = n_points[i]; t.tile_base[i] = tb; tb += (n_points[i] + kTilePoints - 1) / kTilePoints; }
+    hipLaunchKernelGGL(pcs_crop_table_kernel, dim3(1), dim3(64), 0, st, d_tab, t, n_cams);
+    for (int c0 = 0; c0 < n_cams; c0 += kLaunchStreams) {
+        const int nl = std::min(kLaunchStreams, n_cams - c0);
+        CropCams cc{};
+        uint32_t mp = 0;
+        for (int k = 0; k < nl; k++) { cc.in[k] = d_in[c0 + k]; mp = std::max(mp, n_points[c0 + k]); }
+        if (mp) hipLaunchKernelGGL(pcs_crop_count_kernel, tile_grid(mp, nl), dim3(kBlockThreads), 0, st, d_tab, c0, cc, crop_box(box), d_tile_counts);
+    }
+    hipLaunchKernelGGL(pcs_scan_kernel, dim3((unsigned)n_cams), dim3(1024), 0, st, d_tab, 0, n_cams, 0u, (uint32_t)downsample,
+                       d_tile_counts, d_tile_prefix, d_cam_kept, d_counts, (uint32_t*)nullptr);
+    // the grand total rides on the first workgroup of camera 0's launch
+    for (int c0 = 0; c0 < n_cams; c0 += kLaunchStreams) {
+        const int nl = std::min(kLaunchStreams, n_cams - c0);
+        CropCams cc{};
+        uint32_t mp = 0;
+        for (int k = 0; k < nl; k++) { cc.in[k] = d_in[c0 + k]; mp = std::max(mp, n_points[c0 + k]); }
+        if (c0 == 0 && mp == 0) mp = 1;         // (one workgroup per camera that writes the total and returns)
+        if (!mp) continue;
+        if (downsample == 1)
+            hipLaunchKernelGGL((pcs_crop_emit_kernel<true>), tile_grid(mp, nl), dim3(kBlockThreads), 0, st, d_tab, c0, cc, crop_box(box), 1u,
+                               d_tile_prefix, d_cam_kept, reinterpret_cast<uint8_t*>(d_out), d_counts + n_cams, n_cams);
+        else
+            hipLaunchKernelGGL((pcs_crop_emit_kernel<false>), tile_grid(mp, nl), dim3(kBlockThreads), 0, st, d_tab, c0, cc, crop_box(box),
+                               (uint32_t)downsample, d_tile_prefix, d_cam_kept, reinterpret_cast<uint8_t*>(d_out), d_counts + n_cams, n_cams);
+    }
     return hipGetLastError();
 }
 

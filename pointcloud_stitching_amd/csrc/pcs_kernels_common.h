@@ -465,6 +465,32 @@ __device__ __forceinline__ uint32_t keep_mask8(const PointIn (&p)[8], uint32_t i
     return keep_from_bits(rng, nz, i0, n, flags);
 }
 
+// ---- crop box (pcs_set_crop_box_mm) -----------------------------------------------------------------
+// The world-frame box on the RECORD: a point is kept iff each of its three shorts s_a (the low 16 bits of the converted coordinate, read
+// as signed: after the int16 wrap) lies in [lo_a, hi_a]. The box reaches a kernel as three dwords in its arguments (SGPRs), never
+// through StreamParams:  xy = lo_x | lo_y << 16,  zz = lo_z | span_z << 16,  sp = span_x | span_y << 16,  span_a = hi_a - lo_a (0 .. 65535).
+// Per axis ((s - lo) & 0xFFFF) <= span in 16-bit modular arithmetic is lo <= s <= hi for signed shorts with lo <= hi.
+struct CropBox { uint32_t xy, zz, sp; };
+__device__ __forceinline__ bool box_keeps(const CropBox& b, uint32_t rxy, uint32_t rzc)
+{
+    const uint32_t dx = (rxy - b.xy) & 0xFFFFu;                      // a borrow out of the low half cannot reach it
+    const uint32_t dy = ((rxy >> 16) - (b.xy >> 16)) & 0xFFFFu;
+    const uint32_t dz = (rzc - b.zz) & 0xFFFFu;
+    return dx <= (b.sp & 0xFFFFu) && dy <= (b.sp >> 16) && dz <= (b.zz >> 16);
+}
+
+// The three converted world coordinates of a point under -m arithmetic (world_mm and the Cvt policy's conversion): what make_record
+// packs into the record's first three shorts. The boxed count pass and the boxed emit tile both call this and nothing else for them,
+// under the same Cvt ladder, so the two passes agree on every bit. `noted`: the floats the policy's running maximum must be told.
+template <class Cvt>
+__device__ __forceinline__ void world_ints(const StreamParams& P, const PointIn& p, const Cvt& cv, float (&noted)[3], uint32_t (&w)[3])
+{
+    noted[0] = world_mm(P.M + 0, p.X, p.Y, p.Z);
+    noted[1] = world_mm(P.M + 4, p.X, p.Y, p.Z);
+    noted[2] = world_mm(P.M + 8, p.X, p.Y, p.Z);
+    w[0] = (uint32_t)cv.cvt(noted[0]); w[1] = (uint32_t)cv.cvt(noted[1]); w[2] = (uint32_t)cv.cvt(noted[2]);
+}
+
 // Wavefront-wide inclusive prefix sum (64 lanes, all active) by DPP: four row_shr steps scan each row of 16 lanes,
 // row_bcast:15 / row_bcast:31 carry the row totals across (the gfx9 sequence). No lane-index registers, no LDS
 // crossbar (ds_bpermute, which __shfl_up compiles to) — and nothing loop-invariant for the compiler to hoist out of

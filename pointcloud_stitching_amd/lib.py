@@ -28,6 +28,8 @@ SYMBOLS = [
     ("pcs_strerror", C.c_char_p, [C.c_int]),
     ("pcs_last_error", C.c_char_p, [_VP]),
     ("pcs_set_cam_to_world", C.c_int, [_VP, C.c_int, _P(C.c_float)]),
+    ("pcs_set_crop_box_mm", C.c_int, [_VP, _P(C.c_int16), _P(C.c_int16)]),
+    ("pcs_get_crop_box_mm", C.c_int, [_VP, _P(C.c_int16), _P(C.c_int16)]),
     ("pcs_stream_points", C.c_int, [_VP, C.c_int]),
     ("pcs_stream_math", C.c_int, [_VP, C.c_int]),
     ("pcs_stream_color_row_const", C.c_int, [_VP, C.c_int]),
@@ -49,6 +51,7 @@ SYMBOLS = [
     ("pcs_collect_frames", C.c_int, [_VP, C.c_int, _VP, C.c_size_t, C.c_int, _P(C.c_int), _P(C.c_int)]),
     ("pcs_deproject", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("pcs_stitch_device", C.c_int, [_VP, _P(_VP), _P(C.c_int), C.c_int, C.c_int, _VP, C.c_size_t, _P(C.c_int)]),
+    ("pcs_crop_payloads_device", C.c_int, [_VP, _P(_VP), _P(C.c_int), C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     ("pcs_transform_payloads_device", C.c_int, [_VP, C.c_int, _P(PayloadDesc), C.c_int, _VP, C.c_size_t, _P(C.c_int), _P(C.c_int)]),
     ("pcs_set_voxel_tail", C.c_int, [_VP, C.c_int]),
     ("pcs_voxel_tail_reruns", C.c_int, [_VP]),
