@@ -72,32 +72,102 @@ def cutoff_keep_np(V, compat=True):
     return ok
 
 
-def deproject_np(sc, depth, half_pixel=False):
-    f32 = np.float32
+MISREADINGS = ("swap_k2_k3", "opencv_order", "no_factor_2", "other_axis", "colour_no_prescale", "colour_r2_after",
+               "depth_modified_form", "radial_division", "depth_after_z")
+
+
+def distortion_active(intr):
+    """A model with all-zero coefficients is inactive (-0.0 is zero, a NaN is not)."""
+    return int(intr.model) != 0 and any(np.float32(k) != np.float32(0) for k in intr.coeffs)
+
+
+def _deproject(T, sc, depth, half_pixel, misreading):
+    """DESIGN.md section 3 in the number type T, every operation one numpy operation on T, in the stated association. With T = float32
+    each of them is rounded once: the exact emulation of a build with no contraction. With T = float64 it is the plain model.
+    `misreading` (one of MISREADINGS, test use only) swaps in one plausible wrong reading of the published formula."""
+    assert misreading is None or misreading in MISREADINGS
+    mis = lambda name: misreading == name
     di, ci = sc.depth, sc.color
     W, H = di.width, di.height
+    one, two = T(1), T(2)
+
+    def coeffs(intr):
+        k = [T(np.float32(c)) for c in intr.coeffs]
+        if mis("swap_k2_k3"):
+            k[2], k[3] = k[3], k[2]
+        if mis("opencv_order"):              # read as k1 k2 k3 p1 p2
+            k = [k[0], k[1], k[3], k[4], k[2]]
+        return k
+
+    def radial(k, r2):                       # 1 + k0*r2 + (k1*r2)*r2 + ((k4*r2)*r2)*r2, left to right
+        return ((one + k[0] * r2) + (k[1] * r2) * r2) + ((k[4] * r2) * r2) * r2
+
+    def tangential(a, kA, kB, x, y, r2, axis, other):        # a + ((2*kA)*x)*y + kB*(r2 + (2*axis)*axis)
+        if mis("other_axis"):
+            axis = other
+        first = (kA * x) * y if mis("no_factor_2") else ((two * kA) * x) * y
+        return (a + first) + kB * (r2 + (two * axis) * axis)
+
+    def scaled(a, f):
+        return a / f if mis("radial_division") else a * f
+
+    def modified_form(k, x, y, r2_after=False):              # the colour branch: scale by f first, keep the r2 of the unscaled point
+        r2 = x * x + y * y
+        f = radial(k, r2)
+        x, y = scaled(x, f), scaled(y, f)
+        if r2_after:
+            r2 = x * x + y * y
+        return tangential(x, k[2], k[3], x, y, r2, x, y), tangential(y, k[3], k[2], x, y, r2, y, x)
+
+    def inverse_form(k, x, y):                               # the depth branch: tangential terms of the unscaled point
+        r2 = x * x + y * y
+        f = radial(k, r2)
+        return (tangential(scaled(x, f), k[2], k[3], x, y, r2, x, y),
+                tangential(scaled(y, f), k[3], k[2], x, y, r2, y, x))
+
     d = np.asarray(depth, np.uint16).reshape(H, W)
     with np.errstate(all="ignore"):
-        z = (f32(sc.depth_scale) * d.astype(f32)).astype(f32)
-        mx = ((np.arange(W, dtype=f32) - f32(di.ppx)) / f32(di.fx)).astype(f32)[None, :]
-        my = ((np.arange(H, dtype=f32) - f32(di.ppy)) / f32(di.fy)).astype(f32)[:, None]
-        X = (z * mx).astype(f32); Y = (z * my).astype(f32); Z = z
-        R = [f32(x) for x in sc.depth_to_color.rotation]; t = [f32(x) for x in sc.depth_to_color.translation]
+        z = T(np.float32(sc.depth_scale)) * d.astype(T)
+        mx = np.broadcast_to(((np.arange(W).astype(T) - T(di.ppx)) / T(di.fx))[None, :], (H, W))
+        my = np.broadcast_to(((np.arange(H).astype(T) - T(di.ppy)) / T(di.fy))[:, None], (H, W))
+        ddist = distortion_active(di)
+        if ddist and not mis("depth_after_z"):
+            mx, my = (modified_form if mis("depth_modified_form") else inverse_form)(coeffs(di), mx, my)
+        X = z * mx; Y = z * my; Z = z
+        if ddist and mis("depth_after_z"):
+            X, Y = inverse_form(coeffs(di), X, Y)
+        R = [T(np.float32(x)) for x in sc.depth_to_color.rotation]; t = [T(np.float32(x)) for x in sc.depth_to_color.translation]
         def row(i):
-            return (((R[i] * X).astype(f32) + (R[i + 3] * Y).astype(f32)).astype(f32)
-                    + (R[i + 6] * Z).astype(f32)).astype(f32) + t[i]
-        P0, P1, P2 = row(0).astype(f32), row(1).astype(f32), row(2).astype(f32)
-        x = (P0 / P2).astype(f32); y = (P1 / P2).astype(f32)
-        px = ((x * f32(ci.fx)).astype(f32) + f32(ci.ppx)).astype(f32)
-        py = ((y * f32(ci.fy)).astype(f32) + f32(ci.ppy)).astype(f32)
+            return ((R[i] * X + R[i + 3] * Y) + R[i + 6] * Z) + t[i]
+        P0, P1, P2 = row(0), row(1), row(2)
+        x = P0 / P2; y = P1 / P2
+        if distortion_active(ci):
+            if mis("colour_no_prescale"):
+                x, y = inverse_form(coeffs(ci), x, y)
+            else:
+                x, y = modified_form(coeffs(ci), x, y, r2_after=mis("colour_r2_after"))
+        px = x * T(ci.fx) + T(ci.ppx)
+        py = y * T(ci.fy) + T(ci.ppy)
         if half_pixel:                      # PCS_FLAG_TEXCOORD_HALF_PIXEL: older librealsense pixel_to_texcoord
-            px = (px + f32(0.5)).astype(f32); py = (py + f32(0.5)).astype(f32)
-        u = (px / f32(ci.width)).astype(f32); v = (py / f32(ci.height)).astype(f32)
+            px = px + T(0.5); py = py + T(0.5)
+        u = px / T(ci.width); v = py / T(ci.height)
     valid = Z != 0
-    u = np.where(valid, u, f32(0)); v = np.where(valid, v, f32(0))
-    vtx = np.stack([X, Y, Z], -1).reshape(-1, 3).astype(f32)
-    tex = np.stack([u, v], -1).reshape(-1, 2).astype(f32)
+    u = np.where(valid, u, T(0)); v = np.where(valid, v, T(0))
+    vtx = np.stack([X, Y, Z], -1).reshape(-1, 3)
+    tex = np.stack([u, v], -1).reshape(-1, 2)
+    assert vtx.dtype == T and tex.dtype == T
     return vtx, tex
+
+
+def deproject_np(sc, depth, half_pixel=False, misreading=None):
+    """a5 in float32, one rounding per operation, with both Brown-Conrady branches: must equal the C oracle bit for bit."""
+    return _deproject(np.float32, sc, depth, half_pixel, misreading)
+
+
+def deproject_f64(sc, depth, half_pixel=False, misreading=None):
+    """The same mathematics on the same (float32-valued) parameters, everything in double: what the oracle's rounding is measured
+    against. Not a bit-exact anything."""
+    return _deproject(np.float64, sc, depth, half_pixel, misreading)
 
 
 def decode_payload_np(payload, downsample=1):
