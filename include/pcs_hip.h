@@ -272,6 +272,57 @@ int pcs_stream_tile_base(const pcs_ctx* ctx, int stream);
 int pcs_process_frames_device_counted(pcs_ctx* ctx, const uint16_t* const* d_depth, const uint8_t* const* d_color,
                                       const uint32_t* d_tile_kept, int16_t* d_payload, size_t payload_shorts, int32_t* d_counts);
 
+/* ---- depth pre-filter: temporal smoothing and hole filling, Z16 -> Z16 on the device --------------------------------------- *
+ * The two librealsense post-processing blocks the reference leaves as TODOs at its a1 seam (rs2_create_temporal_filter_block,
+ * rs2_create_hole_filling_filter_block: src/pcs-camera-optimized.cpp:682-684), as ONE stateful launch over every stream of the
+ * context, upstream of everything else: it writes Z16 rasters the stitch calls then read. The definition is this project's own
+ * (DESIGN.md §3 "Depth pre-filter": modelled on librealsense's published filters, parity with librealsense unpinned); the GPU
+ * output is held bit for bit to a numpy restatement of that text (tests/np_depth_filter.py).
+ *   temporal   per pixel, with c the input, p the stage's previous output and an 8-frame validity history: c and p valid and
+ *              |c - p| < delta -> alpha*c + (1-alpha)*p (fp32: two rounded products, one rounded sum, truncated, clamped to 65535);
+ *              c valid otherwise -> c; c == 0 -> p if p was valid in M of the last L frames (persistence 0..8: never, 8/8, 2/3,
+ *              2/4, 2/8, 1/2, 1/5, 1/8, always), else 0.
+ *   hole_fill  1 = fill from left: after the temporal stage a zero pixel takes the nearest non-zero pixel to its left in its
+ *              row; nothing crosses a row or a stream; filled values never enter the temporal state. librealsense's other two
+ *              modes are raster-order recurrences over two dimensions with no parallel form of the same output: values other
+ *              than 0 and 1 are PCS_ERR_UNSUPPORTED.
+ * pcs_set_depth_filter: validates (NaN, alpha <= 0 or > 1, delta outside 1..65535, persistence outside 0..8, both stages off:
+ *   PCS_ERR_INVALID_ARG; hole_fill not 0 / 1: PCS_ERR_UNSUPPORTED; the temporal parameters are checked whether or not that stage
+ *   is on, so fill the defaults in), synchronises the context's stream (pcs_set_cam_to_world's
+ *   rule), allocates 3 bytes per depth pixel per stream of state when temporal is on (failure: PCS_ERR_NOMEM, the context is left
+ *   without a filter) and zeroes it: setting a filter again resets the state. NULL clears the filter and frees the state, as
+ *   pcs_destroy does. Works on every context (PCS_FLAG_SCALAR_ARITH included: the filter sits upstream of the arithmetic).
+ * pcs_get_depth_filter: 1 and the configuration if a filter is set, 0 (out untouched) if not.
+ * pcs_reset_depth_filter: zeroes the state of every stream (a recording that loops, a scene cut). Asynchronous on the stream.
+ * pcs_filter_depth_device: asynchronous on the context's stream, one launch for all streams; EVERY call advances the state by one
+ *   frame. d_in[s] / d_out[s]: device pointers, 2-byte aligned, depth.width*depth.height uint16, row-major, tightly packed — what
+ *   pcs_process_frames_device asks of d_depth[s]; 16-byte aligned rasters whose width is a multiple of 8 take the wide accesses.
+ *   d_out[s] == d_in[s] (in place) is allowed; any other overlap, between or within streams, is the caller's error. Without a
+ *   filter: PCS_ERR_INVALID_ARG ("depth filter" in pcs_last_error).
+ *   d_tile_kept (optional, 4-byte aligned, pcs_stream_tile_base(ctx, n_streams) words): the call zeroes it on the stream and
+ *   writes the number of NON-ZERO OUTPUT pixels of every PCS_TILE_POINTS tile, in the layout pcs_process_frames_device_counted
+ *   takes — on a PCS_FLAG_DROP_INVALID context the next stitch then needs no count pass. With PCS_FLAG_CUTOFF or a crop box the
+ *   counts would need the deprojection: non-NULL is PCS_ERR_UNSUPPORTED there, nothing launched, nothing written. On a dense
+ *   context the counts are written and correct; the stitch ignores them. Measured (8 x 1280x720): the counts
+ *   cost this call 7.4 us (a memset launch and per-tile atomics), more than the 5.3 us count pass they spare the stitch: on one
+ *   device filter + counted stitch is no faster than filter + pcs_process_frames_device. The counts are for producers that must
+ *   not read the rasters twice.
+ * pcs_filter_depth: host pointers, synchronous: upload, pcs_filter_depth_device in place on the context's staging rasters,
+ *   download (in[s] == out[s] is fine). For the CLI and for tests; no zero-copy route.
+ * HBM traffic per pixel: 10 B with the temporal stage (2 in + 2 out + 4 state value + 2 history), 4 B for hole fill alone.      */
+typedef struct pcs_depth_filter_config {
+    int32_t temporal;      /* 0 off, 1 on */
+    float   alpha;         /* (0,1]; librealsense's default 0.4 */
+    int32_t delta;         /* 1..65535 Z16 units; default 20 */
+    int32_t persistence;   /* 0..8; default 3 */
+    int32_t hole_fill;     /* 0 off, 1 fill from left */
+} pcs_depth_filter_config;
+int pcs_set_depth_filter(pcs_ctx* ctx, const pcs_depth_filter_config* cfg);
+int pcs_get_depth_filter(const pcs_ctx* ctx, pcs_depth_filter_config* out);
+int pcs_reset_depth_filter(pcs_ctx* ctx);
+int pcs_filter_depth_device(pcs_ctx* ctx, const uint16_t* const* d_in, uint16_t* const* d_out, uint32_t* d_tile_kept);
+int pcs_filter_depth(pcs_ctx* ctx, const uint16_t* const* in, uint16_t* const* out);
+
 /* Throughput form: n_sets frame-sets of the SAME streams per call. d_depth / d_color hold n_sets * n_streams device
  * pointers, frame-set major (entry k*n_streams + s = stream s of frame-set k); d_payload[k] is frame-set k's payload
  * pointer (each with payload_shorts capacity), d_counts (optional) n_sets pointers as in pcs_process_frames_device.

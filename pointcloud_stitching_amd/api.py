@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (CloudDesc, Config, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (CloudDesc, Config, DepthFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -142,6 +142,55 @@ class PcsContext:
         cnts = (C.c_int * max(n, 1))(*cam_points)
         self._check(self._lib.pcs_crop_payloads_device(self._h, ptrs, cnts, n, int(downsample), d_stitched_payload or None,
                                                        stitched_shorts, d_counts or None))
+
+    # -- depth pre-filter ----------------------------------------------------------------------
+    def set_depth_filter(self, cfg=True, *, temporal: bool = True, alpha: float = 0.4, delta: int = 20, persistence: int = 3,
+                         hole_fill: int = 0) -> None:
+        """pcs_set_depth_filter: temporal smoothing and / or fill-from-left on the Z16 rasters, upstream of every other call (the
+        definition: DESIGN.md section 3). Keywords default to librealsense's; a DepthFilterConfig may be passed instead;
+        set_depth_filter(None) clears the filter and frees its state. Setting a filter (again) resets the state."""
+        if cfg is None:
+            self._check(self._lib.pcs_set_depth_filter(self._h, None))
+            return
+        if not isinstance(cfg, DepthFilterConfig):
+            cfg = DepthFilterConfig(int(temporal), float(alpha), int(delta), int(persistence), int(hole_fill))
+        self._check(self._lib.pcs_set_depth_filter(self._h, C.byref(cfg)))
+
+    def depth_filter(self) -> Optional[DepthFilterConfig]:
+        """The filter that is set (a DepthFilterConfig), or None."""
+        out = DepthFilterConfig()
+        rc = self._lib.pcs_get_depth_filter(self._h, C.byref(out))
+        if rc < 0:
+            self._check(rc)
+        return out if rc == 1 else None
+
+    def reset_depth_filter(self) -> None:
+        """Zero the temporal state of every stream (a recording looped, the scene was cut)."""
+        self._check(self._lib.pcs_reset_depth_filter(self._h))
+
+    def filter_depth_device(self, d_in: Sequence[int], d_out: Sequence[int], d_tile_kept: int = 0) -> None:
+        """pcs_filter_depth_device on device pointers (ints), asynchronous; d_out[s] may equal d_in[s]. Every call advances the
+        state by one frame. d_tile_kept (optional): stream_tile_base(n_streams) uint32 for process_frames_device_counted."""
+        if len(d_in) != self.n_streams or len(d_out) != self.n_streams:
+            raise ValueError("need one input and one output pointer per stream")
+        ip = (C.c_void_p * self.n_streams)(*d_in)
+        op = (C.c_void_p * self.n_streams)(*d_out)
+        self._check(self._lib.pcs_filter_depth_device(self._h, ip, op, d_tile_kept or None))
+
+    def filter_depth(self, depth: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """pcs_filter_depth: one frame-set of Z16 rasters through the filter (upload, launch, download); returns new arrays of
+        the inputs' shapes."""
+        if len(depth) != self.n_streams:
+            raise ValueError("need one depth raster per stream")
+        d = [np.ascontiguousarray(x, np.uint16) for x in depth]
+        for s in range(self.n_streams):
+            if d[s].size != self.streams[s].n_points:
+                raise ValueError(f"stream {s}: depth raster has {d[s].size} pixels, expected {self.streams[s].n_points}")
+        out = [np.empty_like(x) for x in d]
+        ip = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in d])
+        op = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in out])
+        self._check(self._lib.pcs_filter_depth(self._h, ip, op))
+        return out
 
     # -- a2 twin -----------------------------------------------------------------------------
     def copy_pointcloud_xyzrgb_to_buffer(self, stream: int, vertices, texcoords, color,

@@ -9,6 +9,8 @@
 //               -H (texture coordinates as older librealsense releases computed them: (pixel + 0.5) / size)
 //               -B <xlo,xhi,ylo,yhi,zlo,zhi> (crop box in millimetres, world frame, inclusive: an edge that crops before it sends;
 //                  pcs_set_crop_box_mm; needs -m)
+//               -F <temporal[=alpha:delta:persistence],holes[=left]> (depth pre-filter on the GPU: the two librealsense blocks the
+//                  reference leaves as TODOs in sendXYZRGBPointcloud, :682-684; pcs_set_depth_filter)
 //
 //   -f takes "synth:<W>x<H>" (deterministic synthetic frames; the reference's bags are LFS stubs and
 //   need librealsense), a .pcsraw dump (see pointcloud_stitching_amd/synthetic.py: write_pcsraw) or a
@@ -30,6 +32,7 @@
 
 #include "pcs_bag.h"
 #include "pcs_cropbox.h"
+#include "pcs_depthfilter.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
 
@@ -44,6 +47,8 @@ static const char* dump_path = nullptr;
 static const char* extrinsics_path = nullptr;
 static bool crop = false;
 static int16_t crop_lo[3], crop_hi[3];
+static bool depth_filter = false;
+static pcs_depth_filter_config filter_cfg;
 static int client_sock = 0, sockfd = 0;
 
 static void print_usage()
@@ -63,6 +68,8 @@ static void print_usage()
            "  -H        texture coordinates as older librealsense releases: (pixel + 0.5) / size\n"
            "  -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box: keep the points inside these inclusive bounds, millimetres in the WORLD frame\n"
            "            (after the camera-to-world transform; ANDed with -c / -i; -d keeps every n-th KEPT point); needs -m\n"
+           "  -F <temporal[=alpha:delta:persistence],holes[=left]>  depth pre-filter on the GPU, inside the timed region: temporal\n"
+           "            smoothing (defaults 0.4:20:3 = librealsense's) and / or hole filling from the left, e.g. -F temporal=0.4:20:3,holes\n"
            "  -M        hand the frames over in ordinary pageable memory, as librealsense owns them in the reference's timed region\n"
            "            (:291-293): uploads are staged then. Default: frames copied to page-locked rasters BEFORE the timer starts\n"
            "            (zero copy) - the printed times then belong to a capture pipeline that delivers page-locked frames\n\n");
@@ -71,7 +78,7 @@ static void print_usage()
 static void parseArgs(int argc, char** argv)
 {
     int c;
-    while ((c = getopt(argc, argv, "hf:vst:cmzg:n:d:iCr:o:p:e:PHMB:")) != -1) {
+    while ((c = getopt(argc, argv, "hf:vst:cmzg:n:d:iCr:o:p:e:PHMB:F:")) != -1) {
         switch (c) {
             case 'h': print_usage(); exit(0);
             case 'f': filename = optarg; break;
@@ -97,6 +104,12 @@ static void parseArgs(int argc, char** argv)
                 std::string why;
                 if (!pcs_cropbox::parse(optarg, crop_lo, crop_hi, why)) { std::cerr << "-B " << optarg << ": " << why << std::endl; exit(2); }
                 crop = true;
+                break;
+            }
+            case 'F': {
+                std::string why;
+                if (!pcs_depthfilter::parse(optarg, filter_cfg, why)) { std::cerr << "-F " << optarg << ": " << why << std::endl; exit(2); }
+                depth_filter = true;
                 break;
             }
             default: print_usage(); exit(2);
@@ -154,6 +167,8 @@ struct FrameSource {
         depth.resize(n_streams); color.resize(n_streams);
         return true;
     }
+    // frame `frame` is the source's first frame again: a .pcsraw / .bag that loops (a synthetic source never repeats)
+    bool at_first_frame(int frame) const { return !synth && frames_in_file > 0 && frame % frames_in_file == 0; }
     bool next(int frame)
     {
         if (synth) {
@@ -228,12 +243,17 @@ int main(int argc, char** argv)
         std::cerr << "pcs_set_crop_box_mm: " << pcs_strerror(rc) << ": " << pcs_last_error(ctx) << std::endl; return 1;
     }
 
+    if (depth_filter && (rc = pcs_set_depth_filter(ctx, &filter_cfg)) != PCS_OK) {
+        std::cerr << "pcs_set_depth_filter: " << pcs_strerror(rc) << ": " << pcs_last_error(ctx) << std::endl; return 1;
+    }
+
     const size_t buf_shorts = PCS_HEADER_SHORTS + pcs_max_payload_shorts(ctx);
     short* buffer = nullptr;                                               // the reference mallocs BUF_SIZE shorts (:157);
     if (pcs_host_malloc(ctx, (void**)&buffer, sizeof(short) * buf_shorts) != PCS_OK) {   // page-locked: D2H at link speed
         std::cerr << pcs_last_error(ctx) << std::endl; return 1;
     }
     std::vector<const uint16_t*> dptr(n_streams);
+    std::vector<uint16_t*> fptr(n_streams);           // -F: the same rasters, filtered in place
     std::vector<const uint8_t*> cptr(n_streams);
     std::vector<int> counts(n_streams);
     pcs_kernel_timing(ctx, 1);
@@ -264,14 +284,22 @@ int main(int argc, char** argv)
                 pin_cb[s] = cb;
             }
             if (pageable) {       // -M: the frame source's own (pageable) memory goes straight in, like librealsense's frames do
-                dptr[s] = src.depth[s].data(); cptr[s] = src.color[s].data();
+                dptr[s] = fptr[s] = src.depth[s].data(); cptr[s] = src.color[s].data();
                 continue;
             }
             memcpy(pin_d[s], src.depth[s].data(), db);
             memcpy(pin_c[s], src.color[s].data(), cb);
-            dptr[s] = pin_d[s]; cptr[s] = pin_c[s];
+            dptr[s] = fptr[s] = pin_d[s]; cptr[s] = pin_c[s];
+        }
+        // A source that loops back to its first frame is a scene cut for the temporal state. (As the reference, :276, this program
+        // stops where a recording ends, so no source reaches this today; one that loops resets here.)
+        if (depth_filter && src.at_first_frame(i - 1) && i > 1 && (rc = pcs_reset_depth_filter(ctx)) != PCS_OK) {
+            std::cerr << "pcs_reset_depth_filter: " << pcs_last_error(ctx) << std::endl; return 1;
         }
         auto time_start = clockTime::now();                                   // :291
+        if (depth_filter && (rc = pcs_filter_depth(ctx, dptr.data(), fptr.data())) != PCS_OK) {
+            std::cerr << "pcs_filter_depth: " << pcs_last_error(ctx) << std::endl; return 1;
+        }
         rc = pcs_process_frames(ctx, dptr.data(), cptr.data(), buffer, buf_shorts, send_buffer ? 1 : 0, counts.data(), &buff_size);
         auto time_end = clockTime::now();                                     // :293
         if (rc != PCS_OK) { std::cerr << "pcs_process_frames: " << pcs_last_error(ctx) << std::endl; return 1; }

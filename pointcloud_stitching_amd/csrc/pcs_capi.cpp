@@ -761,6 +761,8 @@ void pcs_destroy(pcs_ctx* c)
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->d_crop_tab) (void)hipFree(c->d_crop_tab);
     if (c->d_crop_tiles) (void)hipFree(c->d_crop_tiles);
+    if (c->d_filter_state) (void)hipFree(c->d_filter_state);
+    if (c->d_filter_tab) (void)hipFree(c->d_filter_tab);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -808,6 +810,151 @@ int pcs_get_crop_box_mm(const pcs_ctx* c, int16_t lo[3], int16_t hi[3])
     if (!has_box(c)) return 0;
     for (int a = 0; a < 3; a++) { if (lo) lo[a] = c->box_lo[a]; if (hi) hi[a] = c->box_hi[a]; }
     return 1;
+}
+
+// ---- depth pre-filter ----------------------------------------------------------------------------
+namespace {
+
+// persistence 0..8 -> "valid in M of the last L frames" (librealsense's documented rules; 0 never, 8 always)
+const int kPersistM[9] = {9, 8, 2, 2, 2, 1, 1, 1, 0};
+const int kPersistL[9] = {8, 8, 3, 4, 8, 2, 5, 8, 8};
+
+void drop_depth_filter(pcs_ctx* c)
+{
+    if (c->d_filter_state) (void)hipFree(c->d_filter_state);
+    if (c->d_filter_tab) (void)hipFree(c->d_filter_tab);
+    c->d_filter_state = nullptr; c->filter_state_bytes = 0; c->d_filter_tab = nullptr;
+    c->filter_set = false;
+}
+
+}  // namespace
+
+int pcs_set_depth_filter(pcs_ctx* c, const pcs_depth_filter_config* cfg)
+try {
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (cfg) {
+        if (cfg->temporal != 0 && cfg->temporal != 1) return fail(c, PCS_ERR_INVALID_ARG, "depth filter: temporal must be 0 or 1, not %d", cfg->temporal);
+        if (!(cfg->alpha > 0.0f && cfg->alpha <= 1.0f)) return fail(c, PCS_ERR_INVALID_ARG, "depth filter: alpha %g is outside (0, 1]", (double)cfg->alpha);
+        if (cfg->delta < 1 || cfg->delta > 65535) return fail(c, PCS_ERR_INVALID_ARG, "depth filter: delta %d is outside 1..65535", cfg->delta);
+        if (cfg->persistence < 0 || cfg->persistence > 8) return fail(c, PCS_ERR_INVALID_ARG, "depth filter: persistence %d is outside 0..8", cfg->persistence);
+        if (cfg->hole_fill != 0 && cfg->hole_fill != 1)
+            return fail(c, PCS_ERR_UNSUPPORTED, "depth filter: hole_fill %d: only 1 (fill from left) is built; librealsense's other modes are "
+                        "raster-order recurrences over two dimensions", cfg->hole_fill);
+        if (!cfg->temporal && !cfg->hole_fill) return fail(c, PCS_ERR_INVALID_ARG, "depth filter: both stages are off (pass NULL to clear the filter)");
+        for (int s = 0; s < c->n_streams; s++)
+            if ((uint32_t)c->h_params[s].W > kFilterRowPixels)
+                return fail(c, PCS_ERR_UNSUPPORTED, "depth filter: stream %d: rows of %d pixels (at most %u)", s, c->h_params[s].W, kFilterRowPixels);
+    }
+    DeviceGuard guard(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // pcs_set_cam_to_world's rule: nothing enqueued earlier sees the change
+    drop_depth_filter(c);
+    if (!cfg) return PCS_OK;
+
+    const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    std::vector<FilterStream> tab(c->n_streams);
+    size_t total = 0;
+    uint32_t max_w = 1, max_rows = 0;
+    for (int s = 0; s < c->n_streams; s++) {
+        const StreamParams& P = c->h_params[s];
+        total += up((size_t)P.n_points * sizeof(uint16_t)) + up((size_t)P.n_points);
+        max_w = std::max(max_w, (uint32_t)P.W); max_rows = std::max(max_rows, (uint32_t)P.H);
+    }
+    if (cfg->temporal) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, total);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, PCS_ERR_NOMEM, "depth filter: hipMalloc(%zu) for the temporal state failed: %s", total, hipGetErrorString(e)); }
+        c->d_filter_state = static_cast<uint8_t*>(q); c->filter_state_bytes = total;
+    }
+    size_t off = 0;
+    for (int s = 0; s < c->n_streams; s++) {
+        const StreamParams& P = c->h_params[s];
+        FilterStream& f = tab[s];
+        f.last = nullptr; f.hist = nullptr;
+        if (cfg->temporal) {
+            f.last = reinterpret_cast<uint16_t*>(c->d_filter_state + off); off += up((size_t)P.n_points * sizeof(uint16_t));
+            f.hist = c->d_filter_state + off;                              off += up((size_t)P.n_points);
+        }
+        f.W = (uint32_t)P.W; f.H = (uint32_t)P.H; f.tile_base = P.tile_base; f.pad = 0;
+    }
+    hipError_t e = hipMalloc((void**)&c->d_filter_tab, sizeof(FilterStream) * tab.size());
+    if (e == hipSuccess) e = hipMemcpy(c->d_filter_tab, tab.data(), sizeof(FilterStream) * tab.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && c->d_filter_state) e = hipMemsetAsync(c->d_filter_state, 0, c->filter_state_bytes, c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        drop_depth_filter(c);
+        return fail(c, e == hipErrorOutOfMemory ? PCS_ERR_NOMEM : PCS_ERR_HIP, "depth filter: setting up the device tables failed: %s", hipGetErrorString(e));
+    }
+    c->filter_cfg = *cfg;
+    c->filter_args.a = cfg->alpha;
+    c->filter_args.oma = 1.0f - c->filter_args.a;
+    c->filter_args.delta = cfg->delta;
+    c->filter_args.l_mask = (1u << kPersistL[cfg->persistence]) - 1u;
+    c->filter_args.m = kPersistM[cfg->persistence];
+    c->filter_max_rows = max_rows; c->filter_max_width = max_w;
+    c->filter_set = true;
+    return PCS_OK;
+} catch (const std::exception& ex) {
+    return fail(c, PCS_ERR_NOMEM, "pcs_set_depth_filter: host allocation failed (%s)", ex.what());
+}
+
+int pcs_get_depth_filter(const pcs_ctx* c, pcs_depth_filter_config* out)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (!c->filter_set) return 0;
+    if (out) *out = c->filter_cfg;
+    return 1;
+}
+
+int pcs_reset_depth_filter(pcs_ctx* c)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (!c->filter_set) return fail(c, PCS_ERR_INVALID_ARG, "pcs_reset_depth_filter: no depth filter is set (pcs_set_depth_filter)");
+    DeviceGuard guard(c->device);
+    if (c->d_filter_state) HIPCHK(c, hipMemsetAsync(c->d_filter_state, 0, c->filter_state_bytes, c->stream));
+    return PCS_OK;
+}
+
+int pcs_filter_depth_device(pcs_ctx* c, const uint16_t* const* d_in, uint16_t* const* d_out, uint32_t* d_tile_kept)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (!c->filter_set) return fail(c, PCS_ERR_INVALID_ARG, "pcs_filter_depth_device: no depth filter is set (pcs_set_depth_filter)");
+    if (!d_in || !d_out) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
+    if (d_tile_kept) {
+        if ((c->flags & PCS_FLAG_CUTOFF) || has_box(c))
+            return fail(c, PCS_ERR_UNSUPPORTED, "pcs_filter_depth_device: tile counts are the non-zero pixels of the filtered rasters; what a "
+                        "context with %s keeps depends on the deprojection (pass d_tile_kept = NULL)", has_box(c) ? "a crop box" : "PCS_FLAG_CUTOFF");
+        if ((uintptr_t)d_tile_kept & 3u) return fail(c, PCS_ERR_INVALID_ARG, "d_tile_kept must be 4-byte aligned");
+    }
+    FilterPtrs fp{};
+    for (int s = 0; s < c->n_streams; s++) {
+        if (!d_in[s] || !d_out[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
+        if (((uintptr_t)d_in[s] | (uintptr_t)d_out[s]) & 1u) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: depth pointer not 2-byte aligned", s);
+        fp.in[s] = d_in[s]; fp.out[s] = d_out[s];
+    }
+    DeviceGuard guard(c->device);
+    if (d_tile_kept) HIPCHK(c, hipMemsetAsync(d_tile_kept, 0, sizeof(uint32_t) * c->total_tiles, c->stream));
+    HIPCHK(c, launch_depth_filter(c->d_filter_tab, c->n_streams, c->filter_max_rows, c->filter_max_width, c->filter_cfg.temporal != 0,
+                                  c->filter_cfg.hole_fill != 0, fp, c->filter_args, d_tile_kept, c->stream));
+    return PCS_OK;
+}
+
+int pcs_filter_depth(pcs_ctx* c, const uint16_t* const* in, uint16_t* const* out)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (!c->filter_set) return fail(c, PCS_ERR_INVALID_ARG, "pcs_filter_depth: no depth filter is set (pcs_set_depth_filter)");
+    if (!in || !out) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
+    for (int s = 0; s < c->n_streams; s++)
+        if (!in[s] || !out[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
+    DeviceGuard guard(c->device);
+    int rc;
+    if ((rc = ensure_rasters(c))) return rc;
+    for (int s = 0; s < c->n_streams; s++)
+        HIPCHK(c, hipMemcpyAsync(c->s_depth[s], in[s], (size_t)c->h_params[s].n_points * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = pcs_filter_depth_device(c, c->s_depth.data(), c->s_depth.data(), nullptr))) return rc;
+    for (int s = 0; s < c->n_streams; s++)
+        HIPCHK(c, hipMemcpyAsync(out[s], c->s_depth[s], (size_t)c->h_params[s].n_points * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PCS_OK;
 }
 
 int pcs_stream_points(const pcs_ctx* c, int stream)

@@ -1,4 +1,4 @@
-// pcs_device.h — structures shared by the HIP kernels (pcs_kernels.hip, pcs_kernels_voxel.hip, pcs_voxel.hip) and the C-ABI host layer
+// pcs_device.h — structures shared by the HIP kernels (pcs_kernels.hip, pcs_kernels_voxel.hip, pcs_kernels_filter.hip, pcs_voxel.hip) and the C-ABI host layer
 // (pcs_capi.cpp). Internal; the public surface is include/pcs_hip.h.
 #pragma once
 
@@ -281,6 +281,33 @@ struct XformCloud {
 };
 struct XformBatch { XformCloud c[kXformBatch]; };
 hipError_t launch_transform_payloads(const XformBatch& xb, int n, uint32_t max_out, hipStream_t st);
+
+// Depth pre-filter (pcs_set_depth_filter, pcs_kernels_filter.hip): temporal smoothing and fill-from-left, Z16 -> Z16, every stream of
+// a context in one launch (blockIdx.y = stream). The table lives in device memory (one entry per stream, uploaded when the filter is
+// set); the per-call raster pointers travel in the kernel's arguments.
+struct FilterStream {
+    uint16_t* last;          // [n_points] the temporal stage's previous output (nullptr: hole fill alone, no state)
+    uint8_t*  hist;          // [n_points] validity shift register, bit 0 = the most recent frame
+    uint32_t  W, H;          // depth raster
+    uint32_t  tile_base;     // as StreamParams::tile_base
+    uint32_t  pad;
+};
+struct FilterPtrs {
+    const uint16_t* in[PCS_MAX_STREAMS];
+    uint16_t*       out[PCS_MAX_STREAMS];      // out[s] == in[s] is allowed
+};
+struct FilterArgs {
+    float    a, oma;         // (float)alpha and 1.0f - a, each rounded once on the host
+    int32_t  delta;
+    uint32_t l_mask;         // (1 << L) - 1 of the persistence rule "valid in M of the last L"
+    int32_t  m;
+};
+// A workgroup owns one row of one stream; its tile counts are gathered in kFilterSlots LDS words, so W <= kFilterRowPixels for every
+// stream (pcs_set_depth_filter refuses wider rows). max_rows / max_width: the tallest and the widest raster of the launch.
+constexpr int      kFilterSlots     = 64;
+constexpr uint32_t kFilterRowPixels = (kFilterSlots - 2) * kTilePoints;
+hipError_t launch_depth_filter(const FilterStream* d_tab, int n_streams, uint32_t max_rows, uint32_t max_width, bool temporal,
+                               bool fill, const FilterPtrs& fp, const FilterArgs& fa, uint32_t* d_tile_kept, hipStream_t st);
 
 // a7 with stride.
 hipError_t launch_stitch(const int16_t* d_src, uint32_t src_points, int downsample,

@@ -111,6 +111,15 @@ struct pcs_ctx {
     StreamParams*                   d_crop_tab = nullptr;      // PCS_MAX_STREAMS entries (n_points, tile_base of each camera)
     uint32_t*                       d_crop_tiles = nullptr; size_t crop_tiles_cap = 0;   // bytes: counts, prefixes, kept per camera
 
+    // pcs_set_depth_filter: the configuration, the per-stream table on the device and the temporal state (one slab: every stream's
+    // last [n] uint16 then hist [n] uint8, each carved at 256 bytes; nullptr for hole fill alone)
+    bool                            filter_set = false;
+    pcs_depth_filter_config         filter_cfg{};
+    FilterArgs                      filter_args{};
+    FilterStream*                   d_filter_tab = nullptr;
+    uint8_t*                        d_filter_state = nullptr; size_t filter_state_bytes = 0;
+    uint32_t                        filter_max_rows = 0, filter_max_width = 0;      // the launch's grid and workgroup size
+
     std::string                     err;
 };
 

@@ -1,0 +1,203 @@
+// pcs_kernels_filter.hip — the depth pre-filter (pcs_set_depth_filter / pcs_filter_depth_device): temporal smoothing and
+// fill-from-left on Z16 rasters, every stream of a context in one launch. The definition is DESIGN.md §3 "Depth pre-filter"; it is
+// this project's own (modelled on librealsense's temporal and hole-filling blocks, parity with librealsense unpinned) and
+// tests/np_depth_filter.py restates it in numpy; the kernel is held to that restatement bit for bit.
+//
+// Shape: a workgroup owns one whole row of one stream (in place is safe: a lane stores exactly the pixels it loaded; the fill's
+// carry never leaves the workgroup). One pass of its 256 lanes covers 2048 pixels of the row, 8 consecutive pixels per lane; a wider
+// row loops and carries one value in a register; a launch whose widest row needs fewer lanes starts fewer waves (whole ones). One
+// row per workgroup measured faster than 2, 4 or 8 (8 x 1280x720, both stages, 256 lanes: 24.5 / 26.0 / 28.4 / 36.6 us; with the
+// three waves a 1280-pixel row fills, 23.8): the kernel waits on memory, and more, shorter workgroups keep more requests in flight.
+// Nontemporal stores of the state measured the same as plain ones (28.3 vs 28.4 us at four rows per workgroup): plain stores stay. Rows whose width is a multiple of 8 with 16-byte aligned rasters
+// move 16 bytes per lane (in, last, out) and 8 bytes of hist; every other row takes 2-byte accesses.
+//
+// Bytes per pixel: 10 with the temporal stage (2 in + 2 out + 4 last read/write + 2 hist read/write), 4 for hole fill alone.
+#include <algorithm>
+
+#include "pcs_device.h"
+
+namespace pcs {
+
+namespace {
+
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+template <bool TEMPORAL, bool FILL, bool COUNT>
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_depth_filter_kernel(const FilterStream* __restrict__ tab, FilterPtrs fp, FilterArgs fa, uint32_t* __restrict__ tile_kept)
+{
+    __shared__ uint32_t s_last[2][4];               // per pass parity: each wave's last non-zero value (0: none)
+    __shared__ uint32_t s_tiles[kFilterSlots];      // non-zero output pixels per tile this workgroup touches
+    const int s = blockIdx.y;
+    const FilterStream F = tab[s];
+    const uint32_t W = F.W;
+    const uint32_t r = blockIdx.x;
+    if (r >= F.H) return;                           // (uniform: before any barrier)
+    const uint16_t* in = fp.in[s];
+    uint16_t* out = fp.out[s];
+    const bool vec = (W & 7u) == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    const uint32_t pass_pixels = blockDim.x * kPointsPerLane;      // <= kTilePoints: a pass touches at most two tiles
+    const uint64_t row0 = (uint64_t)r * W;
+    const uint32_t tile_first = (uint32_t)(row0 / kTilePoints);
+    if (COUNT) {
+        if (threadIdx.x < kFilterSlots) s_tiles[threadIdx.x] = 0;
+        __syncthreads();
+    }
+    uint32_t parity = 0;
+    uint32_t carry = 0;                         // the fill's carry: starts at zero with the row
+    for (uint32_t c0 = 0; c0 < W; c0 += pass_pixels, parity ^= 1u) {
+        const uint32_t col = c0 + threadIdx.x * kPointsPerLane;
+        const uint32_t nv = col < W ? min((uint32_t)kPointsPerLane, W - col) : 0u;      // vec: 0 or 8
+        const uint64_t i0 = row0 + col;
+        uint32_t o[8], l[8], h[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { o[j] = 0; l[j] = 0; h[j] = 0; }
+        if (vec) {
+            if (nv) {
+                const uint4 v = *reinterpret_cast<const uint4*>(in + i0);
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) { o[2 * j] = w[j] & 0xFFFFu; o[2 * j + 1] = w[j] >> 16; }
+                if (TEMPORAL) {
+                    const uint4 q = *reinterpret_cast<const uint4*>(F.last + i0);
+                    const uint2 b = *reinterpret_cast<const uint2*>(F.hist + i0);
+                    const uint32_t lw[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                    for (int j = 0; j < 4; j++) { l[2 * j] = lw[j] & 0xFFFFu; l[2 * j + 1] = lw[j] >> 16; }
+#pragma unroll
+                    for (int j = 0; j < 4; j++) { h[j] = (b.x >> (8 * j)) & 0xFFu; h[4 + j] = (b.y >> (8 * j)) & 0xFFu; }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if ((uint32_t)j < nv) {
+                    o[j] = in[i0 + j];
+                    if (TEMPORAL) { l[j] = F.last[i0 + j]; h[j] = F.hist[i0 + j]; }
+                }
+        }
+        if (TEMPORAL) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const uint32_t c = o[j], p = l[j], hh = h[j];
+                if (c != 0) {
+                    int d = (int)c - (int)p;
+                    d = d < 0 ? -d : d;
+                    if (p != 0 && d < fa.delta) {
+                        // two rounded multiplies and one rounded add: no FMA
+                        const float f = __fadd_rn(__fmul_rn(fa.a, (float)c), __fmul_rn(fa.oma, (float)p));
+                        const uint32_t rr = (uint32_t)min((int)f, 65535);
+                        o[j] = rr; l[j] = rr; h[j] = ((hh << 1) | 1u) & 0xFFu;
+                    } else {
+                        l[j] = c; h[j] = 1u;
+                    }
+                } else {
+                    o[j] = (p != 0 && (int)__popc(hh & fa.l_mask) >= fa.m) ? p : 0u;
+                    h[j] = (hh << 1) & 0xFFu;
+                }
+            }
+            // the state sees the temporal stage alone: stored before the fill touches o[]
+            if (vec) {
+                if (nv) {
+                    uint4 q;
+                    q.x = l[0] | l[1] << 16; q.y = l[2] | l[3] << 16; q.z = l[4] | l[5] << 16; q.w = l[6] | l[7] << 16;
+                    uint2 b;
+                    b.x = h[0] | h[1] << 8 | h[2] << 16 | h[3] << 24;
+                    b.y = h[4] | h[5] << 8 | h[6] << 16 | h[7] << 24;
+                    *reinterpret_cast<uint4*>(F.last + i0) = q;
+                    *reinterpret_cast<uint2*>(F.hist + i0) = b;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    if ((uint32_t)j < nv) { F.last[i0 + j] = (uint16_t)l[j]; F.hist[i0 + j] = (uint8_t)h[j]; }
+            }
+        }
+        if (FILL) {
+            // a scan with the operator b ? b : a. Each lane reduces its 8 pixels; one ballot of "lane holds a non-zero" finds,
+            // for every lane, the nearest such lane below it; the four waves meet in four LDS words behind one barrier.
+            uint32_t run = 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++) run = o[j] ? o[j] : run;
+            const unsigned long long m = __ballot(run != 0);
+            const unsigned long long below = m & ((1ull << lane) - 1ull);
+            const uint32_t prev = (uint32_t)__shfl((int)run, below ? 63 - __clzll((long long)below) : 0);
+            const uint32_t wlast = (uint32_t)__shfl((int)run, m ? 63 - __clzll((long long)m) : 0);
+            if (lane == 0) s_last[parity][wave] = m ? wlast : 0u;
+            __syncthreads();
+            uint32_t win = carry, mine = carry;
+#pragma unroll
+            for (uint32_t w = 0; w < 4; w++) {
+                if (w == wave) mine = win;
+                const uint32_t v = w < n_waves ? s_last[parity][w] : 0u;
+                win = v ? v : win;
+            }
+            carry = win;
+            uint32_t inc = below ? prev : mine;
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                if (o[j] == 0) o[j] = inc; else inc = o[j];
+            }
+        }
+        if (vec) {
+            if (nv) {
+                uint4 v;
+                v.x = o[0] | o[1] << 16; v.y = o[2] | o[3] << 16; v.z = o[4] | o[5] << 16; v.w = o[6] | o[7] << 16;
+                *reinterpret_cast<uint4*>(out + i0) = v;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if ((uint32_t)j < nv) out[i0 + j] = (uint16_t)o[j];
+        }
+        if (COUNT) {
+            // a pass is at most 2048 consecutive pixels: it touches the tile of its first pixel and at most the next one
+            const uint32_t tile_a = (uint32_t)((row0 + c0) / kTilePoints);
+            const uint64_t edge = ((uint64_t)tile_a + 1) * kTilePoints;
+            uint32_t packed = 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if ((uint32_t)j < nv && o[j] != 0) packed += (i0 + j < edge) ? 1u : 0x10000u;
+            packed = wave_sum32(packed);         // <= 512 in each half
+            const uint32_t slot = tile_a - tile_first;
+            if (lane == 0) {
+                if ((packed & 0xFFFFu) && slot < (uint32_t)kFilterSlots) atomicAdd(&s_tiles[slot], packed & 0xFFFFu);
+                if ((packed >> 16) && slot + 1 < (uint32_t)kFilterSlots) atomicAdd(&s_tiles[slot + 1], packed >> 16);
+            }
+        }
+    }
+    if (COUNT) {
+        __syncthreads();
+        if (threadIdx.x < kFilterSlots) {
+            const uint32_t v = s_tiles[threadIdx.x];
+            if (v) atomicAdd(&tile_kept[F.tile_base + tile_first + threadIdx.x], v);       // one per tile touched
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_depth_filter(const FilterStream* d_tab, int n_streams, uint32_t max_rows, uint32_t max_width, bool temporal,
+                               bool fill, const FilterPtrs& fp, const FilterArgs& fa, uint32_t* d_tile_kept, hipStream_t st)
+{
+    if (n_streams <= 0 || max_rows == 0 || max_width == 0) return hipSuccess;
+    if (n_streams > PCS_MAX_STREAMS || (!temporal && !fill)) return hipErrorInvalidValue;
+    const dim3 grid(max_rows, (unsigned)n_streams);
+    // whole waves, as many as the widest row of the launch fills in one pass (at most the four of a 2048-pixel pass)
+    const unsigned lanes = (max_width + kPointsPerLane - 1) / kPointsPerLane;
+    const dim3 block(std::min<unsigned>(kBlockThreads, (lanes + 63u) & ~63u));
+#define L(T, F, C) hipLaunchKernelGGL((pcs_depth_filter_kernel<T, F, C>), grid, block, 0, st, d_tab, fp, fa, d_tile_kept)
+#define LC(T, F) do { if (d_tile_kept) L(T, F, true); else L(T, F, false); } while (0)
+    if (temporal && fill) LC(true, true); else if (temporal) LC(true, false); else LC(false, true);
+#undef LC
+#undef L
+    return hipGetLastError();
+}
+
+}  // namespace pcs

@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import CloudDesc, Config, PayloadDesc, StreamConfig
+from .types import CloudDesc, Config, DepthFilterConfig, PayloadDesc, StreamConfig
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -46,6 +46,11 @@ SYMBOLS = [
     ("pcs_process_frames_device", C.c_int, [_VP, _P(_VP), _P(_VP), _VP, C.c_size_t, _VP]),
     ("pcs_process_frames_device_counted", C.c_int, [_VP, _P(_VP), _P(_VP), _VP, _VP, C.c_size_t, _VP]),
     ("pcs_stream_tile_base", C.c_int, [_VP, C.c_int]),
+    ("pcs_set_depth_filter", C.c_int, [_VP, _P(DepthFilterConfig)]),
+    ("pcs_get_depth_filter", C.c_int, [_VP, _P(DepthFilterConfig)]),
+    ("pcs_reset_depth_filter", C.c_int, [_VP]),
+    ("pcs_filter_depth_device", C.c_int, [_VP, _P(_VP), _P(_VP), _VP]),
+    ("pcs_filter_depth", C.c_int, [_VP, _P(_VP), _P(_VP)]),
     ("pcs_process_frames_device_batch", C.c_int, [_VP, C.c_int, _P(_VP), _P(_VP), _P(_VP), C.c_size_t, _P(_VP)]),
     ("pcs_submit_frames", C.c_int, [_VP, _P(_VP), _P(_VP), _P(C.c_int)]),
     ("pcs_collect_frames", C.c_int, [_VP, C.c_int, _VP, C.c_size_t, C.c_int, _P(C.c_int), _P(C.c_int)]),

@@ -80,6 +80,12 @@ class PayloadDesc(C.Structure):
     _fields_ = [("d_payload", C.c_void_p), ("n_points", C.c_int32), ("transform", C.c_float * 16)]
 
 
+class DepthFilterConfig(C.Structure):
+    """pcs_depth_filter_config: the depth pre-filter's stages and the temporal stage's parameters (librealsense's defaults)."""
+    _fields_ = [("temporal", C.c_int32), ("alpha", C.c_float), ("delta", C.c_int32),
+                ("persistence", C.c_int32), ("hole_fill", C.c_int32)]
+
+
 # --- the reference's surveyed extrinsics (data, not code) -------------------------------------
 # src/pcs-camera-optimized.cpp:64-67
 TF_MAT = np.array([
