@@ -323,6 +323,55 @@ int pcs_reset_depth_filter(pcs_ctx* ctx);
 int pcs_filter_depth_device(pcs_ctx* ctx, const uint16_t* const* d_in, uint16_t* const* d_out, uint32_t* d_tile_kept);
 int pcs_filter_depth(pcs_ctx* ctx, const uint16_t* const* in, uint16_t* const* out);
 
+/* ---- depth decimation: every n x n block of a Z16 raster to one pixel, on the device --------------------------------------- *
+ * The first block of librealsense's post-processing chain (decimation, then spatial / temporal, then hole filling), as ONE
+ * stateless launch over every stream of the context, upstream of the depth pre-filter above and of the stitch calls: the payload
+ * shrinks by n*n and loses noise instead of keeping whatever the n-th point happens to be (pcs_config.downsample). The definition
+ * is this project's own (DESIGN.md section 3 "Depth decimation": modelled on librealsense's decimation filter, parity with
+ * librealsense unpinned - the reference never calls the block); the GPU output is held bit for bit to a numpy restatement of that
+ * text (tests/np_decimation.py).
+ *   scale n in 2..8; source W x H uint16, row-major, tightly packed; output Wd x Hd with Wd = W / n, Hd = H / n (integer division).
+ *   Source columns >= n*Wd and rows >= n*Hd are never read. The output is NOT padded (librealsense pads its output dimensions up
+ *   to a multiple of 4). Output pixel (r, c) is taken from the k non-zero values of the block in[n r + a][n c + b], a, b in [0, n):
+ *     k = 0       0
+ *     n = 2, 3    the lower median: with the non-zero values sorted ascending v_0 <= ... <= v_(k-1), v_((k-1) >> 1) (two valid
+ *                 pixels: the nearer surface)
+ *     n >= 4      floor(sum of the non-zero values / k), an integer division
+ *   Nothing crosses a block or a stream; there is no state.
+ * pcs_decimated_stream_config: the stream a decimated raster belongs to. Pure host arithmetic: no context, no device, works on a
+ *   machine without a GPU. The integer pixel index is the pixel's centre (mx = ((float)c - ppx) / fx) and
+ *   decimated column i stands for source columns n i .. n i + n - 1, so
+ *     fx'  = (float)((double)fx / n)                       fy'  likewise
+ *     ppx' = (float)(((double)ppx - (n - 1) / 2.0) / n)    ppy' likewise          width' = W / n, height' = H / n
+ *   each computed in double from the float fields and rounded to float once. model and coeffs are unchanged (they act on the
+ *   normalised mx, my); color, depth_to_color, depth_scale, color_bpp, color_stride and cam_to_world are copied: the colour raster
+ *   is NOT decimated - texture coordinates come from projecting the 3-D point into the colour camera, so the full-resolution
+ *   colour image keeps working. scale 1 copies in to out; in == out is allowed. scale outside 1..8, a NULL pointer, or a raster
+ *   with no pixel left (W / scale == 0 or H / scale == 0): PCS_ERR_INVALID_ARG (pcs_last_error(NULL) says which).
+ * pcs_decimate_depth_device: ctx is the context that will CONSUME the output, created from decimated stream configs (stream s has
+ *   depth.width = Wd_s, depth.height = Hd_s); src_width[s] / src_height[s] (host arrays, n_streams entries) are the source rasters'
+ *   sizes. Stateless: nothing is set, nothing is stored in the context. Validated on the host before anything is launched: scale
+ *   in 2..8; src_width[s] / scale == depth.width and src_height[s] / scale == depth.height for every stream; pointers non-NULL and
+ *   2-byte aligned; no d_out[s] shares a byte with any d_in[t] (in place is impossible) - PCS_ERR_INVALID_ARG, and pcs_last_error
+ *   names the stream and the quantity. Asynchronous on the context's stream, one launch for all streams whatever their sizes; rows
+ *   of any width. Works on every context (PCS_FLAG_SCALAR_ARITH included: decimation sits upstream of the arithmetic). d_out[s] is
+ *   what pcs_filter_depth_device and pcs_process_frames_device* take as d_depth[s]. Source rasters whose width is a multiple of 8
+ *   at a 16-byte aligned address are read with 16-byte loads, outputs likewise written with 16-byte stores; anything else works,
+ *   2 bytes at a time.
+ * pcs_decimate_depth: host pointers, synchronous: upload, pcs_decimate_depth_device, download. For the CLI and for tests. The
+ *   full-size staging is allocated on first use, grown when a later call is larger and freed by pcs_destroy; an allocation failure
+ *   is PCS_ERR_NOMEM and leaves the context usable.
+ * HBM traffic per stream: 2 W H bytes in + 2 Wd Hd bytes out. Measured (python tools/decimate_probe.py 200 20; 8 x 1280x720, one
+ *   MI355X, sources cold from HBM, per-call event pairs, median / minimum of 200 calls): scale 2 8.5 / 8.0 us, scale 3 11.6 / 11.1,
+ *   scale 4 9.0 / 8.6, scale 8 13.0 / 12.5 - latency-bound (the traffic floor is about 2 us). decimate + pcs_process_frames_device
+ *   on the decimated context against pcs_process_frames_device on the full-size one: 18.1 / 19.6 / 15.1 / 19.4 us against 23.2.
+ *   DESIGN.md section 10 (f6).                                                                                                   */
+int pcs_decimated_stream_config(const pcs_stream_config* in, int scale, pcs_stream_config* out);
+int pcs_decimate_depth_device(pcs_ctx* ctx, int scale, const int32_t* src_width, const int32_t* src_height,
+                              const uint16_t* const* d_in, uint16_t* const* d_out);
+int pcs_decimate_depth(pcs_ctx* ctx, int scale, const int32_t* src_width, const int32_t* src_height,
+                       const uint16_t* const* in, uint16_t* const* out);
+
 /* Throughput form: n_sets frame-sets of the SAME streams per call. d_depth / d_color hold n_sets * n_streams device
  * pointers, frame-set major (entry k*n_streams + s = stream s of frame-set k); d_payload[k] is frame-set k's payload
  * pointer (each with payload_shorts capacity), d_counts (optional) n_sets pointers as in pcs_process_frames_device.

@@ -192,6 +192,40 @@ class PcsContext:
         self._check(self._lib.pcs_filter_depth(self._h, ip, op))
         return out
 
+    # -- depth decimation ----------------------------------------------------------------------
+    def _src_sizes(self, src_shapes):
+        if len(src_shapes) != self.n_streams:
+            raise ValueError("need one source (height, width) per stream")
+        ws = (C.c_int32 * self.n_streams)(*[int(w) for _, w in src_shapes])
+        hs = (C.c_int32 * self.n_streams)(*[int(h) for h, _ in src_shapes])
+        return ws, hs
+
+    def decimate_depth_device(self, scale: int, src_shapes: Sequence[Tuple[int, int]], d_in: Sequence[int], d_out: Sequence[int]) -> None:
+        """pcs_decimate_depth_device on device pointers (ints), asynchronous and stateless: every scale x scale block of source
+        raster s (src_shapes[s] = (height, width)) to one pixel of d_out[s], which has this context's depth size — the context was
+        created from types.decimated_stream_config(cfg, scale). The definition: DESIGN.md section 3."""
+        if len(d_in) != self.n_streams or len(d_out) != self.n_streams:
+            raise ValueError("need one input and one output pointer per stream")
+        ws, hs = self._src_sizes(src_shapes)
+        ip = (C.c_void_p * self.n_streams)(*d_in)
+        op = (C.c_void_p * self.n_streams)(*d_out)
+        self._check(self._lib.pcs_decimate_depth_device(self._h, int(scale), ws, hs, ip, op))
+
+    def decimate_depth(self, scale: int, depth: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """pcs_decimate_depth: one frame-set of full-size Z16 rasters (2-D arrays) through the decimation (upload, launch,
+        download); returns new arrays of this context's depth sizes."""
+        if len(depth) != self.n_streams:
+            raise ValueError("need one depth raster per stream")
+        d = [np.ascontiguousarray(x, np.uint16) for x in depth]
+        if any(x.ndim != 2 for x in d):
+            raise ValueError("the source rasters must be 2-D (height, width) arrays")
+        ws, hs = self._src_sizes([x.shape for x in d])
+        out = [np.empty((int(st.depth.height), int(st.depth.width)), np.uint16) for st in self.streams]
+        ip = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in d])
+        op = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in out])
+        self._check(self._lib.pcs_decimate_depth(self._h, int(scale), ws, hs, ip, op))
+        return out
+
     # -- a2 twin -----------------------------------------------------------------------------
     def copy_pointcloud_xyzrgb_to_buffer(self, stream: int, vertices, texcoords, color,
                                          pc_buffer: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:

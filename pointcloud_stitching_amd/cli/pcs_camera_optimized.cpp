@@ -11,6 +11,9 @@
 //                  pcs_set_crop_box_mm; needs -m)
 //               -F <temporal[=alpha:delta:persistence],holes[=left]> (depth pre-filter on the GPU: the two librealsense blocks the
 //                  reference leaves as TODOs in sendXYZRGBPointcloud, :682-684; pcs_set_depth_filter)
+//               -D <n> (depth decimation on the GPU, ahead of -F as in librealsense's chain: every n x n block of the Z16 raster to
+//                  one pixel, median of the valid for n = 2, 3, mean of the valid for n = 4..8; 1 = off; pcs_decimate_depth. The
+//                  definition is this project's own; parity with librealsense unpinned)
 //
 //   -f takes "synth:<W>x<H>" (deterministic synthetic frames; the reference's bags are LFS stubs and
 //   need librealsense), a .pcsraw dump (see pointcloud_stitching_amd/synthetic.py: write_pcsraw) or a
@@ -32,6 +35,7 @@
 
 #include "pcs_bag.h"
 #include "pcs_cropbox.h"
+#include "pcs_decimate.h"
 #include "pcs_depthfilter.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
@@ -49,6 +53,7 @@ static bool crop = false;
 static int16_t crop_lo[3], crop_hi[3];
 static bool depth_filter = false;
 static pcs_depth_filter_config filter_cfg;
+static int decimate = 1;
 static int client_sock = 0, sockfd = 0;
 
 static void print_usage()
@@ -70,6 +75,9 @@ static void print_usage()
            "            (after the camera-to-world transform; ANDed with -c / -i; -d keeps every n-th KEPT point); needs -m\n"
            "  -F <temporal[=alpha:delta:persistence],holes[=left]>  depth pre-filter on the GPU, inside the timed region: temporal\n"
            "            smoothing (defaults 0.4:20:3 = librealsense's) and / or hole filling from the left, e.g. -F temporal=0.4:20:3,holes\n"
+           "  -D <n>    depth decimation on the GPU, inside the timed region and ahead of -F: every n x n block of the depth raster to one\n"
+           "            pixel (n = 2, 3: median of the valid pixels; n = 4..8: their mean; 1 = off); everything downstream sees the\n"
+           "            smaller cloud, the colour image stays as it is\n"
            "  -M        hand the frames over in ordinary pageable memory, as librealsense owns them in the reference's timed region\n"
            "            (:291-293): uploads are staged then. Default: frames copied to page-locked rasters BEFORE the timer starts\n"
            "            (zero copy) - the printed times then belong to a capture pipeline that delivers page-locked frames\n\n");
@@ -78,7 +86,7 @@ static void print_usage()
 static void parseArgs(int argc, char** argv)
 {
     int c;
-    while ((c = getopt(argc, argv, "hf:vst:cmzg:n:d:iCr:o:p:e:PHMB:F:")) != -1) {
+    while ((c = getopt(argc, argv, "hf:vst:cmzg:n:d:iCr:o:p:e:PHMB:F:D:")) != -1) {
         switch (c) {
             case 'h': print_usage(); exit(0);
             case 'f': filename = optarg; break;
@@ -110,6 +118,11 @@ static void parseArgs(int argc, char** argv)
                 std::string why;
                 if (!pcs_depthfilter::parse(optarg, filter_cfg, why)) { std::cerr << "-F " << optarg << ": " << why << std::endl; exit(2); }
                 depth_filter = true;
+                break;
+            }
+            case 'D': {
+                std::string why;
+                if (!pcs_decimate::parse(optarg, decimate, why)) { std::cerr << "-D " << optarg << ": " << why << std::endl; exit(2); }
                 break;
             }
             default: print_usage(); exit(2);
@@ -229,9 +242,19 @@ int main(int argc, char** argv)
         if (cam < n_streams) { std::cerr << extrinsics_path << ": only " << cam << " matrices for " << n_streams << " streams" << std::endl; return 2; }
     }
 
+    // -D: the context is created from the decimated streams; the source's own sizes go to pcs_decimate_depth with every frame
+    std::vector<pcs_stream_config> ctx_cfg = src.cfg;
+    std::vector<int32_t> src_w(n_streams), src_h(n_streams);
+    for (int s = 0; s < n_streams; s++) {
+        src_w[s] = src.cfg[s].depth.width; src_h[s] = src.cfg[s].depth.height;
+        if (decimate > 1 && pcs_decimated_stream_config(&src.cfg[s], decimate, &ctx_cfg[s]) != PCS_OK) {
+            std::cerr << "-D " << decimate << ": stream " << s << ": " << pcs_last_error(nullptr) << std::endl; return 2;
+        }
+    }
+
     pcs_config cfg;
     memset(&cfg, 0, sizeof cfg);
-    cfg.device = device; cfg.n_streams = n_streams; cfg.streams = src.cfg.data(); cfg.downsample = downsample;
+    cfg.device = device; cfg.n_streams = n_streams; cfg.streams = ctx_cfg.data(); cfg.downsample = downsample;
     cfg.flags = (cutoff ? PCS_FLAG_CUTOFF : 0u) | (cutoff_compat ? PCS_FLAG_CUTOFF_COMPAT : 0u) | (drop_invalid ? PCS_FLAG_DROP_INVALID : 0u) |
                 (half_pixel ? PCS_FLAG_TEXCOORD_HALF_PIXEL : 0u) |
                 (use_hip ? 0u : PCS_FLAG_SCALAR_ARITH);      // no -m: copyPointCloudXYZRGBToBuffer's arithmetic (:620-667, 688-694)
@@ -263,6 +286,15 @@ int main(int argc, char** argv)
     std::vector<uint16_t*> pin_d(n_streams, nullptr);
     std::vector<uint8_t*> pin_c(n_streams, nullptr);
     std::vector<size_t> pin_db(n_streams, 0), pin_cb(n_streams, 0);
+    // -D: the decimated rasters (page-locked like the frames, pageable under -M); what -F and the stitch then read
+    std::vector<uint16_t*> dec_d(n_streams, nullptr);
+    std::vector<std::vector<uint16_t>> dec_pageable(n_streams);
+    std::vector<const uint16_t*> sptr(n_streams);     // -D: the source rasters
+    for (int s = 0; decimate > 1 && s < n_streams; s++) {
+        const size_t px = (size_t)ctx_cfg[s].depth.width * ctx_cfg[s].depth.height;
+        if (pageable) { dec_pageable[s].resize(px); dec_d[s] = dec_pageable[s].data(); }
+        else if (pcs_host_malloc(ctx, (void**)&dec_d[s], px * sizeof(uint16_t)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+    }
 
     int i = 0, buff_size = 0;
     double duration_sum = 0, buff_size_sum = 0;
@@ -291,12 +323,17 @@ int main(int argc, char** argv)
             memcpy(pin_c[s], src.color[s].data(), cb);
             dptr[s] = fptr[s] = pin_d[s]; cptr[s] = pin_c[s];
         }
+        if (decimate > 1)
+            for (int s = 0; s < n_streams; s++) { sptr[s] = dptr[s]; dptr[s] = fptr[s] = dec_d[s]; }
         // A source that loops back to its first frame is a scene cut for the temporal state. (As the reference, :276, this program
         // stops where a recording ends, so no source reaches this today; one that loops resets here.)
         if (depth_filter && src.at_first_frame(i - 1) && i > 1 && (rc = pcs_reset_depth_filter(ctx)) != PCS_OK) {
             std::cerr << "pcs_reset_depth_filter: " << pcs_last_error(ctx) << std::endl; return 1;
         }
         auto time_start = clockTime::now();                                   // :291
+        if (decimate > 1 && (rc = pcs_decimate_depth(ctx, decimate, src_w.data(), src_h.data(), sptr.data(), fptr.data())) != PCS_OK) {
+            std::cerr << "pcs_decimate_depth: " << pcs_last_error(ctx) << std::endl; return 1;
+        }
         if (depth_filter && (rc = pcs_filter_depth(ctx, dptr.data(), fptr.data())) != PCS_OK) {
             std::cerr << "pcs_filter_depth: " << pcs_last_error(ctx) << std::endl; return 1;
         }
@@ -327,8 +364,9 @@ int main(int argc, char** argv)
     const size_t pts = points_in / i;
 
     // summary block — same lines as :317-342
-    std::cout << "\n### Video Frames H x W : " << src.cfg[0].color.height << " x " << src.cfg[0].color.width << std::endl;
-    std::cout << "### Depth Frames H x W : " << src.cfg[0].depth.height << " x " << src.cfg[0].depth.width << std::endl;
+    std::cout << "\n### Video Frames H x W : " << ctx_cfg[0].color.height << " x " << ctx_cfg[0].color.width << std::endl;
+    std::cout << "### Depth Frames H x W : " << ctx_cfg[0].depth.height << " x " << ctx_cfg[0].depth.width << std::endl;
+    if (decimate > 1) std::cout << "### Depth decimation : " << decimate << " x " << decimate << " (source " << src_h[0] << " x " << src_w[0] << ")" << std::endl;
     std::cout << "### # Points : " << pts << std::endl;
     std::cout << "\n### Total Frames = " << i << std::endl;
     std::cout << "### AVG Frame Time: " << duration_sum / i << " ms" << std::endl;
@@ -371,6 +409,7 @@ int main(int argc, char** argv)
     }
     pcs_host_free(ctx, buffer);
     for (int s = 0; s < n_streams; s++) { if (pin_d[s]) pcs_host_free(ctx, pin_d[s]); if (pin_c[s]) pcs_host_free(ctx, pin_c[s]); }
+    for (int s = 0; !pageable && s < n_streams; s++) if (dec_d[s]) pcs_host_free(ctx, dec_d[s]);
     pcs_destroy(ctx);
     return 0;
 }

@@ -763,6 +763,7 @@ void pcs_destroy(pcs_ctx* c)
     if (c->d_crop_tiles) (void)hipFree(c->d_crop_tiles);
     if (c->d_filter_state) (void)hipFree(c->d_filter_state);
     if (c->d_filter_tab) (void)hipFree(c->d_filter_tab);
+    if (c->d_decim_src) (void)hipFree(c->d_decim_src);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -955,6 +956,116 @@ int pcs_filter_depth(pcs_ctx* c, const uint16_t* const* in, uint16_t* const* out
         HIPCHK(c, hipMemcpyAsync(out[s], c->s_depth[s], (size_t)c->h_params[s].n_points * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PCS_OK;
+}
+
+// ---- depth decimation ----------------------------------------------------------------------------
+int pcs_decimated_stream_config(const pcs_stream_config* in, int scale, pcs_stream_config* out)
+{
+    if (!in || !out) return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_decimated_stream_config: NULL pointer");
+    if (scale < 1 || scale > 8) return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_decimated_stream_config: scale %d is outside 1..8", scale);
+    const int32_t wd = in->depth.width / scale, hd = in->depth.height / scale;
+    if (in->depth.width <= 0 || in->depth.height <= 0 || wd == 0 || hd == 0)
+        return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_decimated_stream_config: a %d x %d depth raster has no pixel left at scale %d",
+                    in->depth.width, in->depth.height, scale);
+    pcs_stream_config r = *in;                    // (in == out is allowed)
+    if (scale > 1) {
+        // decimated column i stands for source columns n i .. n i + n - 1, whose centre is n i + (n - 1) / 2: each quantity in double
+        // from the float fields, rounded to float once
+        const double n = (double)scale, half = (double)(scale - 1) / 2.0;
+        r.depth.width = wd; r.depth.height = hd;
+        r.depth.fx = (float)((double)in->depth.fx / n);
+        r.depth.fy = (float)((double)in->depth.fy / n);
+        r.depth.ppx = (float)(((double)in->depth.ppx - half) / n);
+        r.depth.ppy = (float)(((double)in->depth.ppy - half) / n);
+    }
+    *out = r;
+    return PCS_OK;
+}
+
+int pcs_decimate_depth_device(pcs_ctx* c, int scale, const int32_t* src_width, const int32_t* src_height,
+                              const uint16_t* const* d_in, uint16_t* const* d_out)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (scale < 2 || scale > 8) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: scale %d is outside 2..8", scale);
+    if (!src_width || !src_height || !d_in || !d_out) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: NULL pointer");
+    DecimArgs da{};
+    uint32_t max_w = 0, max_rows = 0;
+    for (int s = 0; s < c->n_streams; s++) {
+        const StreamParams& P = c->h_params[s];
+        if (src_width[s] <= 0 || src_width[s] / scale != P.W)
+            return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: stream %d: src_width %d / scale %d is not the context's depth.width %d",
+                        s, src_width[s], scale, P.W);
+        if (src_height[s] <= 0 || src_height[s] / scale != P.H)
+            return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: stream %d: src_height %d / scale %d is not the context's depth.height %d",
+                        s, src_height[s], scale, P.H);
+        if (!d_in[s]) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: stream %d: d_in is NULL", s);
+        if (!d_out[s]) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: stream %d: d_out is NULL", s);
+        if ((uintptr_t)d_in[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: stream %d: d_in is not 2-byte aligned", s);
+        if ((uintptr_t)d_out[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: stream %d: d_out is not 2-byte aligned", s);
+        da.in[s] = d_in[s]; da.out[s] = d_out[s];
+        da.Ws[s] = (uint32_t)src_width[s]; da.Wd[s] = (uint32_t)P.W; da.Hd[s] = (uint32_t)P.H;
+        max_w = std::max(max_w, (uint32_t)P.W); max_rows = std::max(max_rows, (uint32_t)P.H);
+    }
+    // no output may share a byte with any input (the source raster as the caller holds it: src_width x src_height)
+    for (int s = 0; s < c->n_streams; s++) {
+        const uintptr_t o0 = (uintptr_t)d_out[s], o1 = o0 + (size_t)c->h_params[s].n_points * sizeof(uint16_t);
+        for (int t = 0; t < c->n_streams; t++) {
+            const uintptr_t i0 = (uintptr_t)d_in[t], i1 = i0 + (size_t)src_width[t] * (size_t)src_height[t] * sizeof(uint16_t);
+            if (o0 < i1 && i0 < o1)
+                return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth_device: stream %d: d_out overlaps d_in of stream %d (decimation cannot "
+                            "run in place)", s, t);
+        }
+    }
+    DeviceGuard guard(c->device);
+    HIPCHK(c, launch_decimate_depth(scale, c->n_streams, max_rows, max_w, da, c->stream));
+    return PCS_OK;
+}
+
+int pcs_decimate_depth(pcs_ctx* c, int scale, const int32_t* src_width, const int32_t* src_height,
+                       const uint16_t* const* in, uint16_t* const* out)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (scale < 2 || scale > 8) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth: scale %d is outside 2..8", scale);
+    if (!src_width || !src_height || !in || !out) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth: NULL pointer");
+    const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t total = 0;
+    for (int s = 0; s < c->n_streams; s++) {
+        const StreamParams& P = c->h_params[s];
+        if (src_width[s] <= 0 || src_width[s] / scale != P.W)
+            return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth: stream %d: src_width %d / scale %d is not the context's depth.width %d",
+                        s, src_width[s], scale, P.W);
+        if (src_height[s] <= 0 || src_height[s] / scale != P.H)
+            return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth: stream %d: src_height %d / scale %d is not the context's depth.height %d",
+                        s, src_height[s], scale, P.H);
+        if (!in[s] || !out[s]) return fail(c, PCS_ERR_INVALID_ARG, "pcs_decimate_depth: stream %d: NULL raster pointer", s);
+        total += up((size_t)src_width[s] * (size_t)src_height[s] * sizeof(uint16_t));
+    }
+    DeviceGuard guard(c->device);
+    int rc;
+    if ((rc = ensure_rasters(c))) return rc;
+    // (growing frees the smaller slab first; every earlier use of it was synchronised before its call returned)
+    if ((rc = ensure(c, c->d_decim_src, c->decim_src_cap, total))) return rc;
+    // From the first copy on, the caller's rasters are in use by the stream: every failure below leaves through the one
+    // synchronise at the end, so that no copy is still reading or writing them when the call returns.
+    const auto run = [&]() -> int {
+        const uint16_t* d_src[PCS_MAX_STREAMS];
+        size_t off = 0;
+        for (int s = 0; s < c->n_streams; s++) {
+            const size_t bytes = (size_t)src_width[s] * (size_t)src_height[s] * sizeof(uint16_t);
+            d_src[s] = reinterpret_cast<const uint16_t*>(c->d_decim_src + off);
+            HIPCHK(c, hipMemcpyAsync(c->d_decim_src + off, in[s], bytes, hipMemcpyHostToDevice, c->stream));
+            off += up(bytes);
+        }
+        int r;
+        if ((r = pcs_decimate_depth_device(c, scale, src_width, src_height, d_src, c->s_depth.data()))) return r;
+        for (int s = 0; s < c->n_streams; s++)
+            HIPCHK(c, hipMemcpyAsync(out[s], c->s_depth[s], (size_t)c->h_params[s].n_points * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+        return PCS_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == PCS_OK && e != hipSuccess) rc = fail(c, PCS_ERR_HIP, "pcs_decimate_depth: hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    return rc;
 }
 
 int pcs_stream_points(const pcs_ctx* c, int stream)

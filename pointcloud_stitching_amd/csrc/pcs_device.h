@@ -309,6 +309,19 @@ constexpr uint32_t kFilterRowPixels = (kFilterSlots - 2) * kTilePoints;
 hipError_t launch_depth_filter(const FilterStream* d_tab, int n_streams, uint32_t max_rows, uint32_t max_width, bool temporal,
                                bool fill, const FilterPtrs& fp, const FilterArgs& fa, uint32_t* d_tile_kept, hipStream_t st);
 
+// Depth decimation (pcs_decimate_depth_device, pcs_kernels_filter.hip): every scale x scale block of a Z16 raster to one pixel, the
+// lower median of its non-zero values (scale 2, 3) or their truncated mean (4..8); every stream of a context in one launch
+// (blockIdx.y = stream). The call is stateless and the source sizes are the caller's, per call: the per-stream table travels in the
+// kernel's arguments with the raster pointers (1792 bytes), so nothing is uploaded and nothing in the context can go stale.
+struct DecimArgs {
+    const uint16_t* in[PCS_MAX_STREAMS];       // source raster, Ws pixels per row
+    uint16_t*       out[PCS_MAX_STREAMS];      // Wd x Hd, tightly packed
+    uint32_t        Ws[PCS_MAX_STREAMS];       // source row pitch in pixels (columns >= scale * Wd are never read)
+    uint32_t        Wd[PCS_MAX_STREAMS], Hd[PCS_MAX_STREAMS];
+};
+// max_rows / max_width: the tallest and the widest OUTPUT raster of the launch. scale outside 2..8 is hipErrorInvalidValue.
+hipError_t launch_decimate_depth(int scale, int n_streams, uint32_t max_rows, uint32_t max_width, const DecimArgs& da, hipStream_t st);
+
 // a7 with stride.
 hipError_t launch_stitch(const int16_t* d_src, uint32_t src_points, int downsample,
                          int16_t* d_dst, hipStream_t st);

@@ -120,6 +120,10 @@ struct pcs_ctx {
     uint8_t*                        d_filter_state = nullptr; size_t filter_state_bytes = 0;
     uint32_t                        filter_max_rows = 0, filter_max_width = 0;      // the launch's grid and workgroup size
 
+    // pcs_decimate_depth (host pointers): the full-size source rasters' staging, one slab carved at 256 bytes per stream; allocated on
+    // first use, grown when a later call needs more. (The decimated outputs land in s_depth, which is decimated-size already.)
+    uint8_t*                        d_decim_src = nullptr; size_t decim_src_cap = 0;
+
     std::string                     err;
 };
 

@@ -12,6 +12,8 @@
 // move 16 bytes per lane (in, last, out) and 8 bytes of hist; every other row takes 2-byte accesses.
 //
 // Bytes per pixel: 10 with the temporal stage (2 in + 2 out + 4 last read/write + 2 hist read/write), 4 for hole fill alone.
+//
+// Second half of the file: the depth decimation (pcs_decimate_depth_device), the stage ahead of the filter; its own comment is there.
 #include <algorithm>
 
 #include "pcs_device.h"
@@ -196,6 +198,191 @@ hipError_t launch_depth_filter(const FilterStream* d_tab, int n_streams, uint32_
 #define LC(T, F) do { if (d_tile_kept) L(T, F, true); else L(T, F, false); } while (0)
     if (temporal && fill) LC(true, true); else if (temporal) LC(true, false); else LC(false, true);
 #undef LC
+#undef L
+    return hipGetLastError();
+}
+
+// ---- depth decimation (pcs_decimate_depth_device) ---------------------------------------------------------------------------------
+// DESIGN.md §3 "Depth decimation": output pixel (r, c) of scale N is taken from the non-zero values of the source block
+// in[N r + a][N c + b]: their lower median for N = 2, 3, floor(sum / count) for N >= 4, 0 when there is none. This project's own
+// definition (modelled on librealsense's decimation block, parity with librealsense unpinned); tests/np_decimation.py restates it.
+//
+// Shape, from the filter's: a lane owns 8 consecutive OUTPUT pixels of one output row, that is 8 N consecutive source pixels of each
+// of N source rows; a wave belongs to one output row; a workgroup is the whole waves the widest output row of the launch fills
+// (a 640-pixel row: two), times as many rows as fit kDecimGroupLanes lanes; a wider row than one pass loops (nothing is carried). No
+// LDS, no barrier. Source rows whose width is a multiple of 8, in a 16-byte aligned raster, are read as N 16-byte loads per lane and
+// row; output rows whose width is a multiple of 8, in a 16-byte aligned raster, are written as one 16-byte store per lane; each side
+// falls back to 2-byte accesses on its own, and so does the one lane whose 8 outputs straddle the end of a row that is read wide.
+namespace {
+
+#ifndef PCS_DECIMATE_GROUP_LANES
+#define PCS_DECIMATE_GROUP_LANES 256          // (a build-time constant so that a lab build can measure others)
+#endif
+constexpr unsigned kDecimGroupLanes = PCS_DECIMATE_GROUP_LANES;
+static_assert(kDecimGroupLanes >= 64 && kDecimGroupLanes <= 1024 && kDecimGroupLanes % 64 == 0, "whole waves");
+
+__device__ __forceinline__ void cswap(uint32_t& a, uint32_t& b)
+{
+    const uint32_t lo = min(a, b), hi = max(a, b);
+    a = lo; b = hi;
+}
+
+// pixel p (a compile-time constant once unrolled) of a lane's slice of one source row: 8 N pixels held as 4 N packed words
+template <int N>
+__device__ __forceinline__ uint32_t slice_px(const uint32_t (&w)[4 * N], int p)
+{
+    return (p & 1) ? w[p >> 1] >> 16 : w[p >> 1] & 0xFFFFu;
+}
+
+// A lane's slice of one source row. wide: N aligned 16-byte loads. Otherwise 2-byte loads of the first n_px pixels, zeros behind
+// them (zeros are invalid pixels, and they only reach outputs that are not stored).
+template <int N>
+__device__ __forceinline__ void load_slice(const uint16_t* p, bool wide, uint32_t n_px, uint32_t (&w)[4 * N])
+{
+    if (wide) {
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            const uint4 v = reinterpret_cast<const uint4*>(p)[k];
+            w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4 * N; q++) {
+            const uint32_t lo = (uint32_t)(2 * q) < n_px ? p[2 * q] : 0u;
+            const uint32_t hi = (uint32_t)(2 * q + 1) < n_px ? p[2 * q + 1] : 0u;
+            w[q] = lo | hi << 16;
+        }
+    }
+}
+
+// N = 2, 3: the block is held (N x N uint4 per lane), zeros become 65536 so that they sort last, a fixed compare-exchange network
+// sorts the 4 or 9 values and a chain of selects picks element (k - 1) >> 1 — no register array is indexed by a run-time value.
+template <int N>
+__device__ __forceinline__ void decimate_median(const uint16_t* src, size_t pitch, bool wide, uint32_t n_px, uint32_t (&o)[8])
+{
+    static_assert(N == 2 || N == 3, "the median scales");
+    uint32_t w[N][4 * N];
+#pragma unroll
+    for (int a = 0; a < N; a++) load_slice<N>(src + a * pitch, wide, n_px, w[a]);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        uint32_t v[N * N], k = 0;
+#pragma unroll
+        for (int a = 0; a < N; a++)
+#pragma unroll
+            for (int b = 0; b < N; b++) {
+                const uint32_t x = slice_px<N>(w[a], N * j + b);
+                k += x != 0 ? 1u : 0u;
+                v[a * N + b] = x != 0 ? x : 65536u;
+            }
+        uint32_t m;
+        if (N == 2) {
+            cswap(v[0], v[1]); cswap(v[2], v[3]); cswap(v[0], v[2]); cswap(v[1], v[3]); cswap(v[1], v[2]);
+            m = k >= 3 ? v[1] : v[0];                                   // (k - 1) >> 1 is 0 for k = 1, 2 and 1 for k = 3, 4
+        } else {
+            // 25 compare-exchanges in 7 layers (a 0-1-principle check over all 512 inputs passes)
+            cswap(v[0], v[3]); cswap(v[1], v[7]); cswap(v[2], v[5]); cswap(v[4], v[8]);
+            cswap(v[0], v[7]); cswap(v[2], v[4]); cswap(v[3], v[8]); cswap(v[5], v[6]);
+            cswap(v[0], v[2]); cswap(v[1], v[3]); cswap(v[4], v[5]); cswap(v[7], v[8]);
+            cswap(v[1], v[4]); cswap(v[3], v[6]); cswap(v[5], v[7]);
+            cswap(v[0], v[1]); cswap(v[2], v[4]); cswap(v[3], v[5]); cswap(v[6], v[8]);
+            cswap(v[2], v[3]); cswap(v[4], v[5]); cswap(v[6], v[7]);
+            cswap(v[1], v[2]); cswap(v[3], v[4]); cswap(v[5], v[6]);
+            const uint32_t idx = (k - 1u) >> 1;                        // 0..4 for k = 1..9
+            m = v[0];
+            m = idx == 1u ? v[1] : m;
+            m = idx == 2u ? v[2] : m;
+            m = idx == 3u ? v[3] : m;
+            m = idx == 4u ? v[4] : m;
+        }
+        o[j] = k != 0 ? m : 0u;
+    }
+}
+
+// N >= 4: the block is not held (N = 8 would be 64 uint4 per lane, and left to itself the compiler does hold it: 256 VGPRs). Eight
+// 32-bit sums (at most 64 x 65535) and eight counts grow source row by source row over two slices that take turns: while one is
+// added the other's loads are in flight. The row loop is kept a loop for that; everything inside it unrolls. The division is the
+// integer one.
+template <int N>
+__device__ __forceinline__ void accumulate_slice(const uint32_t (&w)[4 * N], uint32_t (&sum)[8], uint32_t (&cnt)[8])
+{
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+#pragma unroll
+        for (int b = 0; b < N; b++) {
+            const uint32_t x = slice_px<N>(w, N * j + b);
+            sum[j] += x;
+            cnt[j] += x != 0 ? 1u : 0u;
+        }
+}
+
+template <int N>
+__device__ __forceinline__ void decimate_mean(const uint16_t* src, size_t pitch, bool wide, uint32_t n_px, uint32_t (&o)[8])
+{
+    static_assert(N >= 4 && N <= 8, "the mean scales");
+    uint32_t sum[8], cnt[8], even[4 * N], odd[4 * N];
+#pragma unroll
+    for (int j = 0; j < 8; j++) { sum[j] = 0; cnt[j] = 0; }
+    load_slice<N>(src, wide, n_px, even);
+#pragma unroll 1
+    for (int a = 0; a < N; a += 2) {
+        if (a + 1 < N) load_slice<N>(src + (size_t)(a + 1) * pitch, wide, n_px, odd);
+        accumulate_slice<N>(even, sum, cnt);
+        if (a + 2 < N) load_slice<N>(src + (size_t)(a + 2) * pitch, wide, n_px, even);
+        if (a + 1 < N) accumulate_slice<N>(odd, sum, cnt);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) o[j] = cnt[j] != 0 ? sum[j] / cnt[j] : 0u;
+}
+
+template <int N>
+__global__ __launch_bounds__(kDecimGroupLanes > (unsigned)kBlockThreads ? kDecimGroupLanes : (unsigned)kBlockThreads)
+void pcs_decimate_depth_kernel(DecimArgs da)
+{
+    const int s = blockIdx.y;
+    const uint32_t Ws = da.Ws[s], Wd = da.Wd[s];
+    const uint32_t r = blockIdx.x * blockDim.y + threadIdx.y;          // (blockDim.x is whole waves: a wave has one r)
+    if (r >= da.Hd[s]) return;
+    const uint16_t* in = da.in[s];
+    uint16_t* out = da.out[s];
+    const bool wide_in = (Ws & 7u) == 0 && (((uintptr_t)in) & 15u) == 0;
+    const bool wide_out = (Wd & 7u) == 0 && (((uintptr_t)out) & 15u) == 0;
+    const uint16_t* src_row = in + (size_t)r * N * Ws;
+    uint16_t* out_row = out + (size_t)r * Wd;
+    const uint32_t pass_pixels = blockDim.x * kPointsPerLane;
+    for (uint32_t c0 = 0; c0 < Wd; c0 += pass_pixels) {
+        const uint32_t col = c0 + threadIdx.x * kPointsPerLane;
+        if (col >= Wd) continue;
+        const uint32_t nv = min((uint32_t)kPointsPerLane, Wd - col);    // wide_out: always 8
+        const uint16_t* src = src_row + (size_t)col * N;
+        uint32_t o[8];
+        if constexpr (N <= 3) decimate_median<N>(src, Ws, wide_in && nv == 8u, nv * N, o);
+        else decimate_mean<N>(src, Ws, wide_in && nv == 8u, nv * N, o);
+        if (wide_out) {
+            uint4 v;
+            v.x = o[0] | o[1] << 16; v.y = o[2] | o[3] << 16; v.z = o[4] | o[5] << 16; v.w = o[6] | o[7] << 16;
+            *reinterpret_cast<uint4*>(out_row + col) = v;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if ((uint32_t)j < nv) out_row[col + j] = (uint16_t)o[j];
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_decimate_depth(int scale, int n_streams, uint32_t max_rows, uint32_t max_width, const DecimArgs& da, hipStream_t st)
+{
+    if (scale < 2 || scale > 8 || n_streams < 0 || n_streams > PCS_MAX_STREAMS) return hipErrorInvalidValue;
+    if (n_streams == 0 || max_rows == 0 || max_width == 0) return hipSuccess;
+    // whole waves, as many as the widest output row fills in one pass (at most four); then as many rows as fit the group
+    const unsigned lanes = (max_width + kPointsPerLane - 1) / kPointsPerLane;
+    const unsigned bx = std::min<unsigned>(kBlockThreads, (lanes + 63u) & ~63u);
+    const unsigned by = std::max(1u, kDecimGroupLanes / bx);
+    const dim3 grid((max_rows + by - 1) / by, (unsigned)n_streams), block(bx, by);
+#define L(N) case N: hipLaunchKernelGGL((pcs_decimate_depth_kernel<N>), grid, block, 0, st, da); break
+    switch (scale) { L(2); L(3); L(4); L(5); L(6); L(7); L(8); }
 #undef L
     return hipGetLastError();
 }

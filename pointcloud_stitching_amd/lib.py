@@ -51,6 +51,9 @@ SYMBOLS = [
     ("pcs_reset_depth_filter", C.c_int, [_VP]),
     ("pcs_filter_depth_device", C.c_int, [_VP, _P(_VP), _P(_VP), _VP]),
     ("pcs_filter_depth", C.c_int, [_VP, _P(_VP), _P(_VP)]),
+    ("pcs_decimated_stream_config", C.c_int, [_P(StreamConfig), C.c_int, _P(StreamConfig)]),
+    ("pcs_decimate_depth_device", C.c_int, [_VP, C.c_int, _P(C.c_int32), _P(C.c_int32), _P(_VP), _P(_VP)]),
+    ("pcs_decimate_depth", C.c_int, [_VP, C.c_int, _P(C.c_int32), _P(C.c_int32), _P(_VP), _P(_VP)]),
     ("pcs_process_frames_device_batch", C.c_int, [_VP, C.c_int, _P(_VP), _P(_VP), _P(_VP), C.c_size_t, _P(_VP)]),
     ("pcs_submit_frames", C.c_int, [_VP, _P(_VP), _P(_VP), _P(C.c_int)]),
     ("pcs_collect_frames", C.c_int, [_VP, C.c_int, _VP, C.c_size_t, C.c_int, _P(C.c_int), _P(C.c_int)]),

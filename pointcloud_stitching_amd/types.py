@@ -178,6 +178,19 @@ def make_stream_config(depth: Intrinsics, color: Optional[Intrinsics] = None, *,
     return sc
 
 
+def decimated_stream_config(cfg: StreamConfig, scale: int) -> StreamConfig:
+    """pcs_decimated_stream_config: the stream a raster decimated by `scale` (1..8) belongs to — smaller depth raster, focal lengths
+    and principal point moved so that every decimated pixel deprojects along the centre of its source block; everything else, the
+    colour camera included, is copied. The C function does the arithmetic (no device is touched); ValueError on what it refuses."""
+    from . import lib as _libmod               # (lib imports this module)
+    lib = _libmod.load()
+    out = StreamConfig()
+    rc = lib.pcs_decimated_stream_config(C.byref(cfg), int(scale), C.byref(out))
+    if rc != 0:
+        raise ValueError(f"{STATUS_NAMES.get(rc, rc)}: {(lib.pcs_last_error(None) or b'').decode()}")
+    return out
+
+
 def stream_array(configs: Sequence[StreamConfig]):
     arr = (StreamConfig * len(configs))()
     for i, c in enumerate(configs):
