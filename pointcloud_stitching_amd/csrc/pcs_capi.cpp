@@ -300,6 +300,32 @@ int ensure_rasters(pcs_ctx* c)
     return alloc_raster_slab(c, c->s_slab, c->s_depth, c->s_color);
 }
 
+// The device word a certificate sweep of pcs_create counts into: zeroed, handed to the sweep's launch, read back when the sweep is done.
+struct SweepCounter {
+    unsigned long long* d_bad = nullptr;
+    ~SweepCounter() { if (d_bad) (void)hipFree(d_bad); }
+    template <class Launch>
+    hipError_t run(hipStream_t st, unsigned long long& bad, Launch&& launch)
+    {
+        hipError_t e;
+        if (!d_bad && (e = hipMalloc((void**)&d_bad, sizeof *d_bad)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(d_bad, 0, sizeof *d_bad, st)) != hipSuccess) return e;
+        if ((e = launch(d_bad)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+        return hipStreamSynchronize(st);
+    }
+};
+
+// The tail of pcs_process_frames / pcs_collect_frames: the int32 byte count in front of the payload
+// (src/pcs-multicamera-client.cpp:394-395), the kept points of every stream, the size. h: n_streams counts, then their total.
+void finish_stitched(const pcs_ctx* c, const int32_t* h, int16_t* stitched, int write_header, int* points_per_stream, int* out_size_bytes)
+{
+    const int32_t size = (int32_t)((size_t)h[c->n_streams] * PCS_POINT_BYTES);
+    if (write_header) std::memcpy(stitched, &size, sizeof size);
+    if (points_per_stream) for (int s = 0; s < c->n_streams; s++) points_per_stream[s] = h[s];
+    if (out_size_bytes) *out_size_bytes = size;
+}
+
 }  // namespace
 
 namespace pcs_host {
@@ -335,22 +361,16 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
                      int16_t* d_payload, size_t payload_shorts, int32_t* d_counts, bool force_three_pass,
                      const uint32_t* d_tile_kept)
 {
-    if (payload_shorts < c->max_payload_points * PCS_POINT_SHORTS && !has_pred(c->flags))
-        return fail(c, PCS_ERR_CAPACITY, "payload buffer holds %zu shorts, %zu needed", payload_shorts,
-                    c->max_payload_points * PCS_POINT_SHORTS);
-    if (has_pred(c->flags) && payload_shorts < c->max_payload_points * PCS_POINT_SHORTS)
-        return fail(c, PCS_ERR_CAPACITY, "payload buffer holds %zu shorts; with compaction the worst case "
-                    "%zu is required", payload_shorts, c->max_payload_points * PCS_POINT_SHORTS);
+    const bool pred = has_pred(c->flags);
+    if (payload_shorts < c->max_payload_points * PCS_POINT_SHORTS)
+        return fail(c, PCS_ERR_CAPACITY, pred ? "payload buffer holds %zu shorts; with compaction the worst case %zu is required"
+                                              : "payload buffer holds %zu shorts, %zu needed",
+                    payload_shorts, c->max_payload_points * PCS_POINT_SHORTS);
     if (((uintptr_t)d_payload & 1u) != 0) return fail(c, PCS_ERR_INVALID_ARG, "payload pointer must be 2-byte aligned");
 
-    const bool pred = has_pred(c->flags);
     const bool dense = !pred && c->downsample == 1 && c->dense_ok && (((uintptr_t)d_payload & 15u) == 0);
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (c->kernel_timing) {
-        int rc = acquire_event_pair(c, ev);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(ev.first, c->stream));
-    }
+    KernelTimer timer(c);
+    if (timer.rc) return timer.rc;
     const bool box = has_box(c);       // a boxed context always takes count + scan + emit (PCS_COMPACT_PATH does not apply)
     const bool one_launch = pred && !box && c->downsample == 1 && c->single_pass_ok && !force_three_pass && !d_tile_kept;
     const bool single_pass = one_launch && c->compact_path == 1;
@@ -371,14 +391,9 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
         }
         for (int s0 = 0; single_pass && s0 < c->n_streams; s0 += kLaunchStreams) {
             const int nl = std::min(kLaunchStreams, c->n_streams - s0);
-            FramePtrs fp{};
+            const FramePtrs fp = frame_ptrs(d_depth, d_color, s0, nl);
             uint32_t tiles = 0;
-            int m = 1;
-            for (int k = 0; k < nl; k++) {
-                fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k];
-                tiles += tiles_of(c->h_params[s0 + k].n_points);
-                m = std::min(m, c->h_params[s0 + k].cert_fast);
-            }
+            for (int k = 0; k < nl; k++) tiles += tiles_of(c->h_params[s0 + k].n_points);
             CompactLaunch cl{};
             cl.d_ticket = c->compact_tickets ? c->d_ticket : nullptr; cl.ticket_base = c->tickets_issued;
             cl.d_desc = c->d_desc + c->h_params[s0].tile_base;
@@ -388,24 +403,20 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
             cl.d_error = c->d_error; cl.gen = c->compact_seq; cl.flags = c->flags;
             cl.d_counts = d_counts ? d_counts : c->d_counts; cl.n_total = c->n_streams;
             cl.last_launch = (s0 + nl == c->n_streams) ? 1 : 0;
-            HIPCHK(c, launch_fused_compact(c->d_params, s0, nl, tiles, m >= 1 ? MathSel::Cert : MathSel::Ieee, fp, cl,
+            // (the single-pass kernel has the certified and the IEEE form only)
+            HIPCHK(c, launch_fused_compact(c->d_params, s0, nl, tiles, launch_traits(c, s0, nl).fast ? MathSel::Cert : MathSel::Ieee, fp, cl,
                                            d_payload, c->stream));
             c->tickets_issued += tiles;
         }
-        if (c->kernel_timing) {
-            HIPCHK(c, hipEventRecord(ev.second, c->stream));
-            c->ev_pool.push_back(ev);
-        }
-        return PCS_OK;
+        return timer.finish();
     }
     if (pred) {
         // (a caller that knows how many points each tile keeps — whatever wrote the depth image on the GPU — hands the counts
         // over and the count pass, with its second read of the Z16 rasters, does not run at all)
         for (int s0 = 0; !d_tile_kept && s0 < c->n_streams; s0 += kLaunchStreams) {
             const int nl = std::min(kLaunchStreams, c->n_streams - s0);
-            FramePtrs fp{};
-            uint32_t mp = 0;
-            for (int k = 0; k < nl; k++) { fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k]; mp = std::max(mp, c->h_params[s0 + k].n_points); }
+            const FramePtrs fp = frame_ptrs(d_depth, d_color, s0, nl);
+            const uint32_t mp = launch_traits(c, s0, nl).max_points;
             if (box) HIPCHK(c, launch_fused_count_crop(c->d_params, s0, nl, mp, c->flags, c->box, fp, c->d_tile_counts, c->stream));
             else     HIPCHK(c, launch_fused_count(c->d_params, s0, nl, mp, c->flags, fp, c->d_tile_counts, c->stream));
         }
@@ -415,27 +426,17 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
     }
     for (int s0 = 0; s0 < c->n_streams; s0 += kLaunchStreams) {
         const int nl = std::min(kLaunchStreams, c->n_streams - s0);
-        FramePtrs fp{};
-        uint32_t mp = 0;
-        for (int k = 0; k < nl; k++) { fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k]; mp = std::max(mp, c->h_params[s0 + k].n_points); }
-        bool fast = true, ident = true, noovf = true;    // AND over the streams of this launch
-        bool rowc = true;                                // ... and every stream row-constant, its raster rows whole 8-pixel runs
-        bool dd = false, cd = false;
-        for (int k = 0; k < nl; k++) {
-            const StreamParams& q = c->h_params[s0 + k];
-            fast &= q.cert_fast != 0; ident &= q.ident_r != 0; noovf &= q.no_overflow != 0;
-            rowc &= q.ident_r == 2 && (q.W & 7) == 0 && q.color_bytes >= 16;
-            dd |= q.ddist != 0;
-            cd |= q.cdist != 0 || q.tex_half != 0;
-        }
-        const MathSel sel = !fast ? MathSel::Ieee
-                          : noovf ? (ident ? MathSel::CertIdentRNoOvf : MathSel::CertNoOvf)
-                                  : (ident ? MathSel::CertIdentR : MathSel::Cert);
-        if (scalar_arith(c))   // a3: the dense / general launch over ScalarArith, -c a per-point select in it (no count, no scan)
-            HIPCHK(c, launch_fused_scalar(c->d_params, s0, nl, mp, dense, scalar_cut(c), c->downsample, fast ? MathSel::Cert : MathSel::Ieee,
+        const FramePtrs fp = frame_ptrs(d_depth, d_color, s0, nl);
+        const LaunchTraits t = launch_traits(c, s0, nl);
+        const uint32_t mp = t.max_points;
+        const MathSel sel = launch_math(t);
+        if (scalar_arith(c))   // a3: the dense / general launch over ScalarArith, -c a per-point select in it (no count, no scan);
+                               // its kernels have the certified and the IEEE form only
+            HIPCHK(c, launch_fused_scalar(c->d_params, s0, nl, mp, dense, scalar_cut(c), c->downsample, t.fast ? MathSel::Cert : MathSel::Ieee,
                                           fp, d_payload, c->stream));
         else if (dense) // (the dense kernel's row-constant form: its colour window is requested beside the depth, pcs_kernels.hip)
-            HIPCHK(c, launch_fused_dense(c->d_params, s0, nl, mp, dd, cd, sel == MathSel::CertIdentRNoOvf && rowc ? MathSel::CertRowConstNoOvf : sel,
+            HIPCHK(c, launch_fused_dense(c->d_params, s0, nl, mp, t.any_ddist, t.any_cdist,
+                                         sel == MathSel::CertIdentRNoOvf && t.row_const_tile ? MathSel::CertRowConstNoOvf : sel,
                                          fp, d_payload, c->stream));
         else if (box)
             HIPCHK(c, launch_fused_emit_crop(c->d_params, s0, nl, mp, c->flags, c->box, c->downsample, sel, fp, c->d_tile_prefix,
@@ -449,11 +450,7 @@ int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* 
     if (!pred && d_counts)     // counts are known from the configuration: a device-to-device copy, no host sync
         HIPCHK(c, hipMemcpyAsync(d_counts, c->d_static_counts, sizeof(int32_t) * (c->n_streams + 1),
                                  hipMemcpyDeviceToDevice, c->stream));
-    if (c->kernel_timing) {
-        HIPCHK(c, hipEventRecord(ev.second, c->stream));
-        c->ev_pool.push_back(ev);
-    }
-    return PCS_OK;
+    return timer.finish();
 }
 
 }  // namespace pcs_host
@@ -579,6 +576,7 @@ int pcs_create(pcs_ctx** out, const pcs_config* cfg)
     } while (0)
 
     DeviceGuard guard(c->device);
+    SweepCounter sweep;      // the certificate sweeps' device word: freed on every way out of this function
     CREATE_CHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
     CREATE_CHK(hipEventCreate(&c->ev_begin));
@@ -642,18 +640,13 @@ int pcs_create(pcs_ctx** out, const pcs_config* cfg)
     CREATE_CHK(hipMemset(c->d_arrive, 0, sizeof(uint32_t)));
     {   // device certificate for CertMath::div_const: all 2^32 numerators, once per distinct raster dimension
         std::vector<std::pair<int32_t, bool>> seen;
-        unsigned long long* d_bad = nullptr;
         auto verified = [&](int32_t dim, bool& ok) -> hipError_t {
             for (auto& pr : seen) if (pr.first == dim) { ok = pr.second; return hipSuccess; }
-            hipError_t e;
-            if (!d_bad && (e = hipMalloc((void**)&d_bad, sizeof(unsigned long long))) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream)) != hipSuccess) return e;
             const float cf = (float)dim, rc = (float)(1.0 / (double)cf);
-            if ((e = launch_verify_div_const(cf, rc, dim, d_bad, c->stream)) != hipSuccess) return e;
-            unsigned long long h = 1;
-            if ((e = hipMemcpyAsync(&h, d_bad, sizeof h, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
-            if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
-            ok = (h == 0);
+            unsigned long long bad = 1;
+            const hipError_t e = sweep.run(c->stream, bad, [&](unsigned long long* d_bad) { return launch_verify_div_const(cf, rc, dim, d_bad, c->stream); });
+            if (e != hipSuccess) return e;
+            ok = (bad == 0);
             seen.emplace_back(dim, ok);
             return hipSuccess;
         };
@@ -665,18 +658,7 @@ int pcs_create(pcs_ctx** out, const pcs_config* cfg)
             CREATE_CHK(verified(p.cH, okh));
             if (!(okw && okh)) { p.cert_fast = 0; p.ident_r = 0; p.no_overflow = 0; }
         }
-        if (d_bad) (void)hipFree(d_bad);
     }
-    // Single-pass compaction (one launch, direct-sum placement): 27.3-28.6 us against 30.3-32.2 us
-    // for count + scan + emit on 8x720p, but its forward progress assumes workgroups are dispatched in
-    // blockIdx order (bounded waits + three-pass re-run catch a violation) -> opt-in. PCS_COMPACT_TICKETS=1
-    // hands tile ids out in start order instead (dispatch-order independent; the contended atomic makes it 63 us).
-    // Ordered compaction. Default: count + scan + emit — three small launches, no inter-workgroup waiting at all, and
-    // the fastest form at large sizes (16 x 1080p: 111 us vs 129 us). PCS_COMPACT_PATH=single (older spelling:
-    // PCS_COMPACT_SINGLE_PASS=1) selects the single-pass kernel (one launch, Z16 read once; 32.6 vs 33.9 us on 8 x 720p,
-    // but its forward progress assumes workgroups are dispatched in blockIdx order — bounded waits + a three-pass re-run
-    // catch a violation), PCS_COMPACT_TICKETS=1 its dispatch-order independent but slow ticketed variant. DESIGN.md §5
-    // lists the persistent / chunked variants that were built to lift the ordering assumption and measured slower.
     // Ordered compaction. Default: count + scan + emit — three small launches, no inter-workgroup waiting at all, and the
     // fastest form at large sizes (16 x 1080p: 106 us vs 126 us). PCS_COMPACT_PATH=single (older spelling:
     // PCS_COMPACT_SINGLE_PASS=1) selects the single-pass kernel (one launch, Z16 read once; 31.2 vs 31.7 us on 8 x 720p,
@@ -703,27 +685,21 @@ int pcs_create(pcs_ctx** out, const pcs_config* cfg)
         // behind the my LUT is valid and ident_r becomes 2. PCS_ROW_CONST=0 leaves every stream at 1 (A/B; the tests run both).
         const char* env = getenv("PCS_ROW_CONST");
         const bool want = !(env && env[0] == '0');
-        unsigned long long* d_bad = nullptr;
         bool any = false;
         for (int s = 0; want && s < c->n_streams; s++) {
             StreamParams& p = c->h_params[s];
             const float* t = c->cfg[s].depth_to_color.translation;
             if (p.ident_r != 1 || p.ddist || p.cdist || p.tex_half || t[1] != 0.0f || t[2] != 0.0f || !p.z_zero_iff_d_zero) continue;
-            if (!d_bad) CREATE_CHK(hipMalloc((void**)&d_bad, sizeof(unsigned long long)));
-            CREATE_CHK(hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream));
             int32_t* d_crow = reinterpret_cast<int32_t*>(const_cast<float*>(p.my) + p.H);
-            CREATE_CHK(launch_certify_color_row(c->d_params, s, p.H, d_crow, d_bad, c->stream));
-            unsigned long long h = 1;
-            CREATE_CHK(hipMemcpyAsync(&h, d_bad, sizeof h, hipMemcpyDeviceToHost, c->stream));
-            CREATE_CHK(hipStreamSynchronize(c->stream));
-            if (h == 0) {
+            unsigned long long bad = 1;
+            CREATE_CHK(sweep.run(c->stream, bad, [&](unsigned long long* d_bad) { return launch_certify_color_row(c->d_params, s, p.H, d_crow, d_bad, c->stream); }));
+            if (bad == 0) {
                 p.ident_r = 2; any = true;
                 int32_t win[3];
                 color_window_params(p, t[0], win);
                 CREATE_CHK(hipMemcpy(d_crow + p.H, win, sizeof win, hipMemcpyHostToDevice));    // behind the colour rows (the my LUT's spare words)
             }
         }
-        if (d_bad) (void)hipFree(d_bad);
         if (any) CREATE_CHK(hipMemcpy(c->d_params, c->h_params.data(), sizeof(StreamParams) * c->n_streams, hipMemcpyHostToDevice));
     }
 #undef CREATE_CHK
@@ -926,12 +902,10 @@ int pcs_filter_depth_device(pcs_ctx* c, const uint16_t* const* d_in, uint16_t* c
                         "context with %s keeps depends on the deprojection (pass d_tile_kept = NULL)", has_box(c) ? "a crop box" : "PCS_FLAG_CUTOFF");
         if ((uintptr_t)d_tile_kept & 3u) return fail(c, PCS_ERR_INVALID_ARG, "d_tile_kept must be 4-byte aligned");
     }
+    int rc;
+    if ((rc = check_rasters(c, d_in, d_out, true)) || (rc = check_rasters(c, d_out, d_in, true))) return rc;      // (both are depth rasters)
     FilterPtrs fp{};
-    for (int s = 0; s < c->n_streams; s++) {
-        if (!d_in[s] || !d_out[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
-        if (((uintptr_t)d_in[s] | (uintptr_t)d_out[s]) & 1u) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: depth pointer not 2-byte aligned", s);
-        fp.in[s] = d_in[s]; fp.out[s] = d_out[s];
-    }
+    for (int s = 0; s < c->n_streams; s++) { fp.in[s] = d_in[s]; fp.out[s] = d_out[s]; }
     DeviceGuard guard(c->device);
     if (d_tile_kept) HIPCHK(c, hipMemsetAsync(d_tile_kept, 0, sizeof(uint32_t) * c->total_tiles, c->stream));
     HIPCHK(c, launch_depth_filter(c->d_filter_tab, c->n_streams, c->filter_max_rows, c->filter_max_width, c->filter_cfg.temporal != 0,
@@ -944,10 +918,9 @@ int pcs_filter_depth(pcs_ctx* c, const uint16_t* const* in, uint16_t* const* out
     if (!c) return PCS_ERR_INVALID_ARG;
     if (!c->filter_set) return fail(c, PCS_ERR_INVALID_ARG, "pcs_filter_depth: no depth filter is set (pcs_set_depth_filter)");
     if (!in || !out) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
-    for (int s = 0; s < c->n_streams; s++)
-        if (!in[s] || !out[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
-    DeviceGuard guard(c->device);
     int rc;
+    if ((rc = check_rasters(c, in, out, false))) return rc;
+    DeviceGuard guard(c->device);
     if ((rc = ensure_rasters(c))) return rc;
     for (int s = 0; s < c->n_streams; s++)
         HIPCHK(c, hipMemcpyAsync(c->s_depth[s], in[s], (size_t)c->h_params[s].n_points * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
@@ -1173,12 +1146,8 @@ int pcs_copy_pointclouds_xyzrgb_to_buffer_device(pcs_ctx* c, int n_clouds, const
         }
         return PCS_OK;
     }
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (c->kernel_timing) {
-        int rc = acquire_event_pair(c, ev);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(ev.first, c->stream));
-    }
+    KernelTimer timer(c);
+    if (timer.rc) return timer.rc;
     for (int i0 = 0; i0 < n_clouds; i0 += kPackBatch) {
         const int nb = std::min(kPackBatch, n_clouds - i0);
         PackBatch pb{};
@@ -1198,11 +1167,7 @@ int pcs_copy_pointclouds_xyzrgb_to_buffer_device(pcs_ctx* c, int n_clouds, const
     if (d_out_points)
         for (int i = 0; i < n_clouds; i++)
             HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(d_out_points + i), clouds[i].n_points, 1, c->stream));
-    if (c->kernel_timing) {
-        HIPCHK(c, hipEventRecord(ev.second, c->stream));
-        c->ev_pool.push_back(ev);
-    }
-    return PCS_OK;
+    return timer.finish();
 }
 
 // The device's view of a page-locked host range (pcs_host_malloc, hipHostMalloc, hipHostRegister).
@@ -1364,10 +1329,7 @@ int pcs_process_frames_device(pcs_ctx* c, const uint16_t* const* d_depth, const 
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
     if (!d_depth || !d_color || !d_payload) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
-    for (int s = 0; s < c->n_streams; s++)
-        if (!d_depth[s] || !d_color[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
-    for (int s = 0; s < c->n_streams; s++)
-        if ((uintptr_t)d_depth[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: depth pointer not 2-byte aligned", s);
+    if (int rc = check_rasters(c, d_depth, d_color, true)) return rc;
     DeviceGuard guard(c->device);
     return run_fused_device(c, d_depth, d_color, d_payload, payload_shorts, d_counts);
 } catch (const std::exception& ex) {
@@ -1382,10 +1344,7 @@ try {
     PCS_NO_CROP_BOX(c, "pcs_process_frames_device_counted");
     if (!d_depth || !d_color || !d_payload || !d_tile_kept) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     if ((uintptr_t)d_tile_kept & 3u) return fail(c, PCS_ERR_INVALID_ARG, "d_tile_kept must be 4-byte aligned");
-    for (int s = 0; s < c->n_streams; s++) {
-        if (!d_depth[s] || !d_color[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
-        if ((uintptr_t)d_depth[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: depth pointer not 2-byte aligned", s);
-    }
+    if (int rc = check_rasters(c, d_depth, d_color, true)) return rc;
     DeviceGuard guard(c->device);
     return run_fused_device(c, d_depth, d_color, d_payload, payload_shorts, d_counts, true, has_pred(c->flags) ? d_tile_kept : nullptr);
 } catch (const std::exception& ex) {
@@ -1416,13 +1375,8 @@ try {
         if (!d_payload[k]) return fail(c, PCS_ERR_INVALID_ARG, "frame-set %d: NULL payload pointer", k);
         if ((uintptr_t)d_payload[k] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "frame-set %d: payload pointer must be 2-byte aligned", k);
         aligned &= ((uintptr_t)d_payload[k] & 15u) == 0;
-        for (int s = 0; s < S; s++) {
-            if (!d_depth[(size_t)k * S + s] || !d_color[(size_t)k * S + s])
-                return fail(c, PCS_ERR_INVALID_ARG, "frame-set %d stream %d: NULL raster pointer", k, s);
-            if ((uintptr_t)d_depth[(size_t)k * S + s] & 1u)
-                return fail(c, PCS_ERR_INVALID_ARG, "frame-set %d stream %d: depth pointer not 2-byte aligned", k, s);
-        }
     }
+    if (int rc = check_rasters(c, d_depth, d_color, true, n_sets, true)) return rc;
     DeviceGuard guard(c->device);
     const int per_launch = std::min(kBatchSets, kBatchEntries / S);
     const bool dense = !has_pred(c->flags) && c->downsample == 1 && c->dense_ok && aligned && per_launch >= 2;
@@ -1445,27 +1399,14 @@ try {
         uint32_t* tprefix = tcounts + tt * per_launch;
         uint32_t* kept    = tprefix + tt * per_launch;
         int32_t*  icounts = reinterpret_cast<int32_t*>(kept + (size_t)S * per_launch);
-        bool fast = true, ident = true;
-        for (int s = 0; s < S; s++) { fast &= c->h_params[s].cert_fast != 0; ident &= c->h_params[s].ident_r != 0; }
-        const MathSel sel = !fast ? MathSel::Ieee : (ident ? MathSel::CertIdentR : MathSel::Cert);
-        std::pair<hipEvent_t, hipEvent_t> ev{};
-        if (c->kernel_timing) {
-            int rc = acquire_event_pair(c, ev);
-            if (rc) return rc;
-            HIPCHK(c, hipEventRecord(ev.first, c->stream));
-        }
+        const MathSel sel = launch_math(launch_traits(c, 0, S));      // (the emit kernels take no account of the no-overflow half)
+        KernelTimer timer(c);
+        if (timer.rc) return timer.rc;
         for (int k0 = 0; k0 < n_sets; k0 += per_launch) {
             const int nk = std::min(per_launch, n_sets - k0);
-            BatchPtrs bp{};
+            const BatchPtrs bp = batch_ptrs(S, d_depth, d_color, d_payload, k0, nk);
             BatchCounts bc{};
-            for (int k = 0; k < nk; k++) {
-                bp.payload[k] = reinterpret_cast<uint8_t*>(d_payload[k0 + k]);
-                bc.counts[k] = (d_counts && d_counts[k0 + k]) ? d_counts[k0 + k] : icounts + (size_t)k * (S + 1);
-                for (int s = 0; s < S; s++) {
-                    bp.depth[k * S + s] = d_depth[(size_t)(k0 + k) * S + s];
-                    bp.color[k * S + s] = d_color[(size_t)(k0 + k) * S + s];
-                }
-            }
+            for (int k = 0; k < nk; k++) bc.counts[k] = (d_counts && d_counts[k0 + k]) ? d_counts[k0 + k] : icounts + (size_t)k * (S + 1);
             if (has_box(c))
                 HIPCHK(c, launch_crop_batch(c->d_params, S, nk, c->max_points, c->total_tiles, c->flags, c->box, sel, bp, bc,
                                             tcounts, tprefix, kept, c->stream));
@@ -1473,11 +1414,7 @@ try {
                 HIPCHK(c, launch_compact_batch(c->d_params, S, nk, c->max_points, c->total_tiles, c->flags, sel, bp, bc,
                                                tcounts, tprefix, kept, c->stream));
         }
-        if (c->kernel_timing) {
-            HIPCHK(c, hipEventRecord(ev.second, c->stream));
-            c->ev_pool.push_back(ev);
-        }
-        return PCS_OK;
+        return timer.finish();
     }
     if (!dense) {
         for (int k = 0; k < n_sets; k++) {
@@ -1490,46 +1427,21 @@ try {
     if (payload_shorts < c->max_payload_points * PCS_POINT_SHORTS)
         return fail(c, PCS_ERR_CAPACITY, "payload buffers hold %zu shorts, %zu needed", payload_shorts,
                     c->max_payload_points * PCS_POINT_SHORTS);
-    bool fast = true, ident = true, noovf = true, dd = false, cd = false;
-    bool rowc = true;                                    // every stream row-constant, as in run_fused_device
-    for (int s = 0; s < S; s++) {
-        const StreamParams& q = c->h_params[s];
-        fast &= q.cert_fast != 0; ident &= q.ident_r != 0; noovf &= q.no_overflow != 0;
-        rowc &= q.ident_r == 2 && (q.W & 7) == 0 && q.color_bytes >= 16;
-        dd |= q.ddist != 0;
-        cd |= q.cdist != 0 || q.tex_half != 0;
-    }
-    MathSel sel = !fast ? MathSel::Ieee
-                : noovf ? (ident ? MathSel::CertIdentRNoOvf : MathSel::CertNoOvf)
-                        : (ident ? MathSel::CertIdentR : MathSel::Cert);
-    if (sel == MathSel::CertIdentRNoOvf && rowc) sel = MathSel::CertRowConstNoOvf;      // (the row-constant tile: pcs_kernels.hip)
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (c->kernel_timing) {
-        int rc = acquire_event_pair(c, ev);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(ev.first, c->stream));
-    }
+    const LaunchTraits t = launch_traits(c, 0, S);
+    MathSel sel = launch_math(t);
+    if (sel == MathSel::CertIdentRNoOvf && t.row_const_tile) sel = MathSel::CertRowConstNoOvf;      // (the row-constant tile: pcs_kernels.hip)
+    KernelTimer timer(c);
+    if (timer.rc) return timer.rc;
     for (int k0 = 0; k0 < n_sets; k0 += per_launch) {
         const int nk = std::min(per_launch, n_sets - k0);
-        BatchPtrs bp{};
-        for (int k = 0; k < nk; k++) {
-            bp.payload[k] = reinterpret_cast<uint8_t*>(d_payload[k0 + k]);
-            for (int s = 0; s < S; s++) {
-                bp.depth[k * S + s] = d_depth[(size_t)(k0 + k) * S + s];
-                bp.color[k * S + s] = d_color[(size_t)(k0 + k) * S + s];
-            }
-        }
-        HIPCHK(c, launch_fused_dense_batch(c->d_params, S, nk, c->max_points, dd, cd, sel, bp, c->stream));
+        HIPCHK(c, launch_fused_dense_batch(c->d_params, S, nk, c->max_points, t.any_ddist, t.any_cdist, sel,
+                                           batch_ptrs(S, d_depth, d_color, d_payload, k0, nk), c->stream));
     }
     if (d_counts)
         for (int k = 0; k < n_sets; k++)
             if (d_counts[k])
                 HIPCHK(c, hipMemcpyAsync(d_counts[k], c->d_static_counts, sizeof(int32_t) * (S + 1), hipMemcpyDeviceToDevice, c->stream));
-    if (c->kernel_timing) {
-        HIPCHK(c, hipEventRecord(ev.second, c->stream));
-        c->ev_pool.push_back(ev);
-    }
-    return PCS_OK;
+    return timer.finish();
 } catch (const std::exception& ex) {
     return fail(c, PCS_ERR_NOMEM, "pcs_process_frames_device_batch: host allocation failed (%s)", ex.what());
 }
@@ -1541,8 +1453,7 @@ try {
     if (!depth || !color || !stitched) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     DeviceGuard guard(c->device);
     int rc;
-    for (int s = 0; s < c->n_streams; s++)
-        if (!depth[s] || !color[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
+    if ((rc = check_rasters(c, depth, color, false))) return rc;
     {
         // Zero copy: when every raster and the stitched buffer are page-locked host memory the device can address
         // (pcs_host_malloc, hipHostMalloc, hipHostRegister), the kernels read the rasters and write the payload over PCIe
@@ -1576,10 +1487,7 @@ try {
             std::vector<int32_t> h(c->n_streams + 1);
             HIPCHK(c, hipMemcpyAsync(h.data(), c->d_counts, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            const int32_t size = (int32_t)((size_t)h[c->n_streams] * PCS_POINT_BYTES);
-            if (write_header) std::memcpy(stitched, &size, sizeof size);   // src/pcs-multicamera-client.cpp:394-395
-            if (points_per_stream) for (int s = 0; s < c->n_streams; s++) points_per_stream[s] = h[s];
-            if (out_size_bytes) *out_size_bytes = size;
+            finish_stitched(c, h.data(), stitched, write_header, points_per_stream, out_size_bytes);
             return PCS_OK;
         }
     }
@@ -1611,10 +1519,7 @@ try {
                     PCS_HEADER_SHORTS + total * PCS_POINT_SHORTS);
     if (total)
         HIPCHK(c, hipMemcpy(stitched + PCS_HEADER_SHORTS, c->s_payload, total * PCS_POINT_BYTES, hipMemcpyDeviceToHost));
-    const int32_t size = (int32_t)(total * PCS_POINT_BYTES);
-    if (write_header) std::memcpy(stitched, &size, sizeof size);   // src/pcs-multicamera-client.cpp:394-395
-    if (points_per_stream) for (int s = 0; s < c->n_streams; s++) points_per_stream[s] = h[s];
-    if (out_size_bytes) *out_size_bytes = size;
+    finish_stitched(c, h.data(), stitched, write_header, points_per_stream, out_size_bytes);
     return PCS_OK;
 } catch (const std::exception& ex) {
     return fail(c, PCS_ERR_NOMEM, "pcs_process_frames: host allocation failed (%s)", ex.what());
@@ -1625,8 +1530,7 @@ int pcs_submit_frames(pcs_ctx* c, const uint16_t* const* depth, const uint8_t* c
 try {
     if (!c) return PCS_ERR_INVALID_ARG;
     if (!depth || !color || !ticket) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
-    for (int s = 0; s < c->n_streams; s++)
-        if (!depth[s] || !color[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
+    if (int rc = check_rasters(c, depth, color, false)) return rc;
     DeviceGuard guard(c->device);
     pcs_ctx::PipeSlot* sl = nullptr;
     for (auto& cand : c->pipe) if (!cand.busy) { sl = &cand; break; }
@@ -1714,10 +1618,7 @@ try {
     if (total)
         HIPCHK(c, hipMemcpyAsync(stitched + PCS_HEADER_SHORTS, sl->payload, total * PCS_POINT_BYTES, hipMemcpyDeviceToHost, c->dl_stream));
     HIPCHK(c, hipStreamSynchronize(c->dl_stream));
-    const int32_t size = (int32_t)(total * PCS_POINT_BYTES);
-    if (write_header) std::memcpy(stitched, &size, sizeof size);
-    if (points_per_stream) for (int s = 0; s < c->n_streams; s++) points_per_stream[s] = h[s];
-    if (out_size_bytes) *out_size_bytes = size;
+    finish_stitched(c, h.data(), stitched, write_header, points_per_stream, out_size_bytes);
     release.ok = true;
     return PCS_OK;
 } catch (const std::exception& ex) {

@@ -97,19 +97,14 @@ static int launch_raster_voxel_partials(pcs_ctx* c, const uint16_t* const* d_dep
     const int S = c->n_streams;
     for (int s0 = 0; s0 < S; s0 += kLaunchStreams) {
         const int nl = std::min(kLaunchStreams, S - s0);
-        FramePtrs fp{};
-        uint32_t mp = 0, mw = 0, mh = 0;
-        bool fast = true, ident = true, rowc = true, patch_ok = true;
-        for (int k = 0; k < nl; k++) {
-            const StreamParams& q = c->h_params[s0 + k];
-            fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k];
-            mp = std::max(mp, q.n_points);
-            mw = std::max(mw, (uint32_t)q.W); mh = std::max(mh, q.n_points / (uint32_t)q.W);
-            patch_ok &= (q.W & 7) == 0 && ((uintptr_t)d_depth[s0 + k] & 15u) == 0;
-            fast &= q.cert_fast != 0; ident &= q.ident_r != 0; rowc &= q.ident_r == 2;
-        }
-        const MathSel sel = !fast ? MathSel::Ieee : (ident ? (rowc ? MathSel::CertRowConst : MathSel::CertIdentR) : MathSel::Cert);
-        HIPCHK(c, launch_fused_voxel_partials(c->d_params, s0, nl, mp, mw, mh, patch_ok, c->any_ddist || c->any_cdist, c->flags, sel, fp, vs, c->stream));
+        const LaunchTraits t = launch_traits(c, s0, nl);
+        bool patch_ok = true;
+        for (int k = 0; k < nl; k++) patch_ok &= (c->h_params[s0 + k].W & 7) == 0 && ((uintptr_t)d_depth[s0 + k] & 15u) == 0;
+        // the reader's own form: the colour row from the per-row table where every stream has one (it takes no account of the no-overflow half)
+        MathSel sel = launch_math(t);
+        if ((sel == MathSel::CertIdentR || sel == MathSel::CertIdentRNoOvf) && t.row_const) sel = MathSel::CertRowConst;
+        HIPCHK(c, launch_fused_voxel_partials(c->d_params, s0, nl, t.max_points, t.max_w, t.max_h, patch_ok, c->any_ddist || c->any_cdist, c->flags, sel,
+                                              frame_ptrs(d_depth, d_color, s0, nl), vs, c->stream));
     }
     return PCS_OK;
 }
@@ -122,10 +117,7 @@ try {
     if (!d_depth || !d_color || !d_out) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
     if (leaf_mm < 1 || leaf_mm > 32767) return fail(c, PCS_ERR_INVALID_ARG, "leaf_mm %d outside 1..32767", leaf_mm);
     const int S = c->n_streams;
-    for (int s = 0; s < S; s++) {
-        if (!d_depth[s] || !d_color[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
-        if ((uintptr_t)d_depth[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: depth pointer not 2-byte aligned", s);
-    }
+    if (int rc = check_rasters(c, d_depth, d_color, true)) return rc;
     const size_t cap = c->max_payload_points;          // every pixel kept, no stride
     if (out_shorts < cap * PCS_POINT_SHORTS)
         return fail(c, PCS_ERR_CAPACITY, "output holds %zu shorts; the worst case (every pixel its own voxel) needs %zu",
@@ -142,22 +134,14 @@ try {
     const size_t need = voxel_workspace_bytes((uint32_t)cap, voxel_workspace_level((uint32_t)cap, leaf_mm, c->vox_state, false));
     int rc = ensure_voxel_ws(c, need);
     if (rc) return rc;
-    std::pair<hipEvent_t, hipEvent_t> ev{};
-    if (c->kernel_timing) {
-        rc = acquire_event_pair(c, ev);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(ev.first, c->stream));
-    }
+    KernelTimer timer(c);
+    if (timer.rc) return timer.rc;
     VoxelStage vs{};
     HIPCHK(c, voxel_begin((uint32_t)cap, leaf_mm, c->s_voxel_ws, c->s_voxel_ws_cap, &c->vox_state, &vs, c->stream));
     rc = launch_raster_voxel_partials(c, d_depth, d_color, vs);
     if (rc) return rc;
     HIPCHK(c, voxel_finish((uint32_t)cap, leaf_mm, c->s_voxel_ws, c->s_voxel_ws_cap, &c->vox_state, d_out, d_out_points, c->stream));
-    if (c->kernel_timing) {
-        HIPCHK(c, hipEventRecord(ev.second, c->stream));
-        c->ev_pool.push_back(ev);
-    }
-    return PCS_OK;
+    return timer.finish();
 } catch (const std::exception& ex) {
     return fail(c, PCS_ERR_NOMEM, "pcs_process_frames_voxel_device: host allocation failed (%s)", ex.what());
 }
@@ -192,11 +176,7 @@ try {
     if (leaf_mm < 1 || leaf_mm > 32767) return fail(c, PCS_ERR_INVALID_ARG, "leaf_mm %d outside 1..32767", leaf_mm);
     if (((uintptr_t)d_keys & 7u) || ((uintptr_t)d_partials & 31u))
         return fail(c, PCS_ERR_INVALID_ARG, "d_keys must be 8-byte and d_partials 32-byte aligned");
-    const int S = c->n_streams;
-    for (int s = 0; s < S; s++) {
-        if (!d_depth[s] || !d_color[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
-        if ((uintptr_t)d_depth[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: depth pointer not 2-byte aligned", s);
-    }
+    if (int rc = check_rasters(c, d_depth, d_color, true)) return rc;
     const size_t cap = c->max_payload_points;
     if (capacity < cap)
         return fail(c, PCS_ERR_CAPACITY, "partial arrays hold %zu entries; the worst case (every kept point its own partial) needs %zu",
@@ -297,11 +277,7 @@ try {
     if (b.device != c->device)
         return fail(c, PCS_ERR_INVALID_ARG, "the sink lives on device %d, this context on device %d: a sink takes contexts of its own device only "
                     "(the pre-aggregation's atomics are device-scope; other GPUs exchange partials)", b.device, c->device);
-    const int S = c->n_streams;
-    for (int s = 0; s < S; s++) {
-        if (!d_depth[s] || !d_color[s]) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: NULL raster pointer", s);
-        if ((uintptr_t)d_depth[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "stream %d: depth pointer not 2-byte aligned", s);
-    }
+    if (int rc = check_rasters(c, d_depth, d_color, true)) return rc;
     if (c->max_payload_points > b.capacity)
         return fail(c, PCS_ERR_CAPACITY, "the sink was opened for %u points; this context alone can produce %zu", b.capacity, c->max_payload_points);
     DeviceGuard guard(c->device);

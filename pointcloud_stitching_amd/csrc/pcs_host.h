@@ -190,6 +190,112 @@ struct DeviceGuard {
 // The voxel workspace of a context, at least `need` bytes (grows with a quarter of headroom; growing waits for the stream).
 int ensure_voxel_ws(pcs_ctx* c, size_t need);
 int acquire_event_pair(pcs_ctx* c, std::pair<hipEvent_t, hipEvent_t>& pr);
+
+// The kernel-timing bracket (pcs_kernel_timing) around the launches of one call: constructed before the first launch, finish() after the
+// last. One bracket is one interval of pcs_kernel_times_ms. Every exit between the two, a HIPCHK return included, hands the pair back.
+struct KernelTimer {
+    pcs_ctx*                          c;
+    std::pair<hipEvent_t, hipEvent_t> ev{};
+    bool                              open = false;
+    int                               rc = PCS_OK;      // of the construction: the caller returns it if non-zero
+
+    explicit KernelTimer(pcs_ctx* ctx) : c(ctx) { if (c->kernel_timing) rc = start(); }
+    KernelTimer(const KernelTimer&) = delete;
+    KernelTimer& operator=(const KernelTimer&) = delete;
+    ~KernelTimer()
+    {
+        if (!open) return;
+        try { c->ev_free.push_back(ev); } catch (...) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    }
+    int finish()
+    {
+        if (!open) return PCS_OK;
+        HIPCHK(c, hipEventRecord(ev.second, c->stream));
+        c->ev_pool.push_back(ev);
+        open = false;
+        return PCS_OK;
+    }
+
+private:
+    int start()
+    {
+        const int r = acquire_event_pair(c, ev);
+        if (r) return r;
+        open = true;
+        HIPCHK(c, hipEventRecord(ev.first, c->stream));
+        return PCS_OK;
+    }
+};
+
+// What the streams [s0, s0 + nl) of one launch have in common: the AND of their certificates, the OR of their distortions, the largest
+// raster. Every launch site of the fused path takes its arithmetic from this one fold (launch_math) and states its own reduction.
+struct LaunchTraits {
+    uint32_t max_points = 0, max_w = 0, max_h = 0;
+    bool     fast = true, ident = true, noovf = true;     // every stream: cert_fast / ident_r / no_overflow
+    bool     any_ddist = false, any_cdist = false;        // (cdist: or the half-pixel texture convention, which runs on the CDIST path)
+    bool     row_const = true;          // every stream has ident_r == 2: the colour-row table the voxel reader uses (CertRowConst)
+    bool     row_const_tile = true;     // ... its raster rows whole 8-pixel runs, its colour raster 16 bytes or more: the dense tile
+};
+inline LaunchTraits launch_traits(const pcs_ctx* c, int s0, int nl)
+{
+    LaunchTraits t;
+    for (int s = s0; s < s0 + nl; s++) {
+        const StreamParams& q = c->h_params[s];
+        t.max_points = std::max(t.max_points, q.n_points);
+        t.max_w = std::max(t.max_w, (uint32_t)q.W); t.max_h = std::max(t.max_h, q.n_points / (uint32_t)q.W);
+        t.fast &= q.cert_fast != 0; t.ident &= q.ident_r != 0; t.noovf &= q.no_overflow != 0;
+        t.any_ddist |= q.ddist != 0;
+        t.any_cdist |= q.cdist != 0 || q.tex_half != 0;
+        t.row_const &= q.ident_r == 2;
+        t.row_const_tile &= q.ident_r == 2 && (q.W & 7) == 0 && q.color_bytes >= 16;
+    }
+    return t;
+}
+inline MathSel launch_math(const LaunchTraits& t)
+{
+    return !t.fast ? MathSel::Ieee
+         : t.noovf ? (t.ident ? MathSel::CertIdentRNoOvf : MathSel::CertNoOvf)
+                   : (t.ident ? MathSel::CertIdentR : MathSel::Cert);
+}
+
+// The raster pointers of streams [s0, s0 + nl) as one launch takes them / of frame-sets [k0, k0 + nk) as a K-set launch does.
+inline FramePtrs frame_ptrs(const uint16_t* const* d_depth, const uint8_t* const* d_color, int s0, int nl)
+{
+    FramePtrs fp{};
+    for (int k = 0; k < nl; k++) { fp.depth[k] = d_depth[s0 + k]; fp.color[k] = d_color[s0 + k]; }
+    return fp;
+}
+inline BatchPtrs batch_ptrs(int S, const uint16_t* const* d_depth, const uint8_t* const* d_color, int16_t* const* d_payload, int k0, int nk)
+{
+    BatchPtrs bp{};
+    for (int k = 0; k < nk; k++) {
+        bp.payload[k] = reinterpret_cast<uint8_t*>(d_payload[k0 + k]);
+        for (int s = 0; s < S; s++) {
+            bp.depth[k * S + s] = d_depth[(size_t)(k0 + k) * S + s];
+            bp.color[k * S + s] = d_color[(size_t)(k0 + k) * S + s];
+        }
+    }
+    return bp;
+}
+
+// The per-stream raster pointer arrays of an entry point (n_sets frame-sets, entry k * n_streams + s): none NULL, and every depth
+// raster 2-byte aligned where a kernel reads it. A batch call's messages name the frame-set too. (Colour: whatever rides beside.)
+template <class Color>
+int check_rasters(pcs_ctx* c, const uint16_t* const* depth, Color* const* color, bool need_depth_alignment, int n_sets = 1,
+                  bool name_set = false)
+{
+    for (int k = 0; k < n_sets; k++)
+        for (int s = 0; s < c->n_streams; s++) {
+            const size_t i = (size_t)k * c->n_streams + s;
+            const char* what = (!depth[i] || !color[i]) ? "NULL raster pointer"
+                             : (need_depth_alignment && ((uintptr_t)depth[i] & 1u)) ? "depth pointer not 2-byte aligned" : nullptr;
+            if (!what) continue;
+            return name_set ? fail(c, PCS_ERR_INVALID_ARG, "frame-set %d stream %d: %s", k, s, what)
+                            : fail(c, PCS_ERR_INVALID_ARG, "stream %d: %s", s, what);
+        }
+    return PCS_OK;
+}
+
 // The fused path for device-resident rasters. Counts end up in d_counts (if non-null).
 int run_fused_device(pcs_ctx* c, const uint16_t* const* d_depth, const uint8_t* const* d_color, int16_t* d_payload, size_t payload_shorts,
                      int32_t* d_counts, bool force_three_pass = false, const uint32_t* d_tile_kept = nullptr);

@@ -22,6 +22,7 @@
 // payload voxel readers, SLP on; the reasons are at its top). What both share, bit-exactness rules included: pcs_kernels_common.h.
 
 #include <algorithm>
+#include <type_traits>
 
 #include "pcs_kernels_common.h"
 
@@ -1749,6 +1750,49 @@ inline dim3 tile_grid(uint32_t max_points, int n_launch)
     return dim3((max_points + kTilePoints - 1) / kTilePoints, (unsigned)n_launch, 1);
 }
 
+// A launcher's ladder from run-time choices to a template instantiation: the choice arrives at a generic lambda as a tag value
+// (decltype(tag)::value / ::type), and only the combinations a ladder names are instantiated.
+template <class M> struct MathTag { using type = M; };
+constexpr std::true_type  kYes{};
+constexpr std::false_type kNo{};
+
+template <class F> void with_flag(bool b, F&& f) { if (b) f(kYes); else f(kNo); }
+
+// <DDIST, CDIST, Math> of the dense kernels (launch_fused_dense, launch_fused_dense_batch). CertRowConstNoOvf: after dense_row_const.
+template <class F>
+void with_dense_form(MathSel math, bool any_ddist, bool any_cdist, F&& f)
+{
+    if (math == MathSel::CertRowConstNoOvf) { f(kNo, kNo, MathTag<CertRowConstNoOvf>{}); return; }
+    if (math != MathSel::Ieee && !any_ddist) {
+        const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
+        const bool noovf = (math == MathSel::CertNoOvf || math == MathSel::CertIdentRNoOvf) && !any_cdist;
+        if (noovf)      { if (ident) f(kNo, kNo, MathTag<CertIdentNoOvf>{}); else f(kNo, kNo, MathTag<CertNoOvf>{}); }
+        else if (ident) { if (any_cdist) f(kNo, kYes, MathTag<CertMath<true>>{}); else f(kNo, kNo, MathTag<CertMath<true>>{}); }
+        else            { if (any_cdist) f(kNo, kYes, MathTag<CertMath<false>>{}); else f(kNo, kNo, MathTag<CertMath<false>>{}); }
+    } else {
+        if (any_ddist) { if (any_cdist) f(kYes, kYes, MathTag<IeeeMath>{}); else f(kYes, kNo, MathTag<IeeeMath>{}); }
+        else           { if (any_cdist) f(kNo, kYes, MathTag<IeeeMath>{}); else f(kNo, kNo, MathTag<IeeeMath>{}); }
+    }
+}
+
+// The row-constant tile requests its colour window in 16-byte pieces and pixel (0, 0)'s word by a scalar load, a lane's Z16 quad by one
+// 16-byte load (DepthSource::fast): 16-aligned rasters only, every one of the launch's n; otherwise CertIdentNoOvf's kernel.
+inline MathSel dense_row_const(MathSel math, bool any_ddist, bool any_cdist, const uint16_t* const* depth, const uint8_t* const* color, int n)
+{
+    if (math != MathSel::CertRowConstNoOvf) return math;
+    bool aligned = !any_ddist && !any_cdist;
+    for (int k = 0; k < n; k++) aligned &= ((((uintptr_t)color[k]) | ((uintptr_t)depth[k])) & 15u) == 0;
+    return aligned ? math : MathSel::CertIdentRNoOvf;
+}
+
+// Math of the emit kernels (the single-set and the K-set ones, with and without a crop box): they have no no-overflow forms.
+template <class F>
+void with_emit_math(MathSel math, F&& f)
+{
+    const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
+    if (math == MathSel::Ieee) f(MathTag<IeeeMath>{}); else if (ident) f(MathTag<CertMath<true>>{}); else f(MathTag<CertMath<false>>{});
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1763,29 +1807,14 @@ hipError_t launch_fused_dense(const StreamParams* d_params, int stream0, int n_l
     // (PCS_SMALL_TILES=1: one wavefront per 512-point tile — measured no faster on the launches it was meant for, see small_launch)
     const bool small = small_launch(max_points, n_launch);
     const dim3 grid = small ? dim3((max_points + kSmallTilePoints - 1) / kSmallTilePoints, (unsigned)n_launch, 1) : tile_grid(max_points, n_launch);
-#define L(DD, CD, M) do { if (small) hipLaunchKernelGGL((pcs_fused_dense_kernel<DD, CD, M, kSmallThreads>), grid, dim3(kSmallThreads), 0, st, \
-                                        d_params, stream0, fp, reinterpret_cast<uint8_t*>(d_payload)); \
-                          else hipLaunchKernelGGL((pcs_fused_dense_kernel<DD, CD, M>), grid, dim3(kBlockThreads), 0, st, \
-                                        d_params, stream0, fp, reinterpret_cast<uint8_t*>(d_payload)); } while (0)
-    if (math == MathSel::CertRowConstNoOvf) {
-        // the colour window is requested in 16-byte pieces and pixel (0, 0)'s word by a scalar load, a lane's Z16 quad by one 16-byte
-        // load (DepthSource::fast): 16-aligned rasters only; the rest of this launch's frames take CertIdentNoOvf's kernel
-        bool aligned = !any_ddist && !any_cdist;
-        for (int k = 0; k < n_launch; k++) aligned &= ((((uintptr_t)fp.color[k]) | ((uintptr_t)fp.depth[k])) & 15u) == 0;
-        if (aligned) { L(false, false, CertRowConstNoOvf); return hipGetLastError(); }
-        math = MathSel::CertIdentRNoOvf;
-    }
-    if (math != MathSel::Ieee && !any_ddist) {
-        const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
-        const bool noovf = (math == MathSel::CertNoOvf || math == MathSel::CertIdentRNoOvf) && !any_cdist;
-        if (noovf)      { if (ident) L(false, false, CertIdentNoOvf); else L(false, false, CertNoOvf); }
-        else if (ident) { if (any_cdist) L(false, true, CertMath<true>); else L(false, false, CertMath<true>); }
-        else            { if (any_cdist) L(false, true, CertMath<false>); else L(false, false, CertMath<false>); }
-    } else {
-        if (any_ddist) { if (any_cdist) L(true, true, IeeeMath); else L(true, false, IeeeMath); }
-        else           { if (any_cdist) L(false, true, IeeeMath); else L(false, false, IeeeMath); }
-    }
-#undef L
+    math = dense_row_const(math, any_ddist, any_cdist, fp.depth, fp.color, n_launch);
+    uint8_t* out = reinterpret_cast<uint8_t*>(d_payload);
+    with_dense_form(math, any_ddist, any_cdist, [&](auto dd, auto cd, auto m) {
+        constexpr bool DD = decltype(dd)::value, CD = decltype(cd)::value;
+        using M = typename decltype(m)::type;
+        if (small) hipLaunchKernelGGL((pcs_fused_dense_kernel<DD, CD, M, kSmallThreads>), grid, dim3(kSmallThreads), 0, st, d_params, stream0, fp, out);
+        else       hipLaunchKernelGGL((pcs_fused_dense_kernel<DD, CD, M>), grid, dim3(kBlockThreads), 0, st, d_params, stream0, fp, out);
+    });
     return hipGetLastError();
 }
 
@@ -1820,15 +1849,10 @@ hipError_t launch_fused_emit(const StreamParams* d_params, int stream0, int n_la
     const bool pred = (flags & (PCS_FLAG_CUTOFF | PCS_FLAG_DROP_INVALID)) != 0;
     const bool ds1 = downsample == 1;
     uint8_t* out = reinterpret_cast<uint8_t*>(d_payload);
-#define L(PR, D1, M) hipLaunchKernelGGL((pcs_fused_emit_kernel<PR, D1, M>), grid, dim3(kBlockThreads), 0, st, d_params, \
-                                        stream0, fp, flags, (uint32_t)downsample, d_tile_prefix, d_stream_kept, out, \
-                                        d_total_out, n_total_streams)
-#define LM(M) do { if (pred) { if (ds1) L(true, true, M); else L(true, false, M); } \
-                   else      { if (ds1) L(false, true, M); else L(false, false, M); } } while (0)
-    const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
-    if (math == MathSel::Ieee) LM(IeeeMath); else if (ident) LM(CertMath<true>); else LM(CertMath<false>);
-#undef LM
-#undef L
+    with_emit_math(math, [&](auto m) { with_flag(pred, [&](auto pr) { with_flag(ds1, [&](auto d1) {
+        hipLaunchKernelGGL((pcs_fused_emit_kernel<decltype(pr)::value, decltype(d1)::value, typename decltype(m)::type>), grid, dim3(kBlockThreads),
+                           0, st, d_params, stream0, fp, flags, (uint32_t)downsample, d_tile_prefix, d_stream_kept, out, d_total_out, n_total_streams);
+    }); }); });
     return hipGetLastError();
 }
 
@@ -1858,25 +1882,11 @@ hipError_t launch_fused_dense_batch(const StreamParams* d_params, int n_streams,
     if (n_streams <= 0 || n_sets <= 0 || max_points == 0) return hipSuccess;
     if (n_streams * n_sets > kBatchEntries || n_sets > kBatchSets) return hipErrorInvalidValue;
     const dim3 grid((max_points + kTilePoints - 1) / kTilePoints, (unsigned)n_streams, (unsigned)n_sets);
-#define L(DD, CD, M) hipLaunchKernelGGL((pcs_fused_dense_batch_kernel<DD, CD, M>), grid, dim3(kBlockThreads), 0, st, d_params, bp)
-    if (math == MathSel::CertRowConstNoOvf) {
-        // as in launch_fused_dense: 16-aligned rasters only, every set's; otherwise CertIdentNoOvf's kernel
-        bool aligned = !any_ddist && !any_cdist;
-        for (int k = 0; k < n_streams * n_sets; k++) aligned &= ((((uintptr_t)bp.color[k]) | ((uintptr_t)bp.depth[k])) & 15u) == 0;
-        if (aligned) { L(false, false, CertRowConstNoOvf); return hipGetLastError(); }
-        math = MathSel::CertIdentRNoOvf;
-    }
-    if (math != MathSel::Ieee && !any_ddist) {
-        const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
-        const bool noovf = (math == MathSel::CertNoOvf || math == MathSel::CertIdentRNoOvf) && !any_cdist;
-        if (noovf)      { if (ident) L(false, false, CertIdentNoOvf); else L(false, false, CertNoOvf); }
-        else if (ident) { if (any_cdist) L(false, true, CertMath<true>); else L(false, false, CertMath<true>); }
-        else            { if (any_cdist) L(false, true, CertMath<false>); else L(false, false, CertMath<false>); }
-    } else {
-        if (any_ddist) { if (any_cdist) L(true, true, IeeeMath); else L(true, false, IeeeMath); }
-        else           { if (any_cdist) L(false, true, IeeeMath); else L(false, false, IeeeMath); }
-    }
-#undef L
+    math = dense_row_const(math, any_ddist, any_cdist, bp.depth, bp.color, n_streams * n_sets);      // (every set's rasters)
+    with_dense_form(math, any_ddist, any_cdist, [&](auto dd, auto cd, auto m) {
+        hipLaunchKernelGGL((pcs_fused_dense_batch_kernel<decltype(dd)::value, decltype(cd)::value, typename decltype(m)::type>), grid,
+                           dim3(kBlockThreads), 0, st, d_params, bp);
+    });
     return hipGetLastError();
 }
 
@@ -1894,11 +1904,10 @@ hipError_t launch_compact_batch(const StreamParams* d_params, int n_streams, int
     hipLaunchKernelGGL(pcs_scan_batch_kernel, dim3((unsigned)n_streams, (unsigned)n_sets), dim3(1024), 0, st, d_params,
                        d_tile_counts, d_tile_prefix, d_stream_kept, total_tiles, bc);
     const dim3 grid(tiles, (unsigned)n_streams, (unsigned)n_sets);
-#define L(M) hipLaunchKernelGGL((pcs_fused_emit_batch_kernel<M>), grid, dim3(kBlockThreads), 0, st, d_params, bp, flags, \
-                                d_tile_prefix, d_stream_kept, total_tiles, bc)
-    const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
-    if (math == MathSel::Ieee) L(IeeeMath); else if (ident) L(CertMath<true>); else L(CertMath<false>);
-#undef L
+    with_emit_math(math, [&](auto m) {
+        hipLaunchKernelGGL((pcs_fused_emit_batch_kernel<typename decltype(m)::type>), grid, dim3(kBlockThreads), 0, st, d_params, bp, flags,
+                           d_tile_prefix, d_stream_kept, total_tiles, bc);
+    });
     return hipGetLastError();
 }
 
@@ -2072,13 +2081,10 @@ hipError_t launch_fused_emit_crop(const StreamParams* d_params, int stream0, int
     if (n_launch <= 0 || max_points == 0) return hipSuccess;
     const dim3 grid = tile_grid(max_points, n_launch);
     uint8_t* out = reinterpret_cast<uint8_t*>(d_payload);
-#define L(D1, M) hipLaunchKernelGGL((pcs_fused_emit_crop_kernel<D1, M>), grid, dim3(kBlockThreads), 0, st, d_params, stream0, fp, flags, \
-                                    crop_box(box), (uint32_t)downsample, d_tile_prefix, d_stream_kept, out, d_total_out, n_total_streams)
-#define LM(M) do { if (downsample == 1) L(true, M); else L(false, M); } while (0)
-    const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
-    if (math == MathSel::Ieee) LM(IeeeMath); else if (ident) LM(CertMath<true>); else LM(CertMath<false>);
-#undef LM
-#undef L
+    with_emit_math(math, [&](auto m) { with_flag(downsample == 1, [&](auto d1) {
+        hipLaunchKernelGGL((pcs_fused_emit_crop_kernel<decltype(d1)::value, typename decltype(m)::type>), grid, dim3(kBlockThreads), 0, st, d_params,
+                           stream0, fp, flags, crop_box(box), (uint32_t)downsample, d_tile_prefix, d_stream_kept, out, d_total_out, n_total_streams);
+    }); });
     return hipGetLastError();
 }
 
@@ -2094,11 +2100,10 @@ hipError_t launch_crop_batch(const StreamParams* d_params, int n_streams, int n_
                        d_tile_counts, total_tiles);
     hipLaunchKernelGGL(pcs_scan_batch_kernel, dim3((unsigned)n_streams, (unsigned)n_sets), dim3(1024), 0, st, d_params,
                        d_tile_counts, d_tile_prefix, d_stream_kept, total_tiles, bc);
-#define L(M) hipLaunchKernelGGL((pcs_fused_emit_crop_batch_kernel<M>), grid, dim3(kBlockThreads), 0, st, d_params, bp, flags, crop_box(box), \
-                                d_tile_prefix, d_stream_kept, total_tiles, bc)
-    const bool ident = (math == MathSel::CertIdentR || math == MathSel::CertIdentRNoOvf);
-    if (math == MathSel::Ieee) L(IeeeMath); else if (ident) L(CertMath<true>); else L(CertMath<false>);
-#undef L
+    with_emit_math(math, [&](auto m) {
+        hipLaunchKernelGGL((pcs_fused_emit_crop_batch_kernel<typename decltype(m)::type>), grid, dim3(kBlockThreads), 0, st, d_params, bp, flags,
+                           crop_box(box), d_tile_prefix, d_stream_kept, total_tiles, bc);
+    });
     return hipGetLastError();
 }
 
