@@ -372,6 +372,46 @@ int pcs_decimate_depth_device(pcs_ctx* ctx, int scale, const int32_t* src_width,
 int pcs_decimate_depth(pcs_ctx* ctx, int scale, const int32_t* src_width, const int32_t* src_height,
                        const uint16_t* const* in, uint16_t* const* out);
 
+/* ---- spatial filter: edge-preserving smoothing along rows and columns, Z16 -> Z16 on the device ----------------------------- *
+ * The second block of librealsense's chain (decimation, then SPATIAL, then temporal, then hole filling): call it between
+ * pcs_decimate_depth_device and pcs_filter_depth_device. Stateless; 2 x iterations launches over every stream of the context.
+ * The definition is this project's own (DESIGN.md section 3 "Spatial filter": modelled on librealsense's spatial filter, parity
+ * with librealsense unpinned); the GPU output is held bit for bit to a numpy restatement of that text
+ * (tests/np_spatial_filter.py). With a = (float)alpha and oma = 1.0f - a computed once on the host in fp32:
+ *   a line pass over x[0..n-1], fill on or off: v0 = x[0], run = 0; for u = 1..n-1 in order, v1 = x[u]:
+ *     v1 != 0                                 run = 0
+ *     v0, v1 != 0 and 1 <= |v1 - v0| <= delta x[u] = v1 = min((int)(fl(fl(a v1) + fl(oma v0)) + 0.5f), 65535): two rounded products,
+ *                                             two rounded sums, no FMA, truncated (d = 0 and an edge d > delta leave x[u] alone)
+ *     v0 != 0, v1 == 0, fill on, run < hole_radius    run += 1, x[u] = v1 = v0
+ *     then v0 = v1
+ *   one iteration: every row left to right (fill on), every row right to left (fill on), every column top to bottom (fill off),
+ *   every column bottom to top (fill off), each reading what the one before wrote; the filter is `iterations` of those. Nothing
+ *   crosses a stream; no state between calls. Unlike librealsense: the forward pass reaches the last pixel, run resets at every
+ *   valid input pixel, hole_radius is a pixel count (up to exactly that many per gap and direction), Z16 domain only.
+ * pcs_spatial_filter_depth_device: stream sizes are the context's depth.width x depth.height (after decimation: the decimated
+ *   ones). Nothing is set in the context and a depth filter that is set is not disturbed. Validated on the host before anything
+ *   is launched, PCS_ERR_INVALID_ARG with the quantity (and for a pointer the stream) in pcs_last_error: NULL config; NaN,
+ *   alpha <= 0 or > 1; delta outside 1..65535; iterations outside 1..5; hole_radius outside 0..65535; NULL or odd pointers; a
+ *   d_out[s] that shares a byte with any d_in[t] other than d_out[s] == d_in[s] (in place). Asynchronous on the context's stream.
+ *   The first row launch reads d_in and writes d_out, everything after it runs in place on d_out. Rows of any width; rasters
+ *   whose width is a multiple of 8 at 16-byte aligned addresses take 16-byte accesses in the row launches. Works on every context
+ *   (PCS_FLAG_SCALAR_ARITH included).
+ * pcs_spatial_filter_depth: host pointers, synchronous: upload to the context's staging rasters, in place there, download
+ *   (in[s] == out[s] is fine). For the CLI and for tests.
+ * Cost: one lane walks one line, so a launch is a chain of 2 W (rows) or 2 H (columns) dependent steps and is bound by that
+ *   chain, not by its 4 B/pixel of traffic: iterations x 4000 steps at 1280x720. Not measured yet (python
+ *   tools/spatial_filter_probe.py 200 20 is the measurement); the estimate from the kernels' instruction counts, about 35 ns per
+ *   step and so about 150 us per iteration at 8 x 1280x720, is in DESIGN.md section 10 (f7). It pays after a decimation.         */
+typedef struct pcs_spatial_filter_config {
+    float   alpha;         /* (0,1]; default 0.5 */
+    int32_t delta;         /* 1..65535 Z16 units; default 20 */
+    int32_t iterations;    /* 1..5; default 2 */
+    int32_t hole_radius;   /* 0..65535 pixels filled per gap and direction in the row passes; default 0 (off) */
+} pcs_spatial_filter_config;
+int pcs_spatial_filter_depth_device(pcs_ctx* ctx, const pcs_spatial_filter_config* cfg, const uint16_t* const* d_in,
+                                    uint16_t* const* d_out);
+int pcs_spatial_filter_depth(pcs_ctx* ctx, const pcs_spatial_filter_config* cfg, const uint16_t* const* in, uint16_t* const* out);
+
 /* Throughput form: n_sets frame-sets of the SAME streams per call. d_depth / d_color hold n_sets * n_streams device
  * pointers, frame-set major (entry k*n_streams + s = stream s of frame-set k); d_payload[k] is frame-set k's payload
  * pointer (each with payload_shorts capacity), d_counts (optional) n_sets pointers as in pcs_process_frames_device.

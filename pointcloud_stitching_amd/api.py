@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (CloudDesc, Config, DepthFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (CloudDesc, Config, DepthFilterConfig, SpatialFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -224,6 +224,36 @@ class PcsContext:
         ip = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in d])
         op = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in out])
         self._check(self._lib.pcs_decimate_depth(self._h, int(scale), ws, hs, ip, op))
+        return out
+
+    # -- spatial filter ------------------------------------------------------------------------
+    def spatial_filter_depth_device(self, d_in: Sequence[int], d_out: Sequence[int], *, alpha: float = 0.5, delta: int = 20,
+                                    iterations: int = 2, hole_radius: int = 0) -> None:
+        """pcs_spatial_filter_depth_device on device pointers (ints), asynchronous and stateless: the edge-preserving recurrence
+        along every row and every column of every stream, `iterations` times (2 x iterations launches); d_out[s] may equal d_in[s].
+        The rasters have this context's depth sizes. The definition: DESIGN.md section 3."""
+        if len(d_in) != self.n_streams or len(d_out) != self.n_streams:
+            raise ValueError("need one input and one output pointer per stream")
+        cfg = SpatialFilterConfig(float(alpha), int(delta), int(iterations), int(hole_radius))
+        ip = (C.c_void_p * self.n_streams)(*d_in)
+        op = (C.c_void_p * self.n_streams)(*d_out)
+        self._check(self._lib.pcs_spatial_filter_depth_device(self._h, C.byref(cfg), ip, op))
+
+    def spatial_filter_depth(self, depth: Sequence[np.ndarray], *, alpha: float = 0.5, delta: int = 20, iterations: int = 2,
+                             hole_radius: int = 0) -> List[np.ndarray]:
+        """pcs_spatial_filter_depth: one frame-set of Z16 rasters through the spatial filter (upload, launches, download); returns
+        new arrays of the inputs' shapes."""
+        if len(depth) != self.n_streams:
+            raise ValueError("need one depth raster per stream")
+        d = [np.ascontiguousarray(x, np.uint16) for x in depth]
+        for s in range(self.n_streams):
+            if d[s].size != self.streams[s].n_points:
+                raise ValueError(f"stream {s}: depth raster has {d[s].size} pixels, expected {self.streams[s].n_points}")
+        cfg = SpatialFilterConfig(float(alpha), int(delta), int(iterations), int(hole_radius))
+        out = [np.empty_like(x) for x in d]
+        ip = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in d])
+        op = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in out])
+        self._check(self._lib.pcs_spatial_filter_depth(self._h, C.byref(cfg), ip, op))
         return out
 
     # -- a2 twin -----------------------------------------------------------------------------

@@ -14,6 +14,9 @@
 //               -D <n> (depth decimation on the GPU, ahead of -F as in librealsense's chain: every n x n block of the Z16 raster to
 //                  one pixel, median of the valid for n = 2, 3, mean of the valid for n = 4..8; 1 = off; pcs_decimate_depth. The
 //                  definition is this project's own; parity with librealsense unpinned)
+//               -S <alpha:delta:iterations[:radius] | default> (spatial edge-preserving filter on the GPU, after -D and ahead of -F as in
+//                  librealsense's chain: a recursive smoother along every row and column that stops at depth steps larger than delta;
+//                  pcs_spatial_filter_depth. This project's own definition; parity with librealsense unpinned)
 //
 //   -f takes "synth:<W>x<H>" (deterministic synthetic frames; the reference's bags are LFS stubs and
 //   need librealsense), a .pcsraw dump (see pointcloud_stitching_amd/synthetic.py: write_pcsraw) or a
@@ -37,6 +40,7 @@
 #include "pcs_cropbox.h"
 #include "pcs_decimate.h"
 #include "pcs_depthfilter.h"
+#include "pcs_spatialfilter.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
 
@@ -54,6 +58,8 @@ static int16_t crop_lo[3], crop_hi[3];
 static bool depth_filter = false;
 static pcs_depth_filter_config filter_cfg;
 static int decimate = 1;
+static bool spatial_filter = false;
+static pcs_spatial_filter_config spatial_cfg;
 static int client_sock = 0, sockfd = 0;
 
 static void print_usage()
@@ -78,6 +84,10 @@ static void print_usage()
            "  -D <n>    depth decimation on the GPU, inside the timed region and ahead of -F: every n x n block of the depth raster to one\n"
            "            pixel (n = 2, 3: median of the valid pixels; n = 4..8: their mean; 1 = off); everything downstream sees the\n"
            "            smaller cloud, the colour image stays as it is\n"
+           "  -S <alpha:delta:iterations[:radius] | default>  spatial edge-preserving depth filter on the GPU, inside the timed region,\n"
+           "            after -D and ahead of -F: every row and every column is smoothed recursively in both directions, `iterations`\n"
+           "            times; a step between neighbours larger than delta (Z16 units) is kept as an edge; radius > 0 also fills up to\n"
+           "            that many zero pixels per gap and direction along the rows (default = 0.5:20:2, no fill)\n"
            "  -M        hand the frames over in ordinary pageable memory, as librealsense owns them in the reference's timed region\n"
            "            (:291-293): uploads are staged then. Default: frames copied to page-locked rasters BEFORE the timer starts\n"
            "            (zero copy) - the printed times then belong to a capture pipeline that delivers page-locked frames\n\n");
@@ -86,7 +96,7 @@ static void print_usage()
 static void parseArgs(int argc, char** argv)
 {
     int c;
-    while ((c = getopt(argc, argv, "hf:vst:cmzg:n:d:iCr:o:p:e:PHMB:F:D:")) != -1) {
+    while ((c = getopt(argc, argv, "hf:vst:cmzg:n:d:iCr:o:p:e:PHMB:F:D:S:")) != -1) {
         switch (c) {
             case 'h': print_usage(); exit(0);
             case 'f': filename = optarg; break;
@@ -123,6 +133,12 @@ static void parseArgs(int argc, char** argv)
             case 'D': {
                 std::string why;
                 if (!pcs_decimate::parse(optarg, decimate, why)) { std::cerr << "-D " << optarg << ": " << why << std::endl; exit(2); }
+                break;
+            }
+            case 'S': {
+                std::string why;
+                if (!pcs_spatialfilter::parse(optarg, spatial_cfg, why)) { std::cerr << "-S " << optarg << ": " << why << std::endl; exit(2); }
+                spatial_filter = true;
                 break;
             }
             default: print_usage(); exit(2);
@@ -276,7 +292,7 @@ int main(int argc, char** argv)
         std::cerr << pcs_last_error(ctx) << std::endl; return 1;
     }
     std::vector<const uint16_t*> dptr(n_streams);
-    std::vector<uint16_t*> fptr(n_streams);           // -F: the same rasters, filtered in place
+    std::vector<uint16_t*> fptr(n_streams);           // -S, -F: the same rasters, filtered in place
     std::vector<const uint8_t*> cptr(n_streams);
     std::vector<int> counts(n_streams);
     pcs_kernel_timing(ctx, 1);
@@ -333,6 +349,9 @@ int main(int argc, char** argv)
         auto time_start = clockTime::now();                                   // :291
         if (decimate > 1 && (rc = pcs_decimate_depth(ctx, decimate, src_w.data(), src_h.data(), sptr.data(), fptr.data())) != PCS_OK) {
             std::cerr << "pcs_decimate_depth: " << pcs_last_error(ctx) << std::endl; return 1;
+        }
+        if (spatial_filter && (rc = pcs_spatial_filter_depth(ctx, &spatial_cfg, dptr.data(), fptr.data())) != PCS_OK) {
+            std::cerr << "pcs_spatial_filter_depth: " << pcs_last_error(ctx) << std::endl; return 1;
         }
         if (depth_filter && (rc = pcs_filter_depth(ctx, dptr.data(), fptr.data())) != PCS_OK) {
             std::cerr << "pcs_filter_depth: " << pcs_last_error(ctx) << std::endl; return 1;

@@ -1041,6 +1041,88 @@ int pcs_decimate_depth(pcs_ctx* c, int scale, const int32_t* src_width, const in
     return rc;
 }
 
+// ---- spatial filter ------------------------------------------------------------------------------
+namespace {
+
+// The one place that decides a spatial call: the configuration's ranges, then the kernels' constants (a, oma rounded once, here).
+int spatial_constants(pcs_ctx* c, const char* name, const pcs_spatial_filter_config* cfg, SpatialArgs& sa)
+{
+    if (!cfg) return fail(c, PCS_ERR_INVALID_ARG, "%s: NULL config", name);
+    if (!(cfg->alpha > 0.0f && cfg->alpha <= 1.0f)) return fail(c, PCS_ERR_INVALID_ARG, "%s: alpha %g is outside (0, 1]", name, (double)cfg->alpha);
+    if (cfg->delta < 1 || cfg->delta > 65535) return fail(c, PCS_ERR_INVALID_ARG, "%s: delta %d is outside 1..65535", name, cfg->delta);
+    if (cfg->iterations < 1 || cfg->iterations > 5) return fail(c, PCS_ERR_INVALID_ARG, "%s: iterations %d is outside 1..5", name, cfg->iterations);
+    if (cfg->hole_radius < 0 || cfg->hole_radius > 65535)
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: hole_radius %d is outside 0..65535", name, cfg->hole_radius);
+    sa.a = cfg->alpha;
+    sa.oma = 1.0f - sa.a;
+    sa.delta = (float)cfg->delta;
+    sa.radius = (uint32_t)cfg->hole_radius;
+    return PCS_OK;
+}
+
+}  // namespace
+
+int pcs_spatial_filter_depth_device(pcs_ctx* c, const pcs_spatial_filter_config* cfg, const uint16_t* const* d_in, uint16_t* const* d_out)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    const char* name = "pcs_spatial_filter_depth_device";
+    SpatialArgs sa{};
+    if (int rc = spatial_constants(c, name, cfg, sa)) return rc;
+    if (!d_in || !d_out) return fail(c, PCS_ERR_INVALID_ARG, "%s: NULL pointer", name);
+    uint32_t max_w = 0, max_rows = 0;
+    for (int s = 0; s < c->n_streams; s++) {
+        const StreamParams& P = c->h_params[s];
+        if (!d_in[s]) return fail(c, PCS_ERR_INVALID_ARG, "%s: stream %d: d_in is NULL", name, s);
+        if (!d_out[s]) return fail(c, PCS_ERR_INVALID_ARG, "%s: stream %d: d_out is NULL", name, s);
+        if ((uintptr_t)d_in[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "%s: stream %d: d_in is not 2-byte aligned", name, s);
+        if ((uintptr_t)d_out[s] & 1u) return fail(c, PCS_ERR_INVALID_ARG, "%s: stream %d: d_out is not 2-byte aligned", name, s);
+        sa.in[s] = d_in[s]; sa.out[s] = d_out[s];
+        sa.W[s] = (uint32_t)P.W; sa.H[s] = (uint32_t)P.H;
+        max_w = std::max(max_w, (uint32_t)P.W); max_rows = std::max(max_rows, (uint32_t)P.H);
+    }
+    // an output may be its own stream's input (in place); any other byte shared with an input is refused: the launches after the
+    // first run in place on the outputs, so a neighbour's input would be read half filtered
+    for (int s = 0; s < c->n_streams; s++) {
+        const uintptr_t o0 = (uintptr_t)d_out[s], o1 = o0 + (size_t)c->h_params[s].n_points * sizeof(uint16_t);
+        for (int t = 0; t < c->n_streams; t++) {
+            const uintptr_t i0 = (uintptr_t)d_in[t], i1 = i0 + (size_t)c->h_params[t].n_points * sizeof(uint16_t);
+            if (o0 < i1 && i0 < o1 && !(s == t && o0 == i0))
+                return fail(c, PCS_ERR_INVALID_ARG, "%s: stream %d: d_out overlaps d_in of stream %d (only d_out[s] == d_in[s] may share bytes)",
+                            name, s, t);
+        }
+    }
+    DeviceGuard guard(c->device);
+    HIPCHK(c, launch_spatial_filter(c->n_streams, cfg->iterations, max_rows, max_w, sa, c->stream));
+    return PCS_OK;
+}
+
+int pcs_spatial_filter_depth(pcs_ctx* c, const pcs_spatial_filter_config* cfg, const uint16_t* const* in, uint16_t* const* out)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    const char* name = "pcs_spatial_filter_depth";
+    SpatialArgs unused{};
+    int rc;
+    if ((rc = spatial_constants(c, name, cfg, unused))) return rc;
+    if (!in || !out) return fail(c, PCS_ERR_INVALID_ARG, "%s: NULL pointer", name);
+    for (int s = 0; s < c->n_streams; s++)
+        if (!in[s] || !out[s]) return fail(c, PCS_ERR_INVALID_ARG, "%s: stream %d: NULL raster pointer", name, s);
+    DeviceGuard guard(c->device);
+    if ((rc = ensure_rasters(c))) return rc;
+    // From the first copy on the caller's rasters are in use by the stream: every failure below leaves through the one synchronise.
+    const auto run = [&]() -> int {
+        for (int s = 0; s < c->n_streams; s++)
+            HIPCHK(c, hipMemcpyAsync(c->s_depth[s], in[s], (size_t)c->h_params[s].n_points * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        if (int r = pcs_spatial_filter_depth_device(c, cfg, c->s_depth.data(), c->s_depth.data())) return r;
+        for (int s = 0; s < c->n_streams; s++)
+            HIPCHK(c, hipMemcpyAsync(out[s], c->s_depth[s], (size_t)c->h_params[s].n_points * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+        return PCS_OK;
+    };
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == PCS_OK && e != hipSuccess) rc = fail(c, PCS_ERR_HIP, "%s: hipStreamSynchronize failed: %s", name, hipGetErrorString(e));
+    return rc;
+}
+
 int pcs_stream_points(const pcs_ctx* c, int stream)
 {
     if (!c || stream < 0 || stream >= c->n_streams) return PCS_ERR_INVALID_ARG;

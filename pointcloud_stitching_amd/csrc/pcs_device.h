@@ -322,6 +322,22 @@ struct DecimArgs {
 // max_rows / max_width: the tallest and the widest OUTPUT raster of the launch. scale outside 2..8 is hipErrorInvalidValue.
 hipError_t launch_decimate_depth(int scale, int n_streams, uint32_t max_rows, uint32_t max_width, const DecimArgs& da, hipStream_t st);
 
+// Spatial filter (pcs_spatial_filter_depth_device, pcs_kernels_filter.hip): the edge-preserving recurrence along every row (both
+// directions, with the bounded hole fill) and then along every column (both directions), `iterations` times: 2 x iterations launches,
+// each over every stream of a context (blockIdx.y = stream), one lane per line. The first row launch reads in[] and writes out[];
+// every later launch runs in place on out[] (in[s] == out[s] is allowed). Stateless, like the decimation: the per-call table travels in
+// the kernels' arguments (1552 bytes), nothing is uploaded, nothing is stored in the context.
+struct SpatialArgs {
+    const uint16_t* in[PCS_MAX_STREAMS];
+    uint16_t*       out[PCS_MAX_STREAMS];
+    uint32_t        W[PCS_MAX_STREAMS], H[PCS_MAX_STREAMS];
+    float           a, oma;                    // (float)alpha and 1.0f - a, each rounded once on the host
+    float           delta;                     // 1..65535, exact in fp32: the recurrence compares in floats
+    uint32_t        radius;                    // hole_radius: pixels filled per gap and direction in the row passes (0: none)
+};
+// max_rows / max_width: the tallest and the widest raster of the launch. iterations < 1 is hipErrorInvalidValue.
+hipError_t launch_spatial_filter(int n_streams, int iterations, uint32_t max_rows, uint32_t max_width, const SpatialArgs& sa, hipStream_t st);
+
 // a7 with stride.
 hipError_t launch_stitch(const int16_t* d_src, uint32_t src_points, int downsample,
                          int16_t* d_dst, hipStream_t st);

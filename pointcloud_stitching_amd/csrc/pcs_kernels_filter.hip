@@ -387,4 +387,241 @@ hipError_t launch_decimate_depth(int scale, int n_streams, uint32_t max_rows, ui
     return hipGetLastError();
 }
 
+// ---- spatial filter (pcs_spatial_filter_depth_device) ------------------------------------------------------------------------------
+// DESIGN.md §3 "Spatial filter": an edge-preserving recursive smoother that is a recurrence along ONE line at a time - every row left
+// to right and right to left (with the bounded hole fill), then every column down and up, `iterations` times. This project's own
+// definition (modelled on librealsense's spatial filter, parity with librealsense unpinned); tests/np_spatial_filter.py restates it.
+//
+// Shape: one lane owns one line and walks it in both directions, so in place is safe (a lane reads and writes its own line only; the
+// second direction reads what the same lane stored, in program order). A workgroup is one wave: 8 x 720p is about 90 row waves and 160
+// column waves for 1024 SIMDs, so single waves spread furthest, and with a SIMD to itself a wave issues one vector instruction every
+// four cycles whether or not it depends on the one before - a pass costs (instructions per step) x 4 cycles x (2 x line length), and
+// the only lever is the instruction count of the step. The recurrence stays in fp32 (every Z16 value, difference and rounded blend is
+// an exact float): compares, blend and floor never leave the float pipe; values are converted once when they are unpacked and once
+// when they are packed.
+//   rows     a lane's row is contiguous: it takes 8 pixels per 16-byte load / store when the width is a multiple of 8 and both rasters
+//            are 16-byte aligned (every row segment is then aligned), 2-byte accesses otherwise. The 64 lanes of a load touch 64
+//            different 128-byte lines, each line serves 8 consecutive loads of its lane (64 x 128 B = 8 KiB per wave: it stays in the
+//            vector L1), and kSpatialRowAhead chunks are requested ahead of the walk, so the walk never waits on them. No LDS: staging
+//            128-byte segments through LDS coalesces the global accesses but costs two LDS instructions per pixel and direction in the
+//            one instruction stream that is the bottleneck.
+//   columns  lane = column, so every access of a wave is one coalesced 128-byte row segment; 2-byte accesses always (any width, any
+//            2-byte alignment), kSpatialColAhead rows requested ahead of the walk.
+// A line's first pixel needs no special case: from the state (v0 = 0, nothing filled) a step leaves any pixel as it is and takes it
+// as v0.
+namespace {
+
+constexpr int kSpatialRowAhead = 4;           // 8-pixel chunks of a row in flight ahead of the walk
+constexpr int kSpatialColAhead = 32;          // rows of a column in flight ahead of the walk
+
+struct SpatialConst { float a, oma, delta; uint32_t radius; };
+
+// One step of a line pass: v1 is the pixel, (v0, left) the state; returns what the pixel becomes.
+//   blend   v0, v1 valid and 1 <= |v1 - v0| <= delta: fl(fl(fl(a v1) + fl(oma v0)) + 0.5f), truncated - floorf for these positive
+//           values. The definition's min(.., 65535) cannot fire: a + oma <= 1 + 2^-25, two rounded products and a rounded sum of
+//           values <= 65535 stay below 65535.01, plus 0.5f below 65536 - so it is not computed. A blend is never 0 either (it is at
+//           least (1 - 2^-23) min(v0, v1) + 0.5, truncated), so "v1 is 0" after the blend is "the pixel was 0".
+//   fill    (rows only) the pixel is 0, v0 is valid and fewer than `radius` pixels of this gap were filled: it takes v0.
+template <bool FILL>
+__device__ __forceinline__ float spatial_step(float v1, float& v0, uint32_t& left, const SpatialConst& k)
+{
+    const float d = fabsf(__fsub_rn(v1, v0));
+    // v0, v1 and d are non-negative whole numbers: all three are >= 1 exactly when their minimum is not 0
+    const bool blend = fminf(fminf(v0, v1), d) != 0.0f && d <= k.delta;
+    // two rounded multiplies and two rounded adds: no FMA
+    const float f = __fadd_rn(__fmul_rn(k.a, v1), __fmul_rn(k.oma, v0));
+    float r = blend ? floorf(__fadd_rn(f, 0.5f)) : v1;
+    if (FILL) {
+        // left: how many more pixels the gap at hand may take - hole_radius - run while v0 is valid, 0 before a line's first valid
+        // pixel and once a gap was left open (v0 is 0 from there to the next valid pixel), so "v0 != 0 and run < hole_radius" is
+        // "left != 0"
+        const bool valid = v1 != 0.0f;
+        const bool fill = !valid && left != 0u;
+        left = valid ? k.radius : left - (fill ? 1u : 0u);
+        r = fill ? v0 : r;
+    }
+    v0 = r;
+    return r;
+}
+
+// 8 consecutive pixels of a row as four packed words. VEC: one aligned 16-byte access; otherwise the first n (1..8) pixels by 2-byte
+// accesses (the words' other halves are zero on a load and ignored on a store). FULL: n is 8, nothing is tested.
+template <bool VEC, bool FULL>
+__device__ __forceinline__ void load_px8(const uint16_t* p, uint32_t n, uint32_t (&w)[4])
+{
+    if (VEC) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t lo = (FULL || (uint32_t)(2 * q) < n) ? p[2 * q] : 0u;
+            const uint32_t hi = (FULL || (uint32_t)(2 * q + 1) < n) ? p[2 * q + 1] : 0u;
+            w[q] = lo | hi << 16;
+        }
+    }
+}
+template <bool VEC, bool FULL>
+__device__ __forceinline__ void store_px8(uint16_t* p, uint32_t n, const uint32_t (&w)[4])
+{
+    if (VEC) {
+        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            if (FULL || (uint32_t)j < n) p[j] = (uint16_t)((j & 1) ? w[j >> 1] >> 16 : w[j >> 1] & 0xFFFFu);
+    }
+}
+
+// The n (FULL: 8) pixels of one chunk through the recurrence, from the first (forward) or from the last (BACK); packed in, packed out.
+template <bool BACK, bool FULL>
+__device__ __forceinline__ void spatial_walk8(uint32_t (&w)[4], uint32_t n, float& v0, uint32_t& left, const SpatialConst& k)
+{
+    float x[8];
+#pragma unroll
+    for (int q = 0; q < 4; q++) { x[2 * q] = (float)(w[q] & 0xFFFFu); x[2 * q + 1] = (float)(w[q] >> 16); }
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        const int p = BACK ? 7 - t : t;
+        if (FULL || (uint32_t)p < n) x[p] = spatial_step<true>(x[p], v0, left, k);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) w[q] = (uint32_t)x[2 * q] | (uint32_t)x[2 * q + 1] << 16;
+}
+
+// One direction over one row. Chunk i of the sweep is 8 i pixels from the row's start (forward) or from its end (BACK), so the one
+// short chunk of a ragged row (VEC: there is none) is always the last of the sweep. src may be dst: a chunk is requested
+// kSpatialRowAhead chunks before it is walked and stored, and no chunk is requested twice. The main loop runs while the chunks walked
+// AND the chunks requested are whole ones: neither it nor the requests ahead of it have a condition in them, so the compiler's wait
+// counts leave the requests in flight (with a conditional load anywhere on the way in, it waits for all of them at the top of the
+// loop); the tail loop (fewer than 2 kSpatialRowAhead chunks) tests everything. Every condition is the same for all lanes of the
+// wave (one stream, one width).
+template <bool BACK, bool VEC>
+__device__ __forceinline__ void spatial_sweep_row(const uint16_t* src, uint16_t* dst, uint32_t W, const SpatialConst& k)
+{
+    constexpr uint32_t K = kSpatialRowAhead;
+    const uint32_t nch = (W + 7u) >> 3, nfull = W >> 3;
+    const auto col_of = [&](uint32_t i) { return BACK ? (W >= 8u * (i + 1u) ? W - 8u * (i + 1u) : 0u) : 8u * i; };
+    const auto n_of = [&](uint32_t i) { return min(8u, W - 8u * i); };
+    uint32_t ring[K][4];
+    float v0 = 0.0f;
+    uint32_t left = 0;
+    uint32_t i0 = 0;
+    if (2u * K <= nfull) {
+#pragma unroll
+        for (uint32_t j = 0; j < K; j++) load_px8<VEC, true>(src + col_of(j), 8u, ring[j]);
+        for (; i0 + 2u * K <= nfull; i0 += K) {
+#pragma unroll
+            for (uint32_t j = 0; j < K; j++) {
+                spatial_walk8<BACK, true>(ring[j], 8u, v0, left, k);
+                store_px8<VEC, true>(dst + col_of(i0 + j), 8u, ring[j]);
+                load_px8<VEC, true>(src + col_of(i0 + j + K), 8u, ring[j]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < K; j++) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) ring[j][q] = 0;
+            if (j < nch) load_px8<VEC, false>(src + col_of(j), n_of(j), ring[j]);
+        }
+    }
+    for (; i0 < nch; i0 += K) {
+#pragma unroll
+        for (uint32_t j = 0; j < K; j++) {
+            const uint32_t i = i0 + j;
+            if (i >= nch) break;
+            spatial_walk8<BACK, false>(ring[j], n_of(i), v0, left, k);
+            store_px8<VEC, false>(dst + col_of(i), n_of(i), ring[j]);
+            if (i + K < nch) load_px8<VEC, false>(src + col_of(i + K), n_of(i + K), ring[j]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64)
+void pcs_spatial_rows_kernel(SpatialArgs sa)
+{
+    const int s = blockIdx.y;
+    const uint32_t W = sa.W[s];
+    const uint32_t r = blockIdx.x * 64u + threadIdx.x;
+    if (r >= sa.H[s]) return;                                   // (no barrier anywhere: lanes past the last row just leave)
+    const SpatialConst k{sa.a, sa.oma, sa.delta, sa.radius};
+    const size_t row0 = (size_t)r * W;
+    const uint16_t* in = sa.in[s] + row0;
+    uint16_t* out = sa.out[s] + row0;
+    if ((W & 7u) == 0 && ((((uintptr_t)sa.in[s]) | ((uintptr_t)sa.out[s])) & 15u) == 0) {
+        spatial_sweep_row<false, true>(in, out, W, k);
+        spatial_sweep_row<true, true>(out, out, W, k);
+    } else {
+        spatial_sweep_row<false, false>(in, out, W, k);
+        spatial_sweep_row<true, false>(out, out, W, k);
+    }
+}
+
+// One direction over one column: row i of the sweep is raster row i (down) or H - 1 - i (BACK). Byte offsets from the raster's base
+// fit 32 bits (a context's raster has fewer than 2^31 pixels), so the base stays scalar and a step's address is one 32-bit add. Main
+// loop and tail loop as in the row sweep.
+template <bool BACK>
+__device__ __forceinline__ void spatial_sweep_col(uint16_t* x, uint32_t W, uint32_t H, uint32_t c, const SpatialConst& k)
+{
+    constexpr uint32_t K = kSpatialColAhead;
+    const auto off_of = [&](uint32_t i) { return ((BACK ? H - 1u - i : i) * W + c) * 2u; };
+    const auto px = [&](uint32_t off) -> uint16_t& { return *reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(x) + off); };
+    uint32_t ring[K];
+    float v0 = 0.0f;
+    uint32_t left = 0;
+    uint32_t i0 = 0;
+    if (2u * K <= H) {
+#pragma unroll
+        for (uint32_t j = 0; j < K; j++) ring[j] = px(off_of(j));
+        for (; i0 + 2u * K <= H; i0 += K) {
+#pragma unroll
+            for (uint32_t j = 0; j < K; j++) {
+                px(off_of(i0 + j)) = (uint16_t)(uint32_t)spatial_step<false>((float)ring[j], v0, left, k);
+                ring[j] = px(off_of(i0 + j + K));
+            }
+        }
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < K; j++) ring[j] = j < H ? px(off_of(j)) : 0u;
+    }
+    for (; i0 < H; i0 += K) {
+#pragma unroll
+        for (uint32_t j = 0; j < K; j++) {
+            const uint32_t i = i0 + j;
+            if (i >= H) break;
+            px(off_of(i)) = (uint16_t)(uint32_t)spatial_step<false>((float)ring[j], v0, left, k);
+            if (i + K < H) ring[j] = px(off_of(i + K));
+        }
+    }
+}
+
+__global__ __launch_bounds__(64)
+void pcs_spatial_cols_kernel(SpatialArgs sa)
+{
+    const int s = blockIdx.y;
+    const uint32_t W = sa.W[s], H = sa.H[s];
+    const uint32_t c = blockIdx.x * 64u + threadIdx.x;
+    if (c >= W) return;
+    const SpatialConst k{sa.a, sa.oma, sa.delta, sa.radius};
+    spatial_sweep_col<false>(sa.out[s], W, H, c, k);            // (the column launches always run in place on the output)
+    spatial_sweep_col<true>(sa.out[s], W, H, c, k);
+}
+
+}  // namespace
+
+hipError_t launch_spatial_filter(int n_streams, int iterations, uint32_t max_rows, uint32_t max_width, const SpatialArgs& sa, hipStream_t st)
+{
+    if (n_streams < 0 || n_streams > PCS_MAX_STREAMS || iterations < 1) return hipErrorInvalidValue;
+    if (n_streams == 0 || max_rows == 0 || max_width == 0) return hipSuccess;
+    const dim3 block(64), row_grid((max_rows + 63u) / 64u, (unsigned)n_streams), col_grid((max_width + 63u) / 64u, (unsigned)n_streams);
+    SpatialArgs in_place = sa;
+    for (int s = 0; s < n_streams; s++) in_place.in[s] = sa.out[s];
+    for (int it = 0; it < iterations; it++) {
+        hipLaunchKernelGGL(pcs_spatial_rows_kernel, row_grid, block, 0, st, it == 0 ? sa : in_place);
+        hipLaunchKernelGGL(pcs_spatial_cols_kernel, col_grid, block, 0, st, in_place);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace pcs

@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import CloudDesc, Config, DepthFilterConfig, PayloadDesc, StreamConfig
+from .types import CloudDesc, Config, DepthFilterConfig, PayloadDesc, SpatialFilterConfig, StreamConfig
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -54,6 +54,8 @@ SYMBOLS = [
     ("pcs_decimated_stream_config", C.c_int, [_P(StreamConfig), C.c_int, _P(StreamConfig)]),
     ("pcs_decimate_depth_device", C.c_int, [_VP, C.c_int, _P(C.c_int32), _P(C.c_int32), _P(_VP), _P(_VP)]),
     ("pcs_decimate_depth", C.c_int, [_VP, C.c_int, _P(C.c_int32), _P(C.c_int32), _P(_VP), _P(_VP)]),
+    ("pcs_spatial_filter_depth_device", C.c_int, [_VP, _P(SpatialFilterConfig), _P(_VP), _P(_VP)]),
+    ("pcs_spatial_filter_depth", C.c_int, [_VP, _P(SpatialFilterConfig), _P(_VP), _P(_VP)]),
     ("pcs_process_frames_device_batch", C.c_int, [_VP, C.c_int, _P(_VP), _P(_VP), _P(_VP), C.c_size_t, _P(_VP)]),
     ("pcs_submit_frames", C.c_int, [_VP, _P(_VP), _P(_VP), _P(C.c_int)]),
     ("pcs_collect_frames", C.c_int, [_VP, C.c_int, _VP, C.c_size_t, C.c_int, _P(C.c_int), _P(C.c_int)]),

@@ -86,6 +86,11 @@ class DepthFilterConfig(C.Structure):
                 ("persistence", C.c_int32), ("hole_fill", C.c_int32)]
 
 
+class SpatialFilterConfig(C.Structure):
+    """pcs_spatial_filter_config: the spatial filter's parameters; they travel with every call (nothing is set in the context)."""
+    _fields_ = [("alpha", C.c_float), ("delta", C.c_int32), ("iterations", C.c_int32), ("hole_radius", C.c_int32)]
+
+
 # --- the reference's surveyed extrinsics (data, not code) -------------------------------------
 # src/pcs-camera-optimized.cpp:64-67
 TF_MAT = np.array([
