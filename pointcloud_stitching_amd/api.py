@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (CloudDesc, Config, DepthFilterConfig, SpatialFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (CloudDesc, CompressedInfo, Config, DepthFilterConfig, SpatialFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -37,6 +37,24 @@ def _ptr(a: np.ndarray) -> int:
     if not a.flags["C_CONTIGUOUS"]:
         raise ValueError("array must be C-contiguous")
     return a.ctypes.data
+
+
+def compressed_bound(n_points: int) -> int:
+    """pcs_compressed_bound: the largest "PCZ1" container of n_points records (16 + 660 ceil(n / 64))."""
+    return int(_libmod.load().pcs_compressed_bound(int(n_points)))
+
+
+def compressed_info(container) -> CompressedInfo:
+    """pcs_compressed_info: validate a container (bytes or a uint8 array) on the host — no context, no GPU. Raises PcsError
+    (PCS_ERR_INVALID_ARG) whose text names the first violation."""
+    lib = _libmod.load()
+    buf = np.ascontiguousarray(np.frombuffer(container, np.uint8) if isinstance(container, (bytes, bytearray)) else container)
+    info = CompressedInfo()
+    rc = lib.pcs_compressed_info(buf.ctypes.data if buf.nbytes else None, buf.nbytes, C.byref(info))
+    if rc != 0:
+        d = lib.pcs_last_error(None)
+        raise PcsError(rc, d.decode() if d else "")
+    return info
 
 
 class PcsContext:
@@ -317,6 +335,44 @@ class PcsContext:
         self._check(self._lib.pcs_process_frames(self._h, dp, cp, _ptr(buf), buf.size, int(write_header),
                                                  counts, C.byref(size)))
         return buf, [int(x) for x in counts], size.value
+
+    def process_frames_compressed(self, depth: Sequence[np.ndarray], color: Sequence[np.ndarray],
+                                  write_header: bool = True, out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, List[int], int]:
+        """process_frames with the payload compressed on the device ("PCZ1", pcs_process_frames_compressed): returns (uint8 buffer:
+        int32 container bytes, then the container at byte 4; per-stream point counts; container bytes)."""
+        if len(depth) != self.n_streams or len(color) != self.n_streams:
+            raise ValueError("need one depth and one colour raster per stream")
+        d = [np.ascontiguousarray(x, np.uint16).reshape(-1) for x in depth]
+        c = [np.ascontiguousarray(x, np.uint8).reshape(-1) for x in color]
+        for s in range(self.n_streams):
+            if d[s].size != self.streams[s].n_points or c[s].size < self.streams[s].color_bytes:
+                raise ValueError(f"stream {s}: raster size mismatch")
+        dp = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in d])
+        cp = (C.c_void_p * self.n_streams)(*[_ptr(x) for x in c])
+        buf = out if out is not None else np.zeros(4 + compressed_bound(self.max_payload_shorts // POINT_SHORTS), np.uint8)
+        if buf.dtype != np.uint8 or not buf.flags["C_CONTIGUOUS"]:
+            raise ValueError("out must be a contiguous uint8 array")
+        counts = (C.c_int * self.n_streams)()
+        size = C.c_int(0)
+        self._check(self._lib.pcs_process_frames_compressed(self._h, dp, cp, _ptr(buf), buf.size, int(write_header),
+                                                            counts, C.byref(size)))
+        return buf, [int(x) for x in counts], size.value
+
+    # -- payload codec ("PCZ1") ------------------------------------------------------------------
+    def compress_payload_device(self, d_payload: int, n_points: int, d_out: int, out_capacity: int, d_out_bytes: int = 0) -> None:
+        """Asynchronous; see pcs_compress_payload_device. Device pointers as ints."""
+        self._check(self._lib.pcs_compress_payload_device(self._h, d_payload or None, n_points, d_out, out_capacity, d_out_bytes or None))
+
+    def decompress_payload_device(self, d_in: int, in_bytes: int, n_points: int, d_payload: int, payload_shorts: int) -> None:
+        """Asynchronous; the caller vouches for the container (compressed_info accepted it). See pcs_decompress_payload_device."""
+        self._check(self._lib.pcs_decompress_payload_device(self._h, d_in, in_bytes, n_points, d_payload or None, payload_shorts))
+
+    def decompress_payload(self, container, d_payload: int, payload_shorts: int) -> int:
+        """Validate a container held in host memory, upload it and decode it into d_payload; returns the record count."""
+        buf = np.ascontiguousarray(np.frombuffer(container, np.uint8) if isinstance(container, (bytes, bytearray)) else container)
+        n = C.c_int(0)
+        self._check(self._lib.pcs_decompress_payload(self._h, _ptr(buf), buf.nbytes, d_payload or None, payload_shorts, C.byref(n)))
+        return n.value
 
     def submit_frames(self, depth: Sequence[np.ndarray], color: Sequence[np.ndarray]) -> int:
         """Queue one frame-set (uploads + kernel) and return its ticket; see pcs_submit_frames. The arrays must be

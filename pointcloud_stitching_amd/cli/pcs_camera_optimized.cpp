@@ -3,6 +3,9 @@
 // timing, stdout lines and the TCP push are kept; the per-frame work goes through the C ABI.
 //
 //   reference flags (getopt "hf:vst:cmz", :122):  -h  -f <file>  -v  -s  -t <n>  -c  -m  -z
+//     -z is a TODO in the reference (its snappy call is commented out, :145-147, 333-337, 699-709); here it compresses the stitched
+//     payload on the GPU, losslessly (pcs_process_frames_compressed, the PCZ1 container of DESIGN.md section 4): what -s / -P send
+//     and -o dumps is [int32 container bytes][container], and the summary's byte figures are the container's
 //   additions:  -g <dev>  -n <streams>  -d <stride>  -i (drop invalid depth)  -C (-c without the reference's lane quirk)
 //               -r <frames>  -o <file> (dump last stitched buffer)  -p <port>
 //               -e <file> (camera-to-world matrices instead of the ones pasted into the reference's sources)
@@ -74,6 +77,8 @@ static void print_usage()
            "            without -m, the default loop's -c: z != 0, x != 0, z <= 1.5, nothing compacted (a skipped point is a zero record)\n"
            "  -i        drop invalid-depth pixels   -d <n> keep every n-th point   -n <N> camera streams\n"
            "  -g <dev>  GPU ordinal   -r <frames>   -o <file> dump last stitched buffer   -p <port>\n"
+           "  -z        compress the payload on the GPU (lossless PCZ1 container, DESIGN.md section 4): -s / -P send and -o dumps\n"
+           "            [int32 container bytes][container]; the centre decodes it with its own -z\n"
            "  -P        serve frames on 'Z' pull requests (the live server's protocol) instead of pushing them\n"
            "  -e <file> camera-to-world matrices, 16 row-major floats per line (python -m pointcloud_stitching_amd.calibration)\n"
            "  -H        texture coordinates as older librealsense releases: (pixel + 0.5) / size\n"
@@ -291,6 +296,11 @@ int main(int argc, char** argv)
     if (pcs_host_malloc(ctx, (void**)&buffer, sizeof(short) * buf_shorts) != PCS_OK) {   // page-locked: D2H at link speed
         std::cerr << pcs_last_error(ctx) << std::endl; return 1;
     }
+    // -z: what is sent instead, [int32 container bytes][PCZ1 container] (pcs_process_frames_compressed), sized for the worst case
+    const size_t zbuf_bytes = sizeof(int32_t) + pcs_compressed_bound((int)(pcs_max_payload_shorts(ctx) / PCS_POINT_SHORTS));
+    short* zbuffer = nullptr;
+    if (compress && pcs_host_malloc(ctx, (void**)&zbuffer, zbuf_bytes) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+    short* const wire = compress ? zbuffer : buffer;
     std::vector<const uint16_t*> dptr(n_streams);
     std::vector<uint16_t*> fptr(n_streams);           // -S, -F: the same rasters, filtered in place
     std::vector<const uint8_t*> cptr(n_streams);
@@ -356,15 +366,18 @@ int main(int argc, char** argv)
         if (depth_filter && (rc = pcs_filter_depth(ctx, dptr.data(), fptr.data())) != PCS_OK) {
             std::cerr << "pcs_filter_depth: " << pcs_last_error(ctx) << std::endl; return 1;
         }
-        rc = pcs_process_frames(ctx, dptr.data(), cptr.data(), buffer, buf_shorts, send_buffer ? 1 : 0, counts.data(), &buff_size);
+        if (compress)       // the payload stays on the device and is compressed there: buff_size is the container's
+            rc = pcs_process_frames_compressed(ctx, dptr.data(), cptr.data(), zbuffer, zbuf_bytes, 1, counts.data(), &buff_size);
+        else
+            rc = pcs_process_frames(ctx, dptr.data(), cptr.data(), buffer, buf_shorts, send_buffer ? 1 : 0, counts.data(), &buff_size);
         auto time_end = clockTime::now();                                     // :293
-        if (rc != PCS_OK) { std::cerr << "pcs_process_frames: " << pcs_last_error(ctx) << std::endl; return 1; }
+        if (rc != PCS_OK) { std::cerr << (compress ? "pcs_process_frames_compressed: " : "pcs_process_frames: ") << pcs_last_error(ctx) << std::endl; return 1; }
         if (pull_mode) {      // the live server's protocol (:180-184): one 'Z' per frame, anything else is fatal
             int req = pcs_wire::recv_pull(client_sock);
             if (req < 0) { std::cout << "Client disconnected" << std::endl; break; }
             if (req != pcs_wire::kPullXYZRGB) { std::cerr << "Faulty pull request" << std::endl; return 1; }
         }
-        if (send_buffer && !pcs_wire::send_frame(client_sock, buffer, buff_size)) { std::cout << "Client disconnected" << std::endl; break; }   // :719
+        if (send_buffer && !pcs_wire::send_frame(client_sock, wire, buff_size)) { std::cout << "Client disconnected" << std::endl; break; }   // :719
         const double ms = timeMilli(time_end - time_start).count();
         std::cout << "Frame Time: " << ms << " ms " << "FPS: " << 1000.0 / ms
                   << "\t Buffer size: " << float(buff_size) / (1 << 20) << " MBytes" << std::endl;       // :295-297
@@ -424,9 +437,10 @@ int main(int argc, char** argv)
 
     if (dump_path) {
         FILE* f = fopen(dump_path, "wb");
-        if (f) { fwrite(buffer, 1, (size_t)buff_size + 4, f); fclose(f); }
+        if (f) { fwrite(wire, 1, (size_t)buff_size + 4, f); fclose(f); }
     }
     pcs_host_free(ctx, buffer);
+    if (zbuffer) pcs_host_free(ctx, zbuffer);
     for (int s = 0; s < n_streams; s++) { if (pin_d[s]) pcs_host_free(ctx, pin_d[s]); if (pin_c[s]) pcs_host_free(ctx, pin_c[s]); }
     for (int s = 0; !pageable && s < n_streams; s++) if (dec_d[s]) pcs_host_free(ctx, dec_d[s]);
     pcs_destroy(ctx);

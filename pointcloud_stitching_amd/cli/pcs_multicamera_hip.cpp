@@ -36,6 +36,10 @@
 //                      path crops (with -V the cropped payload goes to pcs_voxel_grid_device_counted); with -c the received
 //                      payloads are cropped on the GPU (pcs_crop_payloads_device, after -T if both are given; -d is the crop
 //                      call's stride: every d-th KEPT record per camera). Not with -G: the node library has no setter.
+//              -z      (with -c) the edges run pcs-camera-optimized -z: every frame is a PCZ1 container, validated
+//                      on the host and decoded on the GPU into the camera's device payload (pcs_decompress_payload) ahead of the
+//                      stitch / -T / -B / -V paths, which see what they always saw; a frame that fails validation ends the run with
+//                      the validator's message. What is served on -p stays raw.
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
@@ -60,7 +64,7 @@ typedef std::chrono::duration<double, std::milli> timeMilli;
 
 static bool timer = false, serve = true;
 static int downsample = 1, n_streams = 8, device = 0, serve_port = 9000, max_sets = 30, n_gpus = 0, voxel_leaf = 0;
-static bool drop_invalid = false, pipelined = false;
+static bool drop_invalid = false, pipelined = false, compressed = false;
 static std::vector<int> gpu_ids;
 static int voxel_route = PCS_NODE_VOXEL_PARTIALS;
 static const char* source = nullptr;
@@ -89,6 +93,8 @@ static void usage()
               << "                  as the reference's pcs-multicamera-optimized does (decode, pcl::transformPointCloud, re-encode)\n"
               << " -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box, millimetres in the world frame, inclusive: -i crops in the fused path, -c crops the\n"
               << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
+              << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
+              << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
               << " -s / -v / -n     PCL viewer features of the reference; not available in this build\n";
 }
@@ -97,7 +103,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:z")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -124,6 +130,7 @@ int main(int argc, char** argv)
             case 'R': voxel_route = (optarg[0] == 'p' && optarg[1] == 'a' && optarg[2] == 'y') ? PCS_NODE_VOXEL_PAYLOADS : PCS_NODE_VOXEL_PARTIALS; break;
             case 'Z': drop_invalid = true; break;
             case 'P': pipelined = true; break;
+            case 'z': compressed = true; break;
             case 'T': transform_path = optarg; break;
             case 'B': {
                 std::string why;
@@ -139,6 +146,7 @@ int main(int argc, char** argv)
     }
     if (downsample < 1) { std::cerr << "downsample must be >= 1" << std::endl; return 2; }
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
+    if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
     if (!source && !cameras) source = "synth:1280x720";      // no live cameras on this node: the synthetic generator
     if (voxel_leaf < 0 || voxel_leaf > 32767) { std::cerr << "-V leaf must be 1..32767 mm" << std::endl; return 2; }
@@ -517,6 +525,12 @@ int main(int argc, char** argv)
             bool ok = true;
             for (int i = 0; i < n_streams; i++) {
                 if (got[i] < 0) { ok = false; break; }
+                if (compressed) {      // the frame is a container: validated on the host, decoded into the camera's device payload
+                    rc = pcs_decompress_payload(ctx, cam_buf[i].data(), (size_t)got[i], static_cast<int16_t*>(d_cam[i]), cam_cap_bytes / 2, &pts[i]);
+                    if (rc != PCS_OK) { std::cerr << "camera " << i << ": " << pcs_strerror(rc) << ": " << pcs_last_error(ctx) << std::endl; return 1; }
+                    dptr[i] = static_cast<const int16_t*>(d_cam[i]);
+                    continue;
+                }
                 pts[i] = got[i] / PCS_POINT_BYTES;
                 if (got[i] && pcs_memcpy_h2d(ctx, d_cam[i], cam_buf[i].data(), (size_t)got[i]) != PCS_OK) ok = false;
                 dptr[i] = static_cast<const int16_t*>(d_cam[i]);

@@ -740,6 +740,9 @@ void pcs_destroy(pcs_ctx* c)
     if (c->d_filter_state) (void)hipFree(c->d_filter_state);
     if (c->d_filter_tab) (void)hipFree(c->d_filter_tab);
     if (c->d_decim_src) (void)hipFree(c->d_decim_src);
+    if (c->d_codec_sizes) (void)hipFree(c->d_codec_sizes);
+    if (c->d_codec_buf) (void)hipFree(c->d_codec_buf);
+    if (c->d_codec_bytes) (void)hipFree(c->d_codec_bytes);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -1605,6 +1608,57 @@ try {
     return PCS_OK;
 } catch (const std::exception& ex) {
     return fail(c, PCS_ERR_NOMEM, "pcs_process_frames: host allocation failed (%s)", ex.what());
+}
+
+// pcs_process_frames with the payload kept on the device and compressed there (pcs_capi_codec.cpp, pcs_kernels_codec.hip): the staged
+// route's uploads and launch decisions (run_fused_device), then the three codec launches on the same stream; only the container and
+// its 4-byte size cross the link on the way back.
+int pcs_process_frames_compressed(pcs_ctx* c, const uint16_t* const* depth, const uint8_t* const* color, void* out, size_t out_capacity,
+                                  int write_header, int* counts, int* out_bytes)
+try {
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (!depth || !color || !out) return fail(c, PCS_ERR_INVALID_ARG, "NULL pointer");
+    DeviceGuard guard(c->device);
+    int rc;
+    if ((rc = check_rasters(c, depth, color, false))) return rc;
+    const size_t worst = pcs_compressed_bound((int)c->max_payload_points);
+    if (out_capacity < sizeof(int32_t) + worst)
+        return fail(c, PCS_ERR_CAPACITY, "pcs_process_frames_compressed: out holds %zu bytes, 4 + pcs_compressed_bound(%zu) = %zu needed",
+                    out_capacity, c->max_payload_points, sizeof(int32_t) + worst);
+    if ((rc = ensure_rasters(c))) return rc;
+    for (int s = 0; s < c->n_streams; s++) {
+        const StreamParams& P = c->h_params[s];
+        HIPCHK(c, hipMemcpyAsync(c->s_depth[s], depth[s], (size_t)P.n_points * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->s_color[s], color[s], P.color_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = ensure(c, c->s_payload, c->s_payload_cap, c->max_payload_points * PCS_POINT_BYTES + 16))) return rc;
+    if ((rc = ensure_idle(c, c->d_codec_buf, c->codec_buf_cap, worst))) return rc;
+    if ((rc = ensure_idle(c, c->d_codec_bytes, c->codec_bytes_cap, sizeof(uint32_t)))) return rc;
+    // the three-pass compaction only: its result never needs a host-side retry, so the stream is not drained before the codec
+    rc = run_fused_device(c, c->s_depth.data(), c->s_color.data(), c->s_payload, c->max_payload_points * PCS_POINT_SHORTS, c->d_counts, true);
+    if (rc) return rc;
+    std::vector<int32_t> h(c->n_streams + 1);
+    if (has_pred(c->flags)) {      // the record count is the device's: one round trip for it
+        HIPCHK(c, hipMemcpyAsync(h.data(), c->d_counts, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {                       // the configuration's: ceil(n / downsample) per stream
+        int32_t total = 0;
+        for (int s = 0; s < c->n_streams; s++) total += h[s] = (int32_t)((c->h_params[s].n_points + (uint32_t)c->downsample - 1) / (uint32_t)c->downsample);
+        h[c->n_streams] = total;
+    }
+    if ((rc = pcs_compress_payload_device(c, c->s_payload, h[c->n_streams], c->d_codec_buf, c->codec_buf_cap, c->d_codec_bytes))) return rc;
+    uint32_t bytes = 0;
+    HIPCHK(c, hipMemcpyAsync(&bytes, c->d_codec_bytes, sizeof bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bytes < 16 || bytes > worst) return fail(c, PCS_ERR_HIP, "pcs_process_frames_compressed: the encoder reported %u bytes", bytes);
+    HIPCHK(c, hipMemcpy(static_cast<uint8_t*>(out) + sizeof(int32_t), c->d_codec_buf, bytes, hipMemcpyDeviceToHost));
+    const int32_t size = (int32_t)bytes;
+    if (write_header) std::memcpy(out, &size, sizeof size);
+    if (counts) for (int s = 0; s < c->n_streams; s++) counts[s] = h[s];
+    if (out_bytes) *out_bytes = size;
+    return PCS_OK;
+} catch (const std::exception& ex) {
+    return fail(c, PCS_ERR_NOMEM, "pcs_process_frames_compressed: host allocation failed (%s)", ex.what());
 }
 
 // ---- software-pipelined host form ------------------------------------------------------------

@@ -338,6 +338,18 @@ struct SpatialArgs {
 // max_rows / max_width: the tallest and the widest raster of the launch. iterations < 1 is hipErrorInvalidValue.
 hipError_t launch_spatial_filter(int n_streams, int iterations, uint32_t max_rows, uint32_t max_width, const SpatialArgs& sa, hipStream_t st);
 
+// Payload codec (pcs_compress_payload_device / pcs_decompress_payload_device, pcs_kernels_codec.hip): the "PCZ1" container of
+// DESIGN.md section 4, 64 records per block, one wavefront per block. Encode is three launches — count (every block's byte size
+// into d_sizes[ceil(n / 64)]), offsets (ONE workgroup scans the sizes, kCodecScanBlocks per pass, and writes block_end[], the
+// container header and, if non-NULL, *d_out_bytes) and emit — and writes at most 16 + 660 ceil(n / 64) bytes; with n == 0 only the
+// offsets launch runs (a 16-byte container). Decode is one launch; it reads nothing at or beyond in_bytes and writes nothing at or
+// beyond record n_points whatever the bytes say (16 + 4 ceil(n / 64) > in_bytes is hipErrorInvalidValue, nothing launched).
+// Payload and container pointers are 4-byte aligned.
+constexpr uint32_t kCodecScanBlocks = 1024;
+hipError_t launch_codec_encode(const int16_t* d_payload, uint32_t n_points, uint32_t* d_sizes, void* d_out, uint32_t* d_out_bytes,
+                               hipStream_t st);
+hipError_t launch_codec_decode(const void* d_in, uint32_t in_bytes, uint32_t n_points, int16_t* d_payload, hipStream_t st);
+
 // a7 with stride.
 hipError_t launch_stitch(const int16_t* d_src, uint32_t src_points, int downsample,
                          int16_t* d_dst, hipStream_t st);

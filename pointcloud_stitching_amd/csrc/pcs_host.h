@@ -124,6 +124,13 @@ struct pcs_ctx {
     // first use, grown when a later call needs more. (The decimated outputs land in s_depth, which is decimated-size already.)
     uint8_t*                        d_decim_src = nullptr; size_t decim_src_cap = 0;
 
+    // payload codec (pcs_capi_codec.cpp): the encoder's block sizes, one word per 64 records, grown on demand; the container staged on
+    // the device by the host forms (pcs_decompress_payload uploads into it, pcs_process_frames_compressed downloads from it) and
+    // their 4-byte byte count
+    uint32_t*                       d_codec_sizes = nullptr; size_t codec_sizes_cap = 0;
+    uint8_t*                        d_codec_buf = nullptr; size_t codec_buf_cap = 0;
+    uint32_t*                       d_codec_bytes = nullptr; size_t codec_bytes_cap = 0;
+
     std::string                     err;
 };
 
@@ -179,6 +186,15 @@ int ensure(pcs_ctx* c, T*& p, size_t& cap, size_t bytes)
     p = static_cast<T*>(q);
     cap = std::max<size_t>(bytes, 256);
     return PCS_OK;
+}
+
+// ensure() for scratch that launches already on the context's stream may still be using: growing waits for the stream first.
+template <class T>
+int ensure_idle(pcs_ctx* c, T*& p, size_t& cap, size_t bytes)
+{
+    if (bytes <= cap && p) return PCS_OK;
+    if (p) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ensure(c, p, cap, bytes);
 }
 
 struct DeviceGuard {

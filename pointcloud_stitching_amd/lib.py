@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import CloudDesc, Config, DepthFilterConfig, PayloadDesc, SpatialFilterConfig, StreamConfig
+from .types import CloudDesc, CompressedInfo, Config, DepthFilterConfig, PayloadDesc, SpatialFilterConfig, StreamConfig
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -75,6 +75,12 @@ SYMBOLS = [
     ("pcs_voxel_sink_begin", C.c_int, [_VP, C.c_size_t, C.c_int, _VP]),
     ("pcs_process_frames_voxel_into_sink_device", C.c_int, [_VP, _P(_VP), _P(_VP), _VP]),
     ("pcs_voxel_sink_finish", C.c_int, [_VP, _VP, _VP, C.c_size_t, _VP]),
+    ("pcs_compressed_bound", C.c_size_t, [C.c_int]),
+    ("pcs_compressed_info", C.c_int, [_VP, C.c_size_t, _P(CompressedInfo)]),
+    ("pcs_compress_payload_device", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_size_t, _VP]),
+    ("pcs_decompress_payload_device", C.c_int, [_VP, _VP, C.c_size_t, C.c_int, _VP, C.c_size_t]),
+    ("pcs_decompress_payload", C.c_int, [_VP, _VP, C.c_size_t, _VP, C.c_size_t, _P(C.c_int)]),
+    ("pcs_process_frames_compressed", C.c_int, [_VP, _P(_VP), _P(_VP), _VP, C.c_size_t, C.c_int, _P(C.c_int), _P(C.c_int)]),
     ("pcs_set_stream", C.c_int, [_VP, _VP]),
     ("pcs_get_stream", _VP, [_VP]),
     ("pcs_synchronize", C.c_int, [_VP]),

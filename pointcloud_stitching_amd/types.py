@@ -91,6 +91,11 @@ class SpatialFilterConfig(C.Structure):
     _fields_ = [("alpha", C.c_float), ("delta", C.c_int32), ("iterations", C.c_int32), ("hole_radius", C.c_int32)]
 
 
+class CompressedInfo(C.Structure):
+    """pcs_compressed_info: what the validator reads from a "PCZ1" container's header."""
+    _fields_ = [("n_points", C.c_uint32), ("n_blocks", C.c_uint32), ("total_bytes", C.c_uint32), ("data_offset", C.c_uint32)]
+
+
 # --- the reference's surveyed extrinsics (data, not code) -------------------------------------
 # src/pcs-camera-optimized.cpp:64-67
 TF_MAT = np.array([
