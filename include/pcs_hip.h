@@ -662,6 +662,44 @@ int pcs_decompress_payload(pcs_ctx* ctx, const void* in, size_t in_bytes, int16_
 int pcs_process_frames_compressed(pcs_ctx* ctx, const uint16_t* const* depth, const uint8_t* const* color, void* out,
                                   size_t out_capacity, int write_header, int* counts, int* out_bytes);
 
+/* ---- radius outlier removal on a packed payload (not in the reference: its centre programs include PCL's filters, unused) -------- *
+ * Record i of n (5 shorts; 0..2 = x, y, z as signed int16 millimetres, 3..4 colour, not looked at) is KEPT iff
+ *     |{ j != i : (xi-xj)^2 + (yi-yj)^2 + (zi-zj)^2 <= radius_mm^2 }| >= min_neighbors
+ * in integers of 32 bits or more from the sign-extended shorts (32767 and -32768 are 65535 mm apart; nothing wraps at 16 bits; no
+ * floats anywhere). j != i is by index: a record with another's coordinates is its neighbour at distance 0. The output is the kept
+ * records in input order, all 10 bytes of each unchanged (the high byte of short 4 included), and their count. Exact and
+ * deterministic: the same bytes for the same input on every run (tests/np_radius_outlier.py restates it as brute force). Modelled on
+ * PCL's RadiusOutlierRemoval; parity with PCL is unpinned. DESIGN.md section 3 has the definition and what follows from it: the
+ * filter knows nothing of invalid depth (a dense payload's zero-depth pixels all sit on their camera's origin and keep each other:
+ * run it behind PCS_FLAG_DROP_INVALID or a crop box), and the result does not depend on record order except for the output's own.
+ * radius_mm 1..1000, min_neighbors 1..255.
+ * pcs_radius_outlier_device: asynchronous on the context's stream, ten launches, no host round trip (a uniform grid of cell edge
+ *   radius_mm in an open-addressing table built per call, a scatter into cell order, one lane per record over its 27 cells with an
+ *   exit at min_neighbors, then the ordered compaction). d_out needs room for the worst case, n_points records: out_shorts >=
+ *   5 n_points is checked up front; nothing outside the first 10 * kept bytes of d_out is written. *d_out_points (device, 4-byte
+ *   aligned, required) receives kept. n_points 0 launches nothing and writes a zero count.
+ * pcs_radius_outlier_device_counted: the count is read from *d_n_points (device, 4-byte aligned) when the kernels run, clamped to
+ *   0..max_points; max_points sizes the workspace, the grids and the output check. What a compaction's or another filter's device
+ *   count feeds; its own output and count feed pcs_voxel_grid_device_counted.
+ * pcs_radius_outlier: host pointers, staged through the context, synchronous.
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the argument), nothing launched, nothing written: radius_mm or
+ *   min_neighbors out of range, a negative count, a NULL pointer (payload and output may be NULL with a count of 0), an odd payload
+ *   or output address, a misaligned count word, out_shorts below the worst case, any overlap of the input, output and count ranges.
+ * Works on every context: flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH are not read. The workspace (40.2 bytes per record
+ *   of n_points / max_points: csrc/pcs_kernels_outlier.hip) lives in the context and grows on demand. A record costs at most the
+ *   population of its 27 cells; n identical records cost n (min_neighbors + 1) distance tests. With pcs_kernel_timing enabled a call
+ *   yields one interval per launch (10). Measured: DESIGN.md section 10 (f9), profiles/outlier_probe.txt.                          */
+#define PCS_OUTLIER_RADIUS_MIN     1
+#define PCS_OUTLIER_RADIUS_MAX     1000
+#define PCS_OUTLIER_NEIGHBORS_MIN  1
+#define PCS_OUTLIER_NEIGHBORS_MAX  255
+int pcs_radius_outlier_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, int radius_mm, int min_neighbors,
+                              int16_t* d_out, size_t out_shorts, int32_t* d_out_points);
+int pcs_radius_outlier_device_counted(pcs_ctx* ctx, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                      int radius_mm, int min_neighbors, int16_t* d_out, size_t out_shorts, int32_t* d_out_points);
+int pcs_radius_outlier(pcs_ctx* ctx, const int16_t* payload, int n_points, int radius_mm, int min_neighbors,
+                       int16_t* out, size_t out_shorts, int* out_points);   /* host pointers, staged, synchronous */
+
 /* ---- stream / timing plumbing ----------------------------------------------------------- */
 int   pcs_set_stream(pcs_ctx* ctx, void* hip_stream);   /* adopt a caller-owned hipStream_t (NULL = own stream) */
 void* pcs_get_stream(pcs_ctx* ctx);

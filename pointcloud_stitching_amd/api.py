@@ -538,6 +538,32 @@ class PcsContext:
         self._check(self._lib.pcs_voxel_grid_device_counted(self._h, d_payload, d_n_points, int(max_points), int(leaf_mm),
                                                             d_out, out_shorts, d_out_points or None))
 
+    # -- radius outlier removal (defined by this build; see include/pcs_hip.h) ---------------------
+    def radius_outlier(self, payload: np.ndarray, radius_mm: int, min_neighbors: int) -> np.ndarray:
+        """Packed records (int16 [n,5]) -> the records with at least min_neighbors others within radius_mm, input order
+        (pcs_radius_outlier: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        out = np.zeros((max(p.shape[0], 1), POINT_SHORTS), np.int16)
+        cnt = C.c_int(0)
+        self._check(self._lib.pcs_radius_outlier(self._h, _ptr(p), p.shape[0], int(radius_mm), int(min_neighbors), _ptr(out),
+                                                 p.shape[0] * POINT_SHORTS, C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def radius_outlier_device(self, d_payload: int, n_points: int, radius_mm: int, min_neighbors: int, d_out: int, out_shorts: int,
+                              d_out_points: int) -> None:
+        """Asynchronous; device pointers as ints; *d_out_points (int32, required) receives the kept count. See
+        pcs_radius_outlier_device."""
+        self._check(self._lib.pcs_radius_outlier_device(self._h, d_payload or None, int(n_points), int(radius_mm), int(min_neighbors),
+                                                        d_out or None, out_shorts, d_out_points or None))
+
+    def radius_outlier_device_counted(self, d_payload: int, d_n_points: int, max_points: int, radius_mm: int, min_neighbors: int,
+                                      d_out: int, out_shorts: int, d_out_points: int) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run. See
+        pcs_radius_outlier_device_counted."""
+        self._check(self._lib.pcs_radius_outlier_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
+                                                                int(radius_mm), int(min_neighbors), d_out or None, out_shorts,
+                                                                d_out_points or None))
+
     def process_frames_voxel_device(self, d_depth: Sequence[int], d_color: Sequence[int], leaf_mm: int, d_out: int,
                                     out_shorts: int, d_out_points: int = 0) -> None:
         """Rasters -> voxel grid without the stitched cloud (pcs_process_frames_voxel_device)."""

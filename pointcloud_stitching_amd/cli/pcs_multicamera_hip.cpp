@@ -40,6 +40,12 @@
 //                      on the host and decoded on the GPU into the camera's device payload (pcs_decompress_payload) ahead of the
 //                      stitch / -T / -B / -V paths, which see what they always saw; a frame that fails validation ends the run with
 //                      the validator's message. What is served on -p stays raw.
+//              -O <radius_mm,min_neighbors>  radius outlier removal on the stitched cloud (pcs_radius_outlier_device: a record stays iff
+//                      at least min_neighbors others lie within radius_mm of it): after -T and -B / -d, before -V. With -c it runs on
+//                      the stitched device payload (with -V its output and device count feed pcs_voxel_grid_device_counted); with -i
+//                      the payload is built on the device (pcs_process_frames_device), filtered by the counted form, then voxelised
+//                      or copied out. -t prints `Outlier removal: <in> -> <kept> points` per frame-set. Not with -G: the node library
+//                      has no such filter. The filter knows nothing of invalid depth: with -i give -Z (or -B).
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
@@ -55,6 +61,7 @@
 #include <signal.h>
 
 #include "pcs_cropbox.h"
+#include "pcs_outlier.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
 #include "../../include/pcs_node.h"
@@ -73,6 +80,8 @@ static const char* dump_path = nullptr;
 static const char* transform_path = nullptr;
 static bool crop = false;
 static int16_t crop_lo[3], crop_hi[3];
+static bool outlier = false;
+static int outlier_radius = 0, outlier_neighbors = 0;
 
 static void usage()
 {
@@ -93,6 +102,8 @@ static void usage()
               << "                  as the reference's pcs-multicamera-optimized does (decode, pcl::transformPointCloud, re-encode)\n"
               << " -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box, millimetres in the world frame, inclusive: -i crops in the fused path, -c crops the\n"
               << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
+              << " -O <radius_mm,min_neighbors>  radius outlier removal on the stitched cloud: a record stays iff at least min_neighbors\n"
+              << "                  others lie within radius_mm (1..1000, 1..255); after -T and -B / -d, before -V; not with -G\n"
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
@@ -103,7 +114,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:z")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -138,6 +149,12 @@ int main(int argc, char** argv)
                 crop = true;
                 break;
             }
+            case 'O': {
+                std::string why;
+                if (!pcs_outlier::parse(optarg, outlier_radius, outlier_neighbors, why)) { std::cerr << "-O " << optarg << ": " << why << std::endl; return 2; }
+                outlier = true;
+                break;
+            }
             case 's': case 'v': case 'n':
                 std::cerr << "-" << (char)c << " drives the reference's PCL viewer / PLY writer, which this build does not include" << std::endl;
                 return 2;
@@ -146,6 +163,7 @@ int main(int argc, char** argv)
     }
     if (downsample < 1) { std::cerr << "downsample must be >= 1" << std::endl; return 2; }
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
+    if (outlier && n_gpus > 0) { std::cerr << "-O is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
     if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
     if (!source && !cameras) source = "synth:1280x720";      // no live cameras on this node: the synthetic generator
@@ -285,9 +303,18 @@ int main(int argc, char** argv)
     }
     // -B with -i -V: the cropped payload and its counts stay on the device between the two calls
     void *d_pay = nullptr, *d_pay_counts = nullptr;
-    if (crop && source && voxel_leaf) {
+    if (source && ((crop && voxel_leaf) || outlier)) {
         if (pcs_device_malloc(ctx, &d_pay, pcs_max_payload_shorts(ctx) * sizeof(int16_t) + 64) != PCS_OK ||
             pcs_device_malloc(ctx, &d_pay_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+    }
+
+    // -O: the filtered payload and its count stay on the device (-V reads both there)
+    void *d_filtered = nullptr, *d_nfiltered = nullptr;
+    if (outlier) {
+        const size_t bytes = source ? pcs_max_payload_shorts(ctx) * sizeof(int16_t) : (size_t)n_streams * cam_cap_bytes;
+        if (pcs_device_malloc(ctx, &d_filtered, bytes + 64) != PCS_OK || pcs_device_malloc(ctx, &d_nfiltered, 64) != PCS_OK) {
+            std::cerr << pcs_last_error(ctx) << std::endl; return 1;
+        }
     }
 
     // -V: device-resident rasters (with -i) and the voxel cloud
@@ -302,17 +329,17 @@ int main(int argc, char** argv)
         }
         if (!node && (pcs_device_malloc(ctx, &d_vox, vox_cap_points * PCS_POINT_BYTES + 64) != PCS_OK ||
                       pcs_device_malloc(ctx, &d_nvox, 64) != PCS_OK)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-        if (source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
-            d_depth.resize(n_streams, nullptr); d_color.resize(n_streams, nullptr);
-            for (int s = 0; s < n_streams; s++) {
-                const size_t db = (size_t)cfgs[s].depth.width * cfgs[s].depth.height * 2;
-                const size_t cb = (size_t)cfgs[s].color_stride * cfgs[s].color.height;
-                if (pcs_device_malloc(ctx, &d_depth[s], db + 64) != PCS_OK || pcs_device_malloc(ctx, &d_color[s], cb + 64) != PCS_OK) {
-                    std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-                }
+        if (!stitched.resize(PCS_HEADER_SHORTS + vox_cap_points * PCS_POINT_SHORTS)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+    }
+    if ((voxel_leaf || outlier) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
+        d_depth.resize(n_streams, nullptr); d_color.resize(n_streams, nullptr);
+        for (int s = 0; s < n_streams; s++) {
+            const size_t db = (size_t)cfgs[s].depth.width * cfgs[s].depth.height * 2;
+            const size_t cb = (size_t)cfgs[s].color_stride * cfgs[s].color.height;
+            if (pcs_device_malloc(ctx, &d_depth[s], db + 64) != PCS_OK || pcs_device_malloc(ctx, &d_color[s], cb + 64) != PCS_OK) {
+                std::cerr << pcs_last_error(ctx) << std::endl; return 1;
             }
         }
-        if (!stitched.resize(PCS_HEADER_SHORTS + vox_cap_points * PCS_POINT_SHORTS)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
     // the voxel cloud of whatever d_vox / d_nvox hold -> stitched (header + records). `again` repeats the device call that filled
     // them: a count of -1 (the bucket tail gave up on a stalled device, include/pcs_hip.h) is answered by one more run on the LSD
@@ -482,6 +509,42 @@ int main(int argc, char** argv)
                     std::cout << "Voxel grid over " << n_gpus << " GPU(s): kernels " << vstats.kernels_ms << " ms, exchange " << vstats.exchange_ms
                               << " ms (" << vstats.exchanged_bytes << " B), root " << vstats.root_voxel_ms << " ms, " << vstats.partials
                               << (voxel_route == PCS_NODE_VOXEL_PARTIALS ? " partials -> " : " points -> ") << vstats.voxels << " voxels" << std::endl;
+            } else if (outlier) {
+                // the payload on the device (under -Z / -B / -d as ever), the filter on its device count, then the voxel grid on the
+                // filter's device count or the kept records out: no count leaves the device in between
+                for (int s = 0; s < n_streams; s++) {
+                    if (pcs_memcpy_h2d(ctx, d_depth[s], depth[s].data(), depth[s].size() * 2) != PCS_OK ||
+                        pcs_memcpy_h2d(ctx, d_color[s], color[s].data(), color[s].size()) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                }
+                const size_t max_shorts = pcs_max_payload_shorts(ctx);
+                const int max_points = (int)(max_shorts / PCS_POINT_SHORTS);
+                const int32_t* d_total = static_cast<const int32_t*>(d_pay_counts) + n_streams;
+                rc = pcs_process_frames_device(ctx, reinterpret_cast<const uint16_t* const*>(d_depth.data()),
+                                               reinterpret_cast<const uint8_t* const*>(d_color.data()), static_cast<int16_t*>(d_pay), max_shorts,
+                                               static_cast<int32_t*>(d_pay_counts));
+                if (rc == PCS_OK)
+                    rc = pcs_radius_outlier_device_counted(ctx, static_cast<const int16_t*>(d_pay), d_total, max_points, outlier_radius, outlier_neighbors,
+                                                           static_cast<int16_t*>(d_filtered), max_shorts, static_cast<int32_t*>(d_nfiltered));
+                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                if (voxel_leaf) {
+                    auto run_voxel = [&]() {
+                        return pcs_voxel_grid_device_counted(ctx, static_cast<const int16_t*>(d_filtered), static_cast<const int32_t*>(d_nfiltered),
+                                                             max_points, voxel_leaf, static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS,
+                                                             static_cast<int32_t*>(d_nvox));
+                    };
+                    rc = run_voxel();
+                    if (rc != PCS_OK || !fetch_voxels(run_voxel)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                }
+                int32_t n_in = 0, n_kept = 0;
+                if (pcs_memcpy_d2h(ctx, &n_in, d_total, sizeof n_in) != PCS_OK || pcs_memcpy_d2h(ctx, &n_kept, d_nfiltered, sizeof n_kept) != PCS_OK ||
+                    pcs_synchronize(ctx) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                if (!voxel_leaf) {
+                    size_bytes = n_kept * PCS_POINT_BYTES;
+                    if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, d_filtered, (size_t)size_bytes) != PCS_OK) return 1;
+                    pcs_synchronize(ctx);
+                    memcpy(stitched.data(), &size_bytes, sizeof(int));
+                }
+                if (timer) std::cout << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl;
             } else if (voxel_leaf) {
                 for (int s = 0; s < n_streams; s++) {
                     if (pcs_memcpy_h2d(ctx, d_depth[s], depth[s].data(), depth[s].size() * 2) != PCS_OK ||
@@ -566,8 +629,26 @@ int main(int argc, char** argv)
             rc = pcs_stitch_device(ctx, dptr.data(), pts.data(), n_streams, downsample, static_cast<int16_t*>(d_stitched),
                                    (size_t)n_streams * cam_cap_bytes / 2, &total_pts);
             if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+            const int outlier_in = total_pts;
+            if (outlier) {
+                rc = pcs_radius_outlier_device(ctx, d_result, total_pts, outlier_radius, outlier_neighbors, static_cast<int16_t*>(d_filtered),
+                                               (size_t)n_streams * cam_cap_bytes / 2, static_cast<int32_t*>(d_nfiltered));
+                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                d_result = static_cast<const int16_t*>(d_filtered);
+                if (!voxel_leaf || timer) {      // (with -V the voxel grid reads the count where it is)
+                    int32_t kept = 0;
+                    if (pcs_memcpy_d2h(ctx, &kept, d_nfiltered, sizeof kept) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) {
+                        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
+                    }
+                    if (timer) std::cout << "Outlier removal: " << outlier_in << " -> " << kept << " points" << std::endl;
+                    if (!voxel_leaf) total_pts = kept;
+                }
+            }
             if (voxel_leaf) {
                 auto run_voxel = [&]() {
+                    if (outlier)
+                        return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nfiltered), outlier_in, voxel_leaf,
+                                                             static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
                     return pcs_voxel_grid_device(ctx, d_result, total_pts, voxel_leaf, static_cast<int16_t*>(d_vox),
                                                  vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
                 };
@@ -607,7 +688,7 @@ int main(int argc, char** argv)
     if (d_vox) pcs_device_free(ctx, d_vox);
     if (d_nvox) pcs_device_free(ctx, d_nvox);
     if (d_stitched) pcs_device_free(ctx, d_stitched);
-    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts}) if (p) pcs_device_free(ctx, p);
+    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts, d_filtered, d_nfiltered}) if (p) pcs_device_free(ctx, p);
     if (node) pcs_node_destroy(node);
     stitched.release();
     pcs_destroy(ctx);

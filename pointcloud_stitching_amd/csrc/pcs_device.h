@@ -350,6 +350,20 @@ hipError_t launch_codec_encode(const int16_t* d_payload, uint32_t n_points, uint
                                hipStream_t st);
 hipError_t launch_codec_decode(const void* d_in, uint32_t in_bytes, uint32_t n_points, int16_t* d_payload, hipStream_t st);
 
+// Radius outlier removal (pcs_radius_outlier_device, pcs_kernels_outlier.hip): kOutlierStages launches on one stream, each its own
+// call so that the host layer can bracket them one by one (pcs_kernel_timing). `capacity` (n_points, or max_points of the counted
+// form) sizes every grid and the workspace; the record count the kernels use is n_points, or *d_n_points clamped to 0..capacity when
+// that pointer is given — read by stage 0, on the device. d_ws: outlier_workspace_bytes(capacity) bytes, 256-byte aligned. Stage 8
+// is launch_scan over the control block's one-entry table: it writes the kept count to d_out_points[0].
+constexpr int kOutlierStages = 10;
+struct OutlierCtl { StreamParams tab; };     // entry 0 of a scan table: n_points = the record count, tile_base = 0
+uint32_t    outlier_slots(uint32_t capacity);
+size_t      outlier_workspace_bytes(uint32_t capacity);
+const char* outlier_stage_name(int stage);
+hipError_t  launch_outlier_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
+                                 int radius_mm, int min_neighbors, void* d_ws, size_t ws_bytes, int16_t* d_out, int32_t* d_out_points,
+                                 hipStream_t st);
+
 // a7 with stride.
 hipError_t launch_stitch(const int16_t* d_src, uint32_t src_points, int downsample,
                          int16_t* d_dst, hipStream_t st);

@@ -131,6 +131,10 @@ struct pcs_ctx {
     uint8_t*                        d_codec_buf = nullptr; size_t codec_buf_cap = 0;
     uint32_t*                       d_codec_bytes = nullptr; size_t codec_bytes_cap = 0;
 
+    // radius outlier removal (pcs_capi_outlier.cpp): the cell index, keep bits and tile words of one call, sized from the call's
+    // n_points / max_points alone (outlier_workspace_bytes), grown on demand the way the voxel workspace is
+    void*                           s_outlier_ws = nullptr; size_t s_outlier_ws_cap = 0;
+
     std::string                     err;
 };
 

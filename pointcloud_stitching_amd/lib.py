@@ -81,6 +81,9 @@ SYMBOLS = [
     ("pcs_decompress_payload_device", C.c_int, [_VP, _VP, C.c_size_t, C.c_int, _VP, C.c_size_t]),
     ("pcs_decompress_payload", C.c_int, [_VP, _VP, C.c_size_t, _VP, C.c_size_t, _P(C.c_int)]),
     ("pcs_process_frames_compressed", C.c_int, [_VP, _P(_VP), _P(_VP), _VP, C.c_size_t, C.c_int, _P(C.c_int), _P(C.c_int)]),
+    ("pcs_radius_outlier_device", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    ("pcs_radius_outlier_device_counted", C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    ("pcs_radius_outlier", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _P(C.c_int)]),
     ("pcs_set_stream", C.c_int, [_VP, _VP]),
     ("pcs_get_stream", _VP, [_VP]),
     ("pcs_synchronize", C.c_int, [_VP]),

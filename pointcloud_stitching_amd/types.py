@@ -23,6 +23,10 @@ FLAG_FORCE_IEEE = 0x8
 FLAG_TEXCOORD_HALF_PIXEL = 0x10     # u = (px + 0.5)/W as older librealsense releases
 FLAG_SCALAR_ARITH = 0x20            # the reference's default (no -m) arithmetic, copyPointCloudXYZRGBToBuffer, bit for bit
 
+OUTLIER_RADIUS_MIN, OUTLIER_RADIUS_MAX = 1, 1000          # pcs_radius_outlier*: radius_mm
+OUTLIER_NEIGHBORS_MIN, OUTLIER_NEIGHBORS_MAX = 1, 255     # ... min_neighbors
+OUTLIER_LAUNCHES = 10                                     # intervals one call adds to kernel_times_ms under kernel_timing
+
 DISTORTION_NONE = 0
 DISTORTION_MODIFIED_BROWN_CONRADY = 1
 DISTORTION_INVERSE_BROWN_CONRADY = 2
