@@ -135,6 +135,7 @@ __device__ __forceinline__ unsigned long long cell_key(int cx, int cy, int cz)
 }
 
 // where a key's probe sequence starts: a 64-bit finaliser's top bits scaled to [0, slots)
+// (restated in numpy by tests/test_radius_outlier_scale.py, with cell_of, cell_key and outlier_slots, to build a cloud whose probes wrap)
 __device__ __forceinline__ uint32_t first_slot(unsigned long long k, uint32_t slots)
 {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdull;

@@ -1,7 +1,9 @@
 """Clouds for the radius outlier removal tests, shared by the CPU tier, the GPU tests and the CLI test. Everything is deterministic.
 A case is (name, (n, 5) int16 records, radius_mm, min_neighbors, expected) where `expected` is the keep mask known WITHOUT the brute
 force (None where only tests/np_radius_outlier.py says). The colour shorts are random; the high byte of short 4 is never zero (the
-filter copies all ten bytes of a record)."""
+filter copies all ten bytes of a record).
+tiled_cubes and lattice_box are the clouds of working size (two and one million records): they are not in cases(), whose brute force
+must stay affordable, and return their expectation with the records."""
 import itertools
 import functools
 
@@ -27,6 +29,12 @@ def cube(side, seed, n=6161):
 CUBES = ((400, 20, 3, 1, 58.3), (400, 20, 1, 1, 95.0), (400, 20, 8, 1, 1.3), (64, 1, 1, 3, 15.8))
 FULL_RANGE = (4097, 2, 1000, 1, 6.2)        # n, seed, radius, min_neighbors, share: many distinct cells, every sign combination
 COUNTS = (0, 1, 2, 63, 64, 65, 2047, 2048, 2049)
+# The clouds of working size (tests/test_radius_outlier_scale.py); none of them is in cases(): their expectations need no pair loop.
+# (copies per axis, pitch, records, kept share in percent at CUBES[0]'s (20, 3): the small cloud's, copy by copy)
+TILED = (7, 427, 7 ** 3 * 6161, 58.3)         # 1 231 713 records kept
+# (shape, origin, records, ((radius, min_neighbors, kept share in percent), ...)): one record per integer point, y up to +32767, z from
+# -32768. Radius 1: faces and interior / interior only, by index arithmetic; radius 2: the records with all 32 neighbours inside.
+LATTICE = ((128, 128, 65), (-64, 32640, -32768), 128 * 128 * 65, ((1, 5, 99.9), (1, 6, 93.9), (2, 32, 88.1)))
 
 
 def full_range():
@@ -120,6 +128,48 @@ def saturation():
 def identical(n=65536):
     """The early-exit case: n x 255 distance tests, not n^2."""
     return with_colour(np.tile(np.array([[123, -456, 789]]), (n, 1)))
+
+
+@functools.lru_cache(maxsize=None)
+def tiled_cubes(copies_per_axis=TILED[0], pitch=TILED[1]):
+    """CUBES[0]'s cloud (side 400, radius 20, min_neighbors 3) copied to every node of a copies_per_axis^3 lattice of that pitch, node
+    (i, j, k) at (i - copies_per_axis // 2) * pitch per axis, every copy with colour shorts of its own, the records shuffled by one fixed
+    permutation: 7^3 x 6161 = 2 113 223 records, 1032 record tiles, 2064 slot tiles. Records of different copies are at least
+    pitch - 399 apart, more than the radius, and the definition does not change under translation: the keep mask is the small cloud's
+    (reference("cube400_r20_k3")), copy by copy, permuted. The pitch is no multiple of the radius: every copy meets the cell grid at
+    another phase. Returns (records, expected keep mask), both read-only."""
+    side, radius, k, seed, _ = CUBES[0]
+    assert pitch - (side - 1) > radius, "neighbouring copies must be more than a radius apart"
+    small = cube(side, seed)
+    small_mask = reference(f"cube{side}_r{radius}_k{k}")
+    n = small.shape[0]
+    parts = []
+    for c, node in enumerate(itertools.product(range(copies_per_axis), repeat=3)):
+        offset = (np.array(node) - copies_per_axis // 2) * pitch
+        parts.append(with_colour(small[:, :3].astype(np.int64) + offset, seed=1000 + c))
+    order = np.random.default_rng(12).permutation(n * len(parts))
+    rec = np.concatenate(parts)[order]
+    mask = np.tile(small_mask, len(parts))[order]
+    for a in range(0, rec.shape[0], 2048):
+        assert 0 < mask[a:a + 2048].sum() < mask[a:a + 2048].shape[0], "a record tile with nothing kept, or nothing dropped"
+    rec.setflags(write=False)
+    mask.setflags(write=False)
+    return rec, mask
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_box(shape=LATTICE[0], origin=LATTICE[1]):
+    """One record on every integer point of origin + [0, shape), shuffled by one fixed permutation. Returns (records, inside), both
+    read-only: inside[i] = how many of record i's six lattice neighbours lie in the box, per axis (index > 0) + (index < extent - 1) —
+    its neighbour count at radius 1, where every record is a cell of its own."""
+    idx = np.indices(shape).reshape(3, -1).T
+    inside = ((idx > 0).astype(np.int64) + (idx < np.array(shape) - 1)).sum(axis=1)
+    order = np.random.default_rng(13).permutation(idx.shape[0])
+    rec = with_colour((idx + np.array(origin))[order])
+    inside = inside[order]
+    rec.setflags(write=False)
+    inside.setflags(write=False)
+    return rec, inside
 
 
 @functools.lru_cache(maxsize=None)

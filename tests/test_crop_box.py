@@ -486,6 +486,35 @@ def test_centre_side_crop_of_packed_payloads(oracle):
         assert e.value.status == -5
 
 
+@pytest.mark.gpu
+def test_centre_side_crop_second_pass_of_the_scan():
+    """One camera of 2 099 201 records = 1026 tiles: the per-camera scan of pcs_crop_payloads_device carries its running total into a
+    second pass of 1024 tiles. Random records over the whole int16 range, a box that keeps about half of them, every third kept
+    record written."""
+    n, ds = 2099201, 3
+    box = ((-32768, -20000, -32768), (32767, 32767, 7000))
+    rng = np.random.default_rng(41)
+    rec = rng.integers(-32768, 32768, (n, 5)).astype(np.int16)
+    keep = mask_rows(rec, box)
+    want = rec[keep][::ds]
+    assert 0.4 * n < keep.sum() < 0.6 * n and 0 < keep[:1024 * 2048].sum() < keep.sum()
+    cfgs, _, _ = S.synth_frame_set(1, 64, 48, single=True)
+    with PcsContext(cfgs) as ctx:
+        ctx.set_crop_box_mm(*box)
+        src = ctx.device_malloc(rec.nbytes + 64)
+        ctx.memcpy_h2d(src + 4, rec)
+        out = ctx.device_malloc(rec.nbytes + 64)
+        cnt = ctx.device_malloc(4 * 2)
+        ctx.crop_payloads_device([src + 4], [n], ds, out + 4, 5 * n, cnt)
+        ctx.synchronize()
+        c = np.empty(2, np.int32)
+        ctx.memcpy_d2h(c, cnt)
+        assert list(c) == [want.shape[0], want.shape[0]]
+        got = np.empty((want.shape[0], 5), np.int16)
+        ctx.memcpy_d2h(got, out + 4)
+        assert_same(got, want)
+
+
 # ---------------------------------------------------------------------------------------------
 # 9. crop, then voxel
 # ---------------------------------------------------------------------------------------------

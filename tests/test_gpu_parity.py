@@ -126,6 +126,23 @@ def test_pack_compaction_matches_t1_order(oracle, flags, n):
     assert_same(out, want)
 
 
+def test_pack_compaction_second_pass_of_the_scan(oracle):
+    """2 099 201 points = 1026 tiles: the a2 twin's scan (launch_pack_scan: the arrival-counter branch of pcs_scan_kernel) carries its
+    running total into a second pass of 1024 tiles."""
+    n, flags = 2099201, FLAG_CUTOFF
+    sc, V, T, col = random_points(n, 31 + n, spread=1.5)
+    V[:, 2] = np.abs(V[:, 2])
+    V[::5, 2] = 0.0
+    want = oracle.pack(sc, V, T, col, flags)
+    assert 0 < want.shape[0] < n
+    kept_in_first_pass = oracle.pack(sc, V[:1024 * 2048], T[:1024 * 2048], col, flags).shape[0]
+    assert 0 < kept_in_first_pass < want.shape[0]                           # the carry is neither zero nor everything
+    with PcsContext([sc], flags=flags) as ctx:
+        out, cnt = ctx.copy_pointcloud_xyzrgb_to_buffer(0, V, T, col)
+    assert cnt == want.shape[0]
+    assert_same(out, want)
+
+
 def test_send_xyzrgb_pointcloud_layout(oracle):
     sc, V, T, col = random_points(1000, 5)
     want, wsize = oracle.send_xyzrgb_pointcloud(sc, V, T, col, buffer_shorts=2_600_000, write_header=True)
@@ -1037,6 +1054,34 @@ def test_batched_compaction_equals_the_oracle(oracle, flags, shapes, n_sets, ske
             got = np.empty(max(want.size, 1), np.int16)
             ctx.memcpy_d2h(got, outs[k])
             assert_same(got[:want.size].reshape(-1, 5), want)
+
+
+def test_batched_compaction_second_pass_of_the_scan(oracle):
+    """One stream of 2048x1100 = 1100 tiles, two frame-sets: pcs_scan_batch_kernel walks the tile counts 1024 at a time and carries
+    the running total into a second pass (tiles 1024 .. 1099 of each set start behind everything the first pass kept)."""
+    w, h, n_sets, flags = 2048, 1100, 2, FLAG_DROP_INVALID
+    cfgs = [S.synth_stream_config(w, h, 0)]
+    assert (cfgs[0].n_points + 2047) // 2048 == 1100
+    sets = [([S.synth_depth(w, h, 0, seed=S.SEED + 31 * k)], [S.synth_color(w, h, 0, seed=S.SEED + 31 * k)]) for k in range(n_sets)]
+    n_sh = cfgs[0].n_points * POINT_SHORTS
+    with PcsContext(cfgs, flags=flags) as ctx:
+        dd = [_upload(ctx, d) for d, _ in sets]
+        dc = [_upload(ctx, c) for _, c in sets]
+        outs = [ctx.device_malloc(n_sh * 2 + 64) for _ in range(n_sets)]
+        d_counts = [ctx.device_malloc(4 * 2) for _ in range(n_sets)]
+        ctx.process_frames_device_batch(dd, dc, outs, n_sh, d_counts)
+        ctx.synchronize()
+        for k in range(n_sets):
+            want, wcounts = oracle.process_frames(cfgs, sets[k][0], sets[k][1], flags)
+            measured = sets[k][0][0].reshape(-1) != 0
+            assert measured[:1024 * 2048].any() and measured[1024 * 2048:].any()       # the carry: neither zero nor everything
+            assert 0 < want.shape[0] < cfgs[0].n_points
+            cnt = np.empty(2, np.int32)
+            ctx.memcpy_d2h(cnt, d_counts[k])
+            assert list(cnt) == [wcounts[0], wcounts[0]], f"set {k}"
+            got = np.empty(want.size, np.int16)
+            ctx.memcpy_d2h(got, outs[k])
+            assert_same(got.reshape(-1, 5), want)
 
 
 def test_batched_compaction_with_a_stride_runs_set_by_set(oracle):

@@ -2,7 +2,11 @@
 restatement of DESIGN.md section 3 (tests/np_radius_outlier.py) over the clouds of tests/radius_outlier_cases.py: at the reference's
 `buffer + 2` shorts and at 16-byte alignment, at every 2-byte phase of input and output for one cloud, with guard bytes behind the
 kept records and behind the worst-case output, twice for determinism, through the counted form, the host form, into the voxel grid,
-and through every refusal."""
+and through every refusal.
+Sizes and table states: clouds of up to 6 161 records with distinct cells (65 536 identical ones), capacities up to 65 536 — one pass of
+the slot scan, one chunk of the tile scan, a nearly empty table. The second and third pass of the slot scan, the tile scan's second
+chunk, the table at one cell per record with faces on the ends of the int16 range, probe sequences that wrap past the last slot and a
+small call in a workspace a 2.1 M-record call left behind are tests/test_radius_outlier_scale.py's."""
 import numpy as np
 import pytest
 

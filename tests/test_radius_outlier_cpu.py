@@ -83,6 +83,94 @@ def test_result_does_not_depend_on_record_order():
     assert (N.keep_mask(rec[perm], r, k) == K.reference("count2049")[perm]).all()
 
 
+# ---- the dense-box restatement, and the clouds of working size ------------------------------------
+def counts_that_matter(rec, r, spread=False):
+    """Every min_neighbors at which the brute-force mask of rec changes, and one beyond the last (legal ones only); spread: at most six
+    of them, both ends among them."""
+    p = rec[:, :3].astype(np.int64)
+    within = (((p[:, None] - p[None]) ** 2).sum(axis=2) <= r * r).sum(axis=1) - 1
+    ks = sorted({int(k) for k in within if k >= 1} | {int(within.max()) + 1})
+    ks = [k for k in ks if 1 <= k <= 255]
+    return ks if len(ks) <= 6 or not spread else [ks[i * (len(ks) - 1) // 5] for i in range(6)]
+
+
+def small_lattice():
+    return K.lattice_box((11, 9, 7), (-5, 32759, -32768))[0]
+
+
+def random_60():
+    return K.with_colour(np.random.default_rng(21).integers(-30, 30, (3000, 3)) + np.array([0, -32738, 32737]))
+
+
+DENSE = ([("saturation", K.saturation, r, k) for r, k in ((1, 1), (6, 1), (6, 2), (6, 5))] +
+         [("duplicates65", lambda: K.duplicates(65), 1, k) for k in (64, 65)] + [("duplicates65", lambda: K.duplicates(65), 3, 64)] +
+         [("lattice_11x9x7", small_lattice, r, None) for r in (1, 2, 3)] +
+         [("random_60", random_60, r, "spread") for r in (1, 2, 5)])
+
+
+@pytest.mark.parametrize("name,cloud,r,k", DENSE, ids=[f"{d[0]}_r{d[2]}_k{d[3]}" for d in DENSE])
+def test_dense_box_restatement_agrees_with_brute_force(name, cloud, r, k):
+    """keep_mask_dense_box is pinned to the pair loop before anything is held to it. k None: every min_neighbors that changes the
+    answer; "spread": six of those. (saturation() at its own radius of 200 is beyond the size condition — 500^3 points — and is asked at radii the box holds.)"""
+    rec = cloud()
+    ks = [k] if isinstance(k, int) else counts_that_matter(rec, r, spread=k == "spread")
+    kept = set()
+    for m in ks:
+        want = N.keep_mask(rec, r, m)
+        assert (N.keep_mask_dense_box(rec, r, m) == want).all(), (name, r, m)
+        kept.add(int(want.sum()))
+    assert isinstance(k, int) or len(kept) > 1                   # (the sweep really moves the answer)
+
+
+def test_dense_box_restatement_refuses_a_box_it_cannot_hold():
+    with pytest.raises(AssertionError):
+        N.keep_mask_dense_box(K.saturation(), 200, 255)
+    assert N.keep_mask_dense_box(np.zeros((0, 5), np.int16), 5, 1).shape == (0,)
+
+
+def test_tiled_cubes_pairs_of_copies_by_brute_force():
+    """tiled_cubes(2), 8 copies, 49 288 records: the per-copy-pair form. The padded box of the whole cloud is 827^3, beyond the dense-box
+    restatement, so for each axis in turn the two copies that differ along it only (12 322 records, whole copies, everything else more
+    than a radius away) go through the pair loop and must give the expected mask's rows. About 7 s per axis here."""
+    rec, want = K.tiled_cubes(2)
+    side, r, k, _, share = K.CUBES[0]
+    assert rec.shape[0] == 8 * 6161 and abs(100.0 * want.mean() - share) <= 2.0
+    xyz = rec[:, :3].astype(np.int64)
+    upper = xyz >= -(side // 2)                          # per axis: in the copy at offset 0 (the other one ends below -227)
+    assert (upper.sum(axis=0) == 4 * 6161).all()
+    for axis in range(3):
+        others = [a for a in range(3) if a != axis]
+        pick = upper[:, others[0]] & upper[:, others[1]]
+        assert pick.sum() == 2 * 6161 and 0 < upper[pick, axis].sum() < pick.sum()
+        assert (N.keep_mask(rec[pick], r, k) == want[pick]).all(), axis
+
+
+def test_tiled_cubes_refuses_copies_within_a_radius():
+    with pytest.raises(AssertionError):
+        K.tiled_cubes(2, 419)                            # a gap of exactly the radius
+
+
+def test_lattice_box_analytic_mask_and_conditions():
+    shape, origin, n, table = K.LATTICE
+    rec, inside = K.lattice_box()
+    assert rec.shape[0] == n > 1048576
+    xyz = rec[:, :3].astype(np.int64)
+    assert xyz[:, 1].max() == 32767 and xyz[:, 2].min() == -32768                  # both ends of the int16 range occur
+    assert np.unique(xyz, axis=0).shape[0] == n                                      # one record per point: n cells at radius 1
+    assert sorted(np.unique(inside)) == [3, 4, 5, 6]
+    shares = {}
+    for k in (5, 6):
+        want = inside >= k
+        assert (N.keep_mask_dense_box(rec, 1, k) == want).all(), k
+        shares[(1, k)] = 100.0 * want.mean()
+    interior = tuple(e - 4 for e in shape)
+    mask = N.keep_mask_dense_box(rec, 2, 32)
+    assert mask.sum() == interior[0] * interior[1] * interior[2]                   # two layers off every face
+    shares[(2, 32)] = 100.0 * mask.mean()
+    for r, k, share in table:
+        assert abs(shares[(r, k)] - share) <= 0.1, (r, k, shares[(r, k)])
+
+
 # ---- the CLI's flag surface ---------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def central():
