@@ -700,6 +700,85 @@ int pcs_radius_outlier_device_counted(pcs_ctx* ctx, const int16_t* d_payload, co
 int pcs_radius_outlier(pcs_ctx* ctx, const int16_t* payload, int n_points, int radius_mm, int min_neighbors,
                        int16_t* out, size_t out_shorts, int* out_points);   /* host pointers, staged, synchronous */
 
+/* ---- extrinsics refinement: nearest-neighbour alignment sums, the rigid fit, the ICP loop (not in the reference) ---------------- *
+ * transform[i] comes from four surveyed markers (calibration.py); these calls refine it from the data: move one camera's payload
+ * onto another's where they overlap. DESIGN.md section 3 "Alignment sums" has the definition and what follows from it.
+ * SUMS. n_source and n_target records of 5 shorts (0..2 = x, y, z signed int16 mm; colour is not read), max_dist_mm 1..1000. The
+ *   MATCH of source record p is the target record q that minimises (d^2, q.z, q.y, q.x), lexicographic, signed, d^2 =
+ *   (px-qx)^2 + (py-qy)^2 + (pz-qz)^2 in integers of 32 bits or more, among the q with d^2 <= max_dist_mm^2; none: p is unmatched.
+ *   The tie-break is by value: equal target records are interchangeable, the order of neither payload matters, many p may share
+ *   one q. The result is pcs_align_sums, eighteen int64, exact (|p_a q_b| <= 2^30, fewer than 2^28 records: nothing reaches 2^63);
+ *   optionally dist2[i] = the match's d^2 of source record i, 0xFFFFFFFF when unmatched. No floats in these kernels; the same bits on
+ *   every run (tests/np_align.py restates it as brute force).
+ * pcs_align_sums_device: asynchronous on the context's stream, no host round trip: the outlier filter's cell index over the target
+ *   (6 launches), match, reduce. Payload pointers 2-byte aligned, d_sums 8-byte, d_dist2 (optional) 4-byte with room for n_source
+ *   words. *d_sums is written whole (never needs zeroing). n_source == 0 or n_target == 0: a zeroed struct with considered =
+ *   n_source, dist2 all 0xFFFFFFFF. With pcs_kernel_timing one interval per launch (8; 2 with an empty target, 1 with an empty source).
+ * pcs_align_sums: host pointers, staged through the context, synchronous.
+ * SOLVE. pcs_align_solve: host code, no context, errors in pcs_last_error(NULL). With n = matched, C[a][b] = n spq[3a+b] - sp[a] sq[b]
+ *   exactly (128-bit integers), then double: C = U S V^T, R = V diag(1, 1, det(V U^T)) U^T — the proper rotation minimising
+ *   sum |R p + t - q|^2 — and t = qbar - R pbar. delta: row-major 4x4 in METRES (t / 1000), last row 0 0 0 1; *rms_mm (optional) =
+ *   sqrt(sd2 / n). PCS_ERR_UNSUPPORTED when matched < 3, or when C's second singular value is at most 1e-9 of its first (collinear or
+ *   coincident points: the rotation is not unique).
+ * LOOP. pcs_align_payloads_device: T_0 = init in double; for k = 0 ..: F_k = (float)T_k; the source moved by F_k with
+ *   pcs_transform_payloads_device's arithmetic and stride source_stride (FLOOR(n / stride) records; records leaving int16 wrap, as
+ *   there); S_k = sums(moved, target); delta_k = solve(S_k); T_k+1 = delta_k T_k. Stops after `iterations` steps
+ *   (PCS_ALIGN_STOP_ITERATIONS); after the step whose delta has a rotation angle <= eps_rot_rad and a translation <= eps_trans_mm,
+ *   unless both are 0 (PCS_ALIGN_STOP_CONVERGED; that delta is applied); when the solve refuses (PCS_ALIGN_STOP_REFUSED: the call
+ *   returns the solve's status and out = the last good (float)T_k — init if the first solve refused). out = (float)T_K otherwise.
+ *   Synchronous; the target's index is built once; per iteration three launches and one 144-byte copy to the host. The report
+ *   (optional) carries the iterations run, matched / considered / rms of the first and the last of them, the stop reason, and
+ *   — the caller fills trace_capacity, trace_transforms (16 floats each) and trace_sums before the call; NULL / 0: none — F_k and
+ *   S_k of iterations 0 .. min(iterations run, trace_capacity) - 1, trace_count of them.
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the argument), nothing launched, nothing written: a parameter out of range,
+ *   a NULL or misaligned pointer (a payload may be NULL with a count of 0), a count outside 0..INT_MAX/10, any output overlapping an
+ *   input or another output, a non-finite value in init.
+ * These calls read no context predicate (flags, crop box, downsample, PCS_FLAG_SCALAR_ARITH). They know nothing of invalid depth: a
+ *   dense payload's zero-depth pixels sit on the camera origin — align payloads made with PCS_FLAG_DROP_INVALID, or cropped. The
+ *   workspace (the index, 40.2 bytes per target record; the moved source, 10 per source record; 144 per 256 source records) lives in
+ *   the context and grows on demand. A source record costs the population of the cells around it that it cannot rule out;
+ *   source_stride is the lever. Measured: DESIGN.md section 10 (f10).                                                              */
+#define PCS_ALIGN_DIST_MIN         1
+#define PCS_ALIGN_DIST_MAX         1000
+#define PCS_ALIGN_ITERATIONS_MAX   100
+#define PCS_ALIGN_STOP_ITERATIONS  0
+#define PCS_ALIGN_STOP_CONVERGED   1
+#define PCS_ALIGN_STOP_REFUSED     2
+struct pcs_align_sums {     /* (a tag only: pcs_align_sums is also the host form's name, as pcs_compressed_info) */
+    int64_t considered;     /* the source records looked at                    */
+    int64_t matched;        /* the source records that found a match           */
+    int64_t sp[3];          /* sum of p over the matched pairs                 */
+    int64_t sq[3];          /* sum of q                                        */
+    int64_t spq[9];         /* spq[3a+b] = sum of p_a q_b                      */
+    int64_t sd2;            /* sum of d^2                                      */
+};
+typedef struct pcs_align_params {
+    int32_t max_dist_mm;    /* 1..1000 */
+    int32_t iterations;     /* 1..100  */
+    int32_t source_stride;  /* >= 1    */
+    int32_t reserved;       /* 0       */
+    double  eps_rot_rad;    /* >= 0; with eps_trans_mm: both 0 = never stop early */
+    double  eps_trans_mm;   /* >= 0    */
+} pcs_align_params;
+typedef struct pcs_align_report {
+    int32_t iterations;                       /* out: sums computed                                     */
+    int32_t stop_reason;                      /* out: PCS_ALIGN_STOP_*                                  */
+    int64_t first_matched, first_considered;  /* out: of iteration 0                                    */
+    int64_t last_matched, last_considered;    /* out: of the last iteration run                         */
+    double  first_rms_mm, last_rms_mm;        /* out: sqrt(sd2 / matched), 0 with nothing matched       */
+    int32_t trace_capacity;                   /* in                                                     */
+    int32_t trace_count;                      /* out                                                    */
+    float*  trace_transforms;                 /* in, optional: trace_capacity x 16 floats (host)        */
+    struct pcs_align_sums* trace_sums;               /* in, optional: trace_capacity entries (host)            */
+} pcs_align_report;
+int pcs_align_sums_device(pcs_ctx* ctx, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
+                          int max_dist_mm, struct pcs_align_sums* d_sums, uint32_t* d_dist2);
+int pcs_align_sums(pcs_ctx* ctx, const int16_t* source, int n_source, const int16_t* target, int n_target, int max_dist_mm,
+                   struct pcs_align_sums* out, uint32_t* dist2);                  /* host pointers, staged, synchronous */
+int pcs_align_solve(const struct pcs_align_sums* sums, double delta[16], double* rms_mm);
+int pcs_align_payloads_device(pcs_ctx* ctx, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
+                              const pcs_align_params* params, const float init[16], float out[16], pcs_align_report* report);
+
 /* ---- stream / timing plumbing ----------------------------------------------------------- */
 int   pcs_set_stream(pcs_ctx* ctx, void* hip_stream);   /* adopt a caller-owned hipStream_t (NULL = own stream) */
 void* pcs_get_stream(pcs_ctx* ctx);

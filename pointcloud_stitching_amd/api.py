@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (CloudDesc, CompressedInfo, Config, DepthFilterConfig, SpatialFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (AlignParams, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, SpatialFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -55,6 +55,26 @@ def compressed_info(container) -> CompressedInfo:
         d = lib.pcs_last_error(None)
         raise PcsError(rc, d.decode() if d else "")
     return info
+
+
+def _sums_from_c(c: AlignSumsC) -> AlignSums:
+    return AlignSums(int(c.considered), int(c.matched), tuple(int(v) for v in c.sp), tuple(int(v) for v in c.sq),
+                     tuple(int(v) for v in c.spq), int(c.sd2))
+
+
+def align_solve(sums: AlignSums) -> Tuple[np.ndarray, float]:
+    """pcs_align_solve: the rigid fit of one set of alignment sums on the host — no context, no GPU. Returns (delta, rms_mm):
+    delta a float64 [4, 4] in metres that moves the source onto the target. Raises PcsError (PCS_ERR_UNSUPPORTED) with fewer than
+    three matches or a degenerate (collinear, coincident) configuration."""
+    lib = _libmod.load()
+    c = sums.to_c()
+    delta = (C.c_double * 16)()
+    rms = C.c_double(0)
+    rc = lib.pcs_align_solve(C.byref(c), delta, C.byref(rms))
+    if rc != 0:
+        d = lib.pcs_last_error(None)
+        raise PcsError(rc, d.decode() if d else "")
+    return np.array(delta[:], np.float64).reshape(4, 4), float(rms.value)
 
 
 class PcsContext:
@@ -563,6 +583,77 @@ class PcsContext:
         self._check(self._lib.pcs_radius_outlier_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
                                                                 int(radius_mm), int(min_neighbors), d_out or None, out_shorts,
                                                                 d_out_points or None))
+
+    # -- extrinsics refinement (defined by this build; see include/pcs_hip.h) ----------------------
+    def align_sums(self, source: np.ndarray, target: np.ndarray, max_dist_mm: int, want_dist2: bool = False):
+        """Packed records (int16 [n,5]) of two overlapping payloads -> the alignment sums of the source against the target
+        (pcs_align_sums: host arrays, staged, synchronous). With want_dist2: (sums, dist2), dist2 a uint32 array with every source
+        record's squared distance to its match, 0xFFFFFFFF when it has none."""
+        s = np.ascontiguousarray(source, np.int16).reshape(-1, POINT_SHORTS)
+        t = np.ascontiguousarray(target, np.int16).reshape(-1, POINT_SHORTS)
+        out = AlignSumsC()
+        dist2 = np.zeros(max(s.shape[0], 1), np.uint32) if want_dist2 else None
+        self._check(self._lib.pcs_align_sums(self._h, _ptr(s) if s.shape[0] else None, s.shape[0], _ptr(t) if t.shape[0] else None,
+                                             t.shape[0], int(max_dist_mm), C.byref(out), _ptr(dist2) if want_dist2 else None))
+        sums = _sums_from_c(out)
+        return (sums, dist2[:s.shape[0]].copy()) if want_dist2 else sums
+
+    def align_sums_device(self, d_source: int, n_source: int, d_target: int, n_target: int, max_dist_mm: int, d_sums: int,
+                          d_dist2: int = 0) -> None:
+        """Asynchronous; device pointers as ints; *d_sums receives eighteen int64, d_dist2 (optional) n_source uint32. See
+        pcs_align_sums_device."""
+        self._check(self._lib.pcs_align_sums_device(self._h, d_source or None, int(n_source), d_target or None, int(n_target),
+                                                    int(max_dist_mm), d_sums or None, d_dist2 or None))
+
+    def align_payloads_device(self, d_source: int, n_source: int, d_target: int, n_target: int, *, max_dist_mm: int,
+                              iterations: int = 20, source_stride: int = 1, eps_rot_rad: float = 0.0, eps_trans_mm: float = 0.0,
+                              init=None, trace: int = 0) -> Tuple[np.ndarray, AlignReport]:
+        """pcs_align_payloads_device: the ICP loop over two device payloads. Returns (matrix, report): the refined float32 [4, 4]
+        in metres that moves the source onto the target, starting from `init` (identity when None), and an AlignReport. A loop
+        whose solve refused does not raise: report.status is PCS_ERR_UNSUPPORTED, report.stop_reason ALIGN_STOP_REFUSED and the
+        matrix the last good one. trace: how many iterations' F_k and S_k to record."""
+        m0 = np.ascontiguousarray(np.eye(4, dtype=np.float32) if init is None else np.asarray(init, np.float32)).reshape(-1)
+        if m0.size != 16:
+            raise ValueError("init is 16 floats, row-major 4x4")
+        params = AlignParams(int(max_dist_mm), int(iterations), int(source_stride), 0, float(eps_rot_rad), float(eps_trans_mm))
+        out = np.zeros(16, np.float32)
+        ntr = max(int(trace), 0)
+        tf = np.zeros((max(ntr, 1), 16), np.float32)
+        ts = (AlignSumsC * max(ntr, 1))()
+        rep = AlignReportC()
+        rep.trace_capacity = ntr
+        rep.trace_transforms = tf.ctypes.data if ntr else None
+        rep.trace_sums = C.addressof(ts) if ntr else None
+        rc = self._lib.pcs_align_payloads_device(self._h, d_source or None, int(n_source), d_target or None, int(n_target),
+                                                 C.byref(params), m0.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(rep))
+        detail = ""
+        if rc != 0:
+            d = self._lib.pcs_last_error(self._h)
+            detail = d.decode() if d else ""
+            if not (rc == -4 and rep.stop_reason == 2 and rep.iterations > 0):      # anything but a refused solve
+                raise PcsError(rc, detail)
+        n = int(rep.trace_count)
+        report = AlignReport(int(rep.iterations), int(rep.stop_reason), int(rc), detail, int(rep.first_matched), int(rep.first_considered),
+                             int(rep.last_matched), int(rep.last_considered), float(rep.first_rms_mm), float(rep.last_rms_mm),
+                             tf[:n].reshape(n, 4, 4).copy(), [_sums_from_c(ts[k]) for k in range(n)])
+        return out.reshape(4, 4), report
+
+    def align_payloads(self, source: np.ndarray, target: np.ndarray, **kw) -> Tuple[np.ndarray, AlignReport]:
+        """Host-array convenience over align_payloads_device: uploads both payloads (int16 [n,5]), runs the loop, frees them."""
+        s = np.ascontiguousarray(source, np.int16).reshape(-1, POINT_SHORTS)
+        t = np.ascontiguousarray(target, np.int16).reshape(-1, POINT_SHORTS)
+        d_s = self.device_malloc(max(s.nbytes, 16))
+        d_t = self.device_malloc(max(t.nbytes, 16))
+        try:
+            if s.nbytes:
+                self.memcpy_h2d(d_s, s)
+            if t.nbytes:
+                self.memcpy_h2d(d_t, t)
+            return self.align_payloads_device(d_s, s.shape[0], d_t, t.shape[0], **kw)
+        finally:
+            self.device_free(d_s)
+            self.device_free(d_t)
 
     def process_frames_voxel_device(self, d_depth: Sequence[int], d_color: Sequence[int], leaf_mm: int, d_out: int,
                                     out_shorts: int, d_out_points: int = 0) -> None:

@@ -1,0 +1,421 @@
+// pcs_capi_align.cpp — extrinsics refinement's part of the C ABI (include/pcs_hip.h, "extrinsics refinement"): the argument checks,
+// the workspace and the launches of pcs_kernels_align.hip over the outlier filter's index (the definition: DESIGN.md section 3; the
+// kernels: section 5), the rigid fit on the host (pcs_align_solve: exact 128-bit covariance, a one-sided Jacobi SVD in double) and the
+// ICP loop. The calls read no context predicate — flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH do not matter: the loop moves
+// the source through launch_transform_payloads itself, pcs_transform_payloads_device's arithmetic without its context checks.
+
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <exception>
+
+#include "pcs_host.h"
+
+using namespace pcs_host;
+
+using AlignSums = struct pcs_align_sums;          // (the bare name is the host form, a function)
+
+static_assert(sizeof(AlignSums) == kAlignTerms * sizeof(int64_t), "pcs_align_sums is kAlignTerms int64 words, no padding");
+
+namespace {
+
+constexpr int kMaxPoints = INT_MAX / PCS_POINT_BYTES;      // a payload's byte count fits an int32
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// [a, a + na) and [b, b + nb) share a byte
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// What the sums forms and the loop check about their payloads; `who` names the entry point.
+int check_payloads(pcs_ctx* c, const char* who, const void* source, const char* s_name, int n_source, const void* target,
+                   const char* t_name, int n_target, int max_dist_mm)
+{
+    if (max_dist_mm < PCS_ALIGN_DIST_MIN || max_dist_mm > PCS_ALIGN_DIST_MAX)
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: max_dist_mm %d is outside %d..%d", who, max_dist_mm, PCS_ALIGN_DIST_MIN, PCS_ALIGN_DIST_MAX);
+    if (n_source < 0 || n_source > kMaxPoints) return fail(c, PCS_ERR_INVALID_ARG, "%s: n_source %d is outside 0..%d", who, n_source, kMaxPoints);
+    if (n_target < 0 || n_target > kMaxPoints) return fail(c, PCS_ERR_INVALID_ARG, "%s: n_target %d is outside 0..%d", who, n_target, kMaxPoints);
+    if (n_source && !source) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is NULL", who, s_name);
+    if (n_target && !target) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is NULL", who, t_name);
+    if ((uintptr_t)source & 1u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 2-byte aligned", who, s_name);
+    if ((uintptr_t)target & 1u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 2-byte aligned", who, t_name);
+    return PCS_OK;
+}
+
+int check_sums_args(pcs_ctx* c, const char* who, const void* source, const char* s_name, int n_source, const void* target,
+                    const char* t_name, int n_target, int max_dist_mm, const void* sums, const char* sums_name, const void* dist2,
+                    const char* dist2_name)
+{
+    if (int rc = check_payloads(c, who, source, s_name, n_source, target, t_name, n_target, max_dist_mm)) return rc;
+    if (!sums) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is NULL", who, sums_name);
+    if ((uintptr_t)sums & 7u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 8-byte aligned", who, sums_name);
+    if ((uintptr_t)dist2 & 3u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 4-byte aligned", who, dist2_name);
+    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES, db = (size_t)n_source * 4;
+    if (ranges_overlap(sums, sizeof(AlignSums), source, sb) || ranges_overlap(sums, sizeof(AlignSums), target, tb))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s or %s", who, sums_name, s_name, t_name);
+    if (ranges_overlap(dist2, db, source, sb) || ranges_overlap(dist2, db, target, tb))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s or %s", who, dist2_name, s_name, t_name);
+    if (ranges_overlap(dist2, db, sums, sizeof(AlignSums)))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s", who, dist2_name, sums_name);
+    return PCS_OK;
+}
+
+// The align workspace of a context, at least `need` bytes: ensure_outlier_ws's policy (a quarter of headroom when it grows; growing
+// waits for the stream; it never shrinks).
+int ensure_align_ws(pcs_ctx* c, size_t need)
+{
+    if (need <= c->s_align_ws_cap && c->s_align_ws) return PCS_OK;
+    const size_t exact = need;
+    if (c->s_align_ws) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        need += need / 4;
+    }
+    int rc = ensure(c, c->s_align_ws, c->s_align_ws_cap, need);
+    if (rc == PCS_ERR_NOMEM && need != exact) rc = ensure(c, c->s_align_ws, c->s_align_ws_cap, exact);      // the headroom is a wish
+    return rc;
+}
+
+// One call's carve of the workspace: the target's index first (outlier_workspace_bytes(n_target), 256-byte aligned as the slab is),
+// then the partials, then what the form asked for.
+struct AlignWs {
+    void*           index = nullptr;  size_t index_bytes = 0;
+    long long*      partials = nullptr;
+    int16_t*        moved = nullptr;          // the loop's moved source
+    AlignSums* sums = nullptr;           // the loop's / the host form's sums
+    uint32_t*       dist2 = nullptr;          // the host form's dist2
+};
+int carve_align_ws(pcs_ctx* c, int n_source, int n_target, bool want_moved, bool want_sums, bool want_dist2, AlignWs* ws)
+{
+    const size_t index_bytes = n_target ? up256(outlier_workspace_bytes((uint32_t)n_target)) : 0;
+    const size_t part_bytes = up256((size_t)align_partials((uint32_t)n_source) * kAlignTerms * sizeof(long long));
+    const size_t moved_bytes = want_moved ? up256((size_t)n_source * PCS_POINT_BYTES) : 0;
+    const size_t sums_bytes = want_sums ? up256(sizeof(AlignSums)) : 0;
+    const size_t dist2_bytes = want_dist2 ? up256((size_t)n_source * 4) : 0;
+    if (int rc = ensure_align_ws(c, index_bytes + part_bytes + moved_bytes + sums_bytes + dist2_bytes)) return rc;
+    uint8_t* w = static_cast<uint8_t*>(c->s_align_ws);
+    ws->index = w; ws->index_bytes = index_bytes; w += index_bytes;
+    ws->partials = reinterpret_cast<long long*>(w); w += part_bytes;
+    ws->moved = reinterpret_cast<int16_t*>(w); w += moved_bytes;
+    ws->sums = reinterpret_cast<AlignSums*>(w); w += sums_bytes;
+    ws->dist2 = reinterpret_cast<uint32_t*>(w);
+    return PCS_OK;
+}
+
+// Stages 0 to 5 of the outlier filter over the target, cell edge max_dist_mm, one timing bracket per launch; its view into *view.
+// n_target == 0: nothing launched, *have = false.
+int build_index(pcs_ctx* c, const int16_t* d_target, int n_target, int max_dist_mm, const AlignWs& ws, OutlierIndexView* view, bool* have)
+{
+    *have = n_target > 0;
+    if (!*have) return PCS_OK;
+    for (int stage = 0; stage <= 5; stage++) {
+        KernelTimer timer(c);
+        if (timer.rc) return timer.rc;
+        // (min_neighbors: stages 0 to 5 do not read it; 1 passes the launcher's range check)
+        HIPCHK(c, launch_outlier_stage(stage, d_target, (uint32_t)n_target, nullptr, (uint32_t)n_target, max_dist_mm, 1, ws.index,
+                                       ws.index_bytes, nullptr, nullptr, c->stream));
+        if (int rc = timer.finish()) return rc;
+    }
+    HIPCHK(c, outlier_index_view((uint32_t)n_target, ws.index, ws.index_bytes, view));
+    return PCS_OK;
+}
+
+// match + reduce of n_source records at d_source into *d_sums (and d_dist2): two launches, one with an empty source.
+int run_match(pcs_ctx* c, const int16_t* d_source, int n_source, const OutlierIndexView* view, int max_dist_mm, const AlignWs& ws,
+              AlignSums* d_sums, uint32_t* d_dist2)
+{
+    if (n_source) {
+        KernelTimer timer(c);
+        if (timer.rc) return timer.rc;
+        HIPCHK(c, launch_align_match(d_source, (uint32_t)n_source, view, max_dist_mm, ws.partials, d_dist2, c->stream));
+        if (int rc = timer.finish()) return rc;
+    }
+    KernelTimer timer(c);
+    if (timer.rc) return timer.rc;
+    HIPCHK(c, launch_align_reduce(ws.partials, align_partials((uint32_t)n_source), reinterpret_cast<long long*>(d_sums), c->stream));
+    return timer.finish();
+}
+
+// ---- the rigid fit -----------------------------------------------------------------------------------
+// One-sided Jacobi (Hestenes) on the columns of A (3 x 3, row-major): A V -> columns orthogonal, V the accumulated rotations. Then
+// sigma_j = |column j|. Small singular values come out with high relative accuracy, which the degeneracy test below needs (an
+// eigen-decomposition of A^T A would square the condition number past double precision at the 1e-9 threshold).
+void jacobi_columns(double A[9], double V[9])
+{
+    for (int k = 0; k < 9; k++) V[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 60; sweep++) {
+        bool rotated = false;
+        for (int p = 0; p < 2; p++)
+            for (int q = p + 1; q < 3; q++) {
+                double alpha = 0, beta = 0, gamma = 0;
+                for (int i = 0; i < 3; i++) {
+                    alpha += A[3 * i + p] * A[3 * i + p];
+                    beta  += A[3 * i + q] * A[3 * i + q];
+                    gamma += A[3 * i + p] * A[3 * i + q];
+                }
+                if (gamma == 0.0 || std::fabs(gamma) <= 1e-16 * std::sqrt(alpha * beta)) continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = cs * t;
+                for (int i = 0; i < 3; i++) {
+                    const double ap = A[3 * i + p], aq = A[3 * i + q];
+                    A[3 * i + p] = cs * ap - sn * aq;
+                    A[3 * i + q] = sn * ap + cs * aq;
+                    const double vp = V[3 * i + p], vq = V[3 * i + q];
+                    V[3 * i + p] = cs * vp - sn * vq;
+                    V[3 * i + q] = sn * vp + cs * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+}
+
+void cross3(const double a[3], const double b[3], double out[3])
+{
+    out[0] = a[1] * b[2] - a[2] * b[1];
+    out[1] = a[2] * b[0] - a[0] * b[2];
+    out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+bool normalise3(double v[3])
+{
+    const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (!(n > 0)) return false;
+    v[0] /= n; v[1] /= n; v[2] /= n;
+    return true;
+}
+
+int solve_sums(const AlignSums& s, double delta[16], double* rms_mm)
+{
+    static const char who[] = "pcs_align_solve";
+    if (s.matched < 3) return fail(nullptr, PCS_ERR_UNSUPPORTED, "%s: matched %lld < 3: no rigid fit", who, (long long)s.matched);
+    const __int128 n = s.matched;
+    double A[9], V[9], scale = 0;
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            const __int128 cab = n * (__int128)s.spq[3 * a + b] - (__int128)s.sp[a] * (__int128)s.sq[b];     // exact
+            A[3 * a + b] = (double)cab;
+            scale = std::max(scale, std::fabs(A[3 * a + b]));
+        }
+    if (scale == 0.0)
+        return fail(nullptr, PCS_ERR_UNSUPPORTED, "%s: degenerate: the covariance is zero (all matched points of one side coincide)", who);
+    for (double& v : A) v /= scale;
+    jacobi_columns(A, V);              // C / scale = U S V^T with A = U S
+    double sig[3];
+    int order[3] = {0, 1, 2};
+    for (int j = 0; j < 3; j++) sig[j] = std::sqrt(A[j] * A[j] + A[3 + j] * A[3 + j] + A[6 + j] * A[6 + j]);
+    std::sort(order, order + 3, [&](int x, int y) { return sig[x] > sig[y]; });
+    if (!(sig[order[1]] > 1e-9 * sig[order[0]]))
+        return fail(nullptr, PCS_ERR_UNSUPPORTED, "%s: degenerate: the covariance's second singular value is at most 1e-9 of its first "
+                    "(collinear or coincident points): the rotation is not unique", who);
+    // u1, u2, v1, v2 from the two largest singular values; u3 = u1 x u2 and v3 = v1 x v2 make det U = det V = +1, which IS the
+    // diag(1, 1, det(V U^T)) of the definition: flipping u3 or v3 flips that determinant with it, the product v3 u3^T d stays.
+    double u[3][3], v[3][3];
+    for (int k = 0; k < 2; k++) {
+        const int j = order[k];
+        for (int i = 0; i < 3; i++) { u[k][i] = A[3 * i + j] / sig[j]; v[k][i] = V[3 * i + j]; }
+    }
+    const double dot = u[0][0] * u[1][0] + u[0][1] * u[1][1] + u[0][2] * u[1][2];        // (~1e-16: what the sweeps left)
+    for (int i = 0; i < 3; i++) u[1][i] -= dot * u[0][i];
+    if (!normalise3(u[0]) || !normalise3(u[1]) || !normalise3(v[0]) || !normalise3(v[1]))
+        return fail(nullptr, PCS_ERR_UNSUPPORTED, "%s: degenerate: a singular vector vanished", who);
+    cross3(u[0], u[1], u[2]);
+    cross3(v[0], v[1], v[2]);
+    double R[9];
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) R[3 * a + b] = v[0][a] * u[0][b] + v[1][a] * u[1][b] + v[2][a] * u[2][b];
+    const double nd = (double)s.matched;
+    const double pb[3] = {(double)s.sp[0] / nd, (double)s.sp[1] / nd, (double)s.sp[2] / nd};
+    const double qb[3] = {(double)s.sq[0] / nd, (double)s.sq[1] / nd, (double)s.sq[2] / nd};
+    for (int a = 0; a < 3; a++) {
+        const double t_mm = qb[a] - (R[3 * a] * pb[0] + R[3 * a + 1] * pb[1] + R[3 * a + 2] * pb[2]);
+        delta[4 * a] = R[3 * a]; delta[4 * a + 1] = R[3 * a + 1]; delta[4 * a + 2] = R[3 * a + 2];
+        delta[4 * a + 3] = t_mm / 1000.0;
+    }
+    delta[12] = delta[13] = delta[14] = 0.0; delta[15] = 1.0;
+    if (rms_mm) *rms_mm = std::sqrt((double)s.sd2 / nd);
+    return PCS_OK;
+}
+
+double rms_of(const AlignSums& s) { return s.matched > 0 ? std::sqrt((double)s.sd2 / (double)s.matched) : 0.0; }
+
+}  // namespace
+
+extern "C" {
+
+int pcs_align_sums_device(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target, int max_dist_mm,
+                          AlignSums* d_sums, uint32_t* d_dist2)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (int rc = check_sums_args(c, "pcs_align_sums_device", d_source, "d_source", n_source, d_target, "d_target", n_target, max_dist_mm,
+                                 d_sums, "d_sums", d_dist2, "d_dist2"))
+        return rc;
+    DeviceGuard guard(c->device);
+    AlignWs ws;
+    if (int rc = carve_align_ws(c, n_source, n_source ? n_target : 0, false, false, false, &ws)) return rc;
+    OutlierIndexView view{};
+    bool have = false;
+    if (n_source)          // (an empty source needs no index)
+        if (int rc = build_index(c, d_target, n_target, max_dist_mm, ws, &view, &have)) return rc;
+    return run_match(c, d_source, n_source, have ? &view : nullptr, max_dist_mm, ws, d_sums, d_dist2);
+}
+
+int pcs_align_sums(pcs_ctx* c, const int16_t* source, int n_source, const int16_t* target, int n_target, int max_dist_mm,
+                   AlignSums* out, uint32_t* dist2)
+try {
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (int rc = check_sums_args(c, "pcs_align_sums", source, "source", n_source, target, "target", n_target, max_dist_mm, out, "out",
+                                 dist2, "dist2"))
+        return rc;
+    DeviceGuard guard(c->device);
+    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES;
+    // the host forms' payload staging (pcs_voxel_grid's and pcs_radius_outlier's: all synchronous, none leaves anything in it)
+    int rc;
+    if ((rc = ensure_idle(c, c->s_voxel_in, c->s_voxel_in_cap, sb))) return rc;
+    if ((rc = ensure_idle(c, c->s_voxel_out, c->s_voxel_out_cap, tb))) return rc;
+    AlignWs ws;
+    if ((rc = carve_align_ws(c, n_source, n_source ? n_target : 0, false, true, dist2 != nullptr, &ws))) return rc;
+    if (sb) HIPCHK(c, hipMemcpyAsync(c->s_voxel_in, source, sb, hipMemcpyHostToDevice, c->stream));
+    if (tb && n_source) HIPCHK(c, hipMemcpyAsync(c->s_voxel_out, target, tb, hipMemcpyHostToDevice, c->stream));
+    OutlierIndexView view{};
+    bool have = false;
+    if (n_source && (rc = build_index(c, c->s_voxel_out, n_target, max_dist_mm, ws, &view, &have))) return rc;
+    if ((rc = run_match(c, c->s_voxel_in, n_source, have ? &view : nullptr, max_dist_mm, ws, ws.sums, dist2 ? ws.dist2 : nullptr))) return rc;
+    AlignSums got;
+    HIPCHK(c, hipMemcpyAsync(&got, ws.sums, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (dist2 && n_source) HIPCHK(c, hipMemcpy(dist2, ws.dist2, (size_t)n_source * 4, hipMemcpyDeviceToHost));
+    *out = got;
+    return PCS_OK;
+} catch (const std::exception& ex) {
+    return fail(c, PCS_ERR_NOMEM, "pcs_align_sums: host allocation failed (%s)", ex.what());
+}
+
+int pcs_align_solve(const AlignSums* sums, double delta[16], double* rms_mm)
+{
+    if (!sums) return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: sums is NULL");
+    if (!delta) return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: delta is NULL");
+    if (sums->matched < 0 || sums->considered < sums->matched)
+        return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: matched %lld is outside 0..considered %lld", (long long)sums->matched,
+                    (long long)sums->considered);
+    double d[16], rms = 0;
+    if (int rc = solve_sums(*sums, d, &rms)) return rc;
+    std::memcpy(delta, d, sizeof d);
+    if (rms_mm) *rms_mm = rms;
+    return PCS_OK;
+}
+
+int pcs_align_payloads_device(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
+                              const pcs_align_params* params, const float init[16], float out[16], pcs_align_report* report)
+{
+    static const char who[] = "pcs_align_payloads_device";
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (!params) return fail(c, PCS_ERR_INVALID_ARG, "%s: params is NULL", who);
+    if (int rc = check_payloads(c, who, d_source, "d_source", n_source, d_target, "d_target", n_target, params->max_dist_mm)) return rc;
+    if (params->iterations < 1 || params->iterations > PCS_ALIGN_ITERATIONS_MAX)
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: iterations %d is outside 1..%d", who, params->iterations, PCS_ALIGN_ITERATIONS_MAX);
+    if (params->source_stride < 1) return fail(c, PCS_ERR_INVALID_ARG, "%s: source_stride %d < 1", who, params->source_stride);
+    if (!(params->eps_rot_rad >= 0) || !std::isfinite(params->eps_rot_rad))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: eps_rot_rad is negative or not finite", who);
+    if (!(params->eps_trans_mm >= 0) || !std::isfinite(params->eps_trans_mm))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: eps_trans_mm is negative or not finite", who);
+    if (!init) return fail(c, PCS_ERR_INVALID_ARG, "%s: init is NULL", who);
+    if (!out) return fail(c, PCS_ERR_INVALID_ARG, "%s: out is NULL", who);
+    for (int k = 0; k < 16; k++)
+        if (!std::isfinite(init[k])) return fail(c, PCS_ERR_INVALID_ARG, "%s: init[%d] is not finite", who, k);
+    int trace_cap = 0;
+    if (report) {
+        if (report->trace_capacity < 0) return fail(c, PCS_ERR_INVALID_ARG, "%s: report->trace_capacity %d < 0", who, report->trace_capacity);
+        trace_cap = report->trace_capacity;
+    }
+    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES;
+    struct { const void* p; size_t n; const char* name; } outs[] = {
+        {out, 16 * sizeof(float), "out"},
+        {report, report ? sizeof *report : 0, "report"},
+        {report ? report->trace_transforms : nullptr, (size_t)trace_cap * 16 * sizeof(float), "report->trace_transforms"},
+        {report ? report->trace_sums : nullptr, (size_t)trace_cap * sizeof(AlignSums), "report->trace_sums"}};
+    for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) {
+        if (ranges_overlap(outs[i].p, outs[i].n, d_source, sb) || ranges_overlap(outs[i].p, outs[i].n, d_target, tb) ||
+            ranges_overlap(outs[i].p, outs[i].n, init, 16 * sizeof(float)) || ranges_overlap(outs[i].p, outs[i].n, params, sizeof *params))
+            return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps an input", who, outs[i].name);
+        for (size_t j = 0; j < i; j++)
+            if (ranges_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n))
+                return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s", who, outs[i].name, outs[j].name);
+    }
+
+    DeviceGuard guard(c->device);
+    const pcs_align_params P = *params;
+    float* const trace_f = report ? report->trace_transforms : nullptr;
+    AlignSums* const trace_s = report ? report->trace_sums : nullptr;
+    const int n_moved = n_source / P.source_stride;          // FLOOR, pcs_transform_payloads_device's rule
+    AlignWs ws;
+    if (int rc = carve_align_ws(c, n_moved, n_moved ? n_target : 0, true, true, false, &ws)) return rc;
+    OutlierIndexView view{};
+    bool have = false;
+    if (n_moved)
+        if (int rc = build_index(c, d_target, n_target, P.max_dist_mm, ws, &view, &have)) return rc;      // once per call
+
+    double T[16];
+    for (int k = 0; k < 16; k++) T[k] = init[k];
+    pcs_align_report rep{};
+    rep.trace_capacity = trace_cap; rep.trace_transforms = trace_f; rep.trace_sums = trace_s;
+    rep.stop_reason = PCS_ALIGN_STOP_ITERATIONS;
+    int status = PCS_OK;
+    const bool may_stop = P.eps_rot_rad > 0 || P.eps_trans_mm > 0;
+    for (int k = 0; k < P.iterations; k++) {
+        float F[16];
+        for (int j = 0; j < 16; j++) F[j] = (float)T[j];
+        if (n_moved) {
+            XformBatch xb;
+            std::memset(&xb, 0, sizeof xb);
+            xb.c[0].in = d_source;
+            xb.c[0].out = reinterpret_cast<uint8_t*>(ws.moved);
+            xb.c[0].n_out = (uint32_t)n_moved;
+            xb.c[0].ds = (uint32_t)P.source_stride;
+            std::memcpy(xb.c[0].M, F, sizeof xb.c[0].M);
+            KernelTimer timer(c);
+            if (timer.rc) return timer.rc;
+            HIPCHK(c, launch_transform_payloads(xb, 1, (uint32_t)n_moved, c->stream));
+            if (int rc = timer.finish()) return rc;
+        }
+        if (int rc = run_match(c, ws.moved, n_moved, have ? &view : nullptr, P.max_dist_mm, ws, ws.sums, nullptr)) return rc;
+        AlignSums S;
+        HIPCHK(c, hipMemcpyAsync(&S, ws.sums, sizeof S, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (k < trace_cap) {
+            if (trace_f) std::memcpy(trace_f + 16 * (size_t)k, F, sizeof F);
+            if (trace_s) trace_s[k] = S;
+            rep.trace_count = k + 1;
+        }
+        rep.iterations = k + 1;
+        if (k == 0) { rep.first_matched = S.matched; rep.first_considered = S.considered; rep.first_rms_mm = rms_of(S); }
+        rep.last_matched = S.matched; rep.last_considered = S.considered; rep.last_rms_mm = rms_of(S);
+        double D[16];
+        const int rc = solve_sums(S, D, nullptr);
+        if (rc) {
+            // the solve speaks through pcs_last_error(NULL); the loop's caller has a context
+            status = fail(c, rc, "%s: iteration %d: %s", who, k, pcs_last_error(nullptr));
+            rep.stop_reason = PCS_ALIGN_STOP_REFUSED;
+            break;
+        }
+        double N[16];
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) N[4 * a + b] = D[4 * a] * T[b] + D[4 * a + 1] * T[4 + b] + D[4 * a + 2] * T[8 + b] + D[4 * a + 3] * T[12 + b];
+        std::memcpy(T, N, sizeof T);
+        if (may_stop) {
+            // the angle from both the trace and the antisymmetric part: exact for small angles, where acos(trace) is not
+            const double sx = D[9] - D[6], sy = D[2] - D[8], sz = D[4] - D[1];
+            const double angle = std::atan2(0.5 * std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0] + D[5] + D[10] - 1.0));
+            const double trans_mm = 1000.0 * std::sqrt(D[3] * D[3] + D[7] * D[7] + D[11] * D[11]);
+            if (angle <= P.eps_rot_rad && trans_mm <= P.eps_trans_mm) { rep.stop_reason = PCS_ALIGN_STOP_CONVERGED; break; }
+        }
+    }
+    for (int j = 0; j < 16; j++) out[j] = (float)T[j];
+    if (report) *report = rep;
+    return status;
+}
+
+}  // extern "C"

@@ -363,6 +363,27 @@ const char* outlier_stage_name(int stage);
 hipError_t  launch_outlier_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
                                  int radius_mm, int min_neighbors, void* d_ws, size_t ws_bytes, int16_t* d_out, int32_t* d_out_points,
                                  hipStream_t st);
+// What stages 0 to 5 leave in a workspace, for a reader other than the flag kernel (pcs_kernels_align.hip): cell key of slot s in
+// keys[s] (all ones: empty; probe from first_slot, pcs_outlier_index.h), the cell's members at xyz[start[s] .. start[s + 1])
+// (x | y << 16, z), slots + 1 starts. Same arguments as launch_outlier_stage; nothing is launched.
+struct OutlierIndexView {
+    const unsigned long long* keys;
+    const uint32_t*           start;
+    const uint2*              xyz;
+    uint32_t                  slots, capacity;
+};
+hipError_t  outlier_index_view(uint32_t capacity, void* d_ws, size_t ws_bytes, OutlierIndexView* view);
+
+// Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
+// index is the outlier filter's, cell edge max_dist_mm (stages 0 to 5 of launch_outlier_stage over the target; `index` is its view,
+// or nullptr for an empty target: nobody matches). launch_align_match: one lane per source record, one 144-byte partial per
+// workgroup of kBlockThreads records into d_partials[align_partials(n_source)], dist2 (optional) written here.
+// launch_align_reduce: one workgroup sums the partials and writes *d_sums whole (n_partials 0: a zeroed struct).
+constexpr int kAlignTerms = 18;              // pcs_align_sums as int64 words
+inline uint32_t align_partials(uint32_t n_source) { return (n_source + kBlockThreads - 1) / kBlockThreads; }
+hipError_t launch_align_match(const int16_t* d_source, uint32_t n_source, const OutlierIndexView* index, int max_dist_mm,
+                              long long* d_partials, uint32_t* d_dist2, hipStream_t st);
+hipError_t launch_align_reduce(const long long* d_partials, uint32_t n_partials, long long* d_sums, hipStream_t st);
 
 // a7 with stride.
 hipError_t launch_stitch(const int16_t* d_src, uint32_t src_points, int downsample,

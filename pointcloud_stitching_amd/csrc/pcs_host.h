@@ -135,6 +135,11 @@ struct pcs_ctx {
     // n_points / max_points alone (outlier_workspace_bytes), grown on demand the way the voxel workspace is
     void*                           s_outlier_ws = nullptr; size_t s_outlier_ws_cap = 0;
 
+    // alignment sums and the ICP loop (pcs_capi_align.cpp): the target's cell index (the outlier filter's layout), the match
+    // launch's per-workgroup partials, the loop's moved source and sums, the host form's sums and dist2 — one slab carved per call,
+    // grown on demand by ensure_outlier_ws's policy
+    void*                           s_align_ws = nullptr; size_t s_align_ws_cap = 0;
+
     std::string                     err;
 };
 

@@ -33,14 +33,13 @@
 #include <algorithm>
 
 #include "pcs_kernels_common.h"
+#include "pcs_outlier_index.h"
 
 namespace pcs {
 
 namespace {
 
 constexpr uint32_t           kStageBytes = kTilePoints * PCS_POINT_BYTES + 32;   // + head skew + tail pad
-constexpr unsigned long long kEmptyKey   = ~0ull;                                // (a key has 48 bits)
-constexpr uint32_t           kNoSlot     = 0xFFFFFFFFu;
 
 // stage_record / unstage_record / load_staged / store_staged: copies of pcs_kernels.hip's, as unstage_record_crop is one — every
 // existing kernel keeps its code byte for byte (tools/isa_compare.py), so nothing there is routed through a shared helper.
@@ -112,37 +111,7 @@ __device__ __forceinline__ void store_staged(const uint8_t* lds, uint32_t head, 
     }
 }
 
-// ---- cells ------------------------------------------------------------------------------------------
-struct Xyz { int x, y, z; };
-
-// the three coordinate shorts of record i, sign-extended (2-byte loads: a payload may sit at any 2-byte phase)
-__device__ __forceinline__ Xyz load_xyz(const int16_t* __restrict__ in, uint32_t i)
-{
-    const int16_t* p = in + (size_t)i * PCS_POINT_SHORTS;
-    return Xyz{p[0], p[1], p[2]};
-}
-
-// floor(v / r) + 32768 for r >= 1: 0 .. 65535 (C++ division truncates; negative coordinates must floor)
-__device__ __forceinline__ int cell_of(int v, int r)
-{
-    const int q = v / r;
-    return q - (int)(v - q * r < 0) + 32768;
-}
-
-__device__ __forceinline__ unsigned long long cell_key(int cx, int cy, int cz)
-{
-    return (unsigned long long)(uint32_t)cx | (unsigned long long)(uint32_t)cy << 16 | (unsigned long long)(uint32_t)cz << 32;
-}
-
-// where a key's probe sequence starts: a 64-bit finaliser's top bits scaled to [0, slots)
-// (restated in numpy by tests/test_radius_outlier_scale.py, with cell_of, cell_key and outlier_slots, to build a cloud whose probes wrap)
-__device__ __forceinline__ uint32_t first_slot(unsigned long long k, uint32_t slots)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return __umulhi((uint32_t)k, slots);
-}
+// ---- cells: cell_of, cell_key, first_slot, load_xyz and the empty key live in pcs_outlier_index.h (the alignment sums share them) ----
 
 // ---- 0: clear ---------------------------------------------------------------------------------------
 // (d_n non-null: the counted form — the count is read here, when the kernels run, and clamped.) Entry 0 of `tab` is all the scan
@@ -381,6 +350,41 @@ size_t outlier_workspace_bytes(uint32_t capacity)
            2 * up256(4 * (size_t)capacity) + up256(8 * (size_t)capacity) + up256(tiles * kBlockThreads) + 2 * up256(4 * tiles);
 }
 
+namespace {
+
+// Where the pieces of a workspace lie: the one carve launch_outlier_stage and outlier_index_view both read.
+struct OutlierCarve {
+    uint32_t            slots, tiles;
+    OutlierCtl*         ctl;
+    unsigned long long* keys;
+    uint32_t*           count;
+    uint32_t*           sums;
+    uint32_t*           slot_of;
+    uint32_t*           rank;
+    uint2*              xyz;
+    unsigned long long* keep_bits;
+    uint32_t*           tile_counts;
+    uint32_t*           tile_prefix;
+
+    OutlierCarve(uint32_t capacity, void* d_ws) : slots(outlier_slots(capacity)), tiles((capacity + kTilePoints - 1) / kTilePoints)
+    {
+        uint8_t* w = static_cast<uint8_t*>(d_ws);
+        auto carve = [&](size_t bytes) { uint8_t* p = w; w += up256(bytes); return p; };
+        ctl         = reinterpret_cast<OutlierCtl*>(carve(sizeof(OutlierCtl)));
+        keys        = reinterpret_cast<unsigned long long*>(carve(8 * (size_t)slots));
+        count       = reinterpret_cast<uint32_t*>(carve(4 * ((size_t)slots + 1)));
+        sums        = reinterpret_cast<uint32_t*>(carve(4 * (size_t)(slots / kTilePoints)));
+        slot_of     = reinterpret_cast<uint32_t*>(carve(4 * (size_t)capacity));
+        rank        = reinterpret_cast<uint32_t*>(carve(4 * (size_t)capacity));
+        xyz         = reinterpret_cast<uint2*>(carve(8 * (size_t)capacity));
+        keep_bits   = reinterpret_cast<unsigned long long*>(carve((size_t)tiles * kBlockThreads));
+        tile_counts = reinterpret_cast<uint32_t*>(carve(4 * (size_t)tiles));
+        tile_prefix = reinterpret_cast<uint32_t*>(carve(4 * (size_t)tiles));
+    }
+};
+
+}  // namespace
+
 const char* outlier_stage_name(int stage)
 {
     static const char* const names[kOutlierStages] = {"clear", "insert", "cell sums", "cell scan", "cell starts", "scatter", "flag",
@@ -395,19 +399,13 @@ hipError_t launch_outlier_stage(int stage, const int16_t* d_in, uint32_t n_point
     if (!capacity || radius_mm < 1 || radius_mm > 1000 || min_neighbors < 1 || min_neighbors > 255 || ws_bytes < outlier_workspace_bytes(capacity) ||
         ((uintptr_t)d_ws & 255u) || (!d_n_points && n_points > capacity))
         return hipErrorInvalidValue;
-    const uint32_t slots = outlier_slots(capacity), tiles = (capacity + kTilePoints - 1) / kTilePoints;
-    uint8_t* w = static_cast<uint8_t*>(d_ws);
-    auto carve = [&](size_t bytes) { uint8_t* p = w; w += up256(bytes); return p; };
-    OutlierCtl* ctl        = reinterpret_cast<OutlierCtl*>(carve(sizeof(OutlierCtl)));
-    auto*     keys         = reinterpret_cast<unsigned long long*>(carve(8 * (size_t)slots));
-    uint32_t* count        = reinterpret_cast<uint32_t*>(carve(4 * ((size_t)slots + 1)));
-    uint32_t* sums         = reinterpret_cast<uint32_t*>(carve(4 * (size_t)(slots / kTilePoints)));
-    uint32_t* slot_of      = reinterpret_cast<uint32_t*>(carve(4 * (size_t)capacity));
-    uint32_t* rank         = reinterpret_cast<uint32_t*>(carve(4 * (size_t)capacity));
-    uint2*    xyz          = reinterpret_cast<uint2*>(carve(8 * (size_t)capacity));
-    auto*     keep_bits    = reinterpret_cast<unsigned long long*>(carve((size_t)tiles * kBlockThreads));
-    uint32_t* tile_counts  = reinterpret_cast<uint32_t*>(carve(4 * (size_t)tiles));
-    uint32_t* tile_prefix  = reinterpret_cast<uint32_t*>(carve(4 * (size_t)tiles));
+    const OutlierCarve cv(capacity, d_ws);
+    const uint32_t slots = cv.slots, tiles = cv.tiles;
+    OutlierCtl* const ctl = cv.ctl;
+    unsigned long long* const keys = cv.keys, * const keep_bits = cv.keep_bits;
+    uint32_t* const count = cv.count, * const sums = cv.sums, * const slot_of = cv.slot_of, * const rank = cv.rank,
+            * const tile_counts = cv.tile_counts, * const tile_prefix = cv.tile_prefix;
+    uint2* const xyz = cv.xyz;
     const dim3 per_record((capacity + kBlockThreads - 1) / kBlockThreads), per_slot_tile(slots / kTilePoints), block(kBlockThreads);
     switch (stage) {
     case 0:
@@ -446,6 +444,14 @@ hipError_t launch_outlier_stage(int stage, const int16_t* d_in, uint32_t n_point
         return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t outlier_index_view(uint32_t capacity, void* d_ws, size_t ws_bytes, OutlierIndexView* view)
+{
+    if (!capacity || !view || ws_bytes < outlier_workspace_bytes(capacity) || ((uintptr_t)d_ws & 255u)) return hipErrorInvalidValue;
+    const OutlierCarve cv(capacity, d_ws);
+    *view = OutlierIndexView{cv.keys, cv.count, cv.xyz, cv.slots, capacity};
+    return hipSuccess;
 }
 
 }  // namespace pcs

@@ -6,7 +6,8 @@ rs2_extrinsics so a librealsense binding can memcpy).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, Optional, Sequence
+from dataclasses import dataclass, field
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -26,6 +27,13 @@ FLAG_SCALAR_ARITH = 0x20            # the reference's default (no -m) arithmetic
 OUTLIER_RADIUS_MIN, OUTLIER_RADIUS_MAX = 1, 1000          # pcs_radius_outlier*: radius_mm
 OUTLIER_NEIGHBORS_MIN, OUTLIER_NEIGHBORS_MAX = 1, 255     # ... min_neighbors
 OUTLIER_LAUNCHES = 10                                     # intervals one call adds to kernel_times_ms under kernel_timing
+
+ALIGN_DIST_MIN, ALIGN_DIST_MAX = 1, 1000                  # pcs_align_*: max_dist_mm
+ALIGN_ITERATIONS_MAX = 100
+ALIGN_STOP_ITERATIONS, ALIGN_STOP_CONVERGED, ALIGN_STOP_REFUSED = 0, 1, 2
+ALIGN_INDEX_LAUNCHES = 6                                  # kernel_times_ms intervals: the target's index, once per call
+ALIGN_SUMS_LAUNCHES = 8                                   # ... one align_sums call (index, match, reduce)
+ALIGN_ITERATION_LAUNCHES = 3                              # ... one iteration of the loop (transform, match, reduce)
 
 DISTORTION_NONE = 0
 DISTORTION_MODIFIED_BROWN_CONRADY = 1
@@ -98,6 +106,78 @@ class SpatialFilterConfig(C.Structure):
 class CompressedInfo(C.Structure):
     """pcs_compressed_info: what the validator reads from a "PCZ1" container's header."""
     _fields_ = [("n_points", C.c_uint32), ("n_blocks", C.c_uint32), ("total_bytes", C.c_uint32), ("data_offset", C.c_uint32)]
+
+
+class AlignSumsC(C.Structure):
+    """struct pcs_align_sums: eighteen int64."""
+    _fields_ = [("considered", C.c_int64), ("matched", C.c_int64), ("sp", C.c_int64 * 3), ("sq", C.c_int64 * 3),
+                ("spq", C.c_int64 * 9), ("sd2", C.c_int64)]
+
+
+class AlignParams(C.Structure):
+    """pcs_align_params."""
+    _fields_ = [("max_dist_mm", C.c_int32), ("iterations", C.c_int32), ("source_stride", C.c_int32), ("reserved", C.c_int32),
+                ("eps_rot_rad", C.c_double), ("eps_trans_mm", C.c_double)]
+
+
+class AlignReportC(C.Structure):
+    """pcs_align_report."""
+    _fields_ = [("iterations", C.c_int32), ("stop_reason", C.c_int32),
+                ("first_matched", C.c_int64), ("first_considered", C.c_int64),
+                ("last_matched", C.c_int64), ("last_considered", C.c_int64),
+                ("first_rms_mm", C.c_double), ("last_rms_mm", C.c_double),
+                ("trace_capacity", C.c_int32), ("trace_count", C.c_int32),
+                ("trace_transforms", C.c_void_p), ("trace_sums", C.c_void_p)]
+
+
+@dataclass(frozen=True)
+class AlignSums:
+    """The alignment sums of one correspondence step (Python integers: exact)."""
+    considered: int
+    matched: int
+    sp: Tuple[int, int, int]
+    sq: Tuple[int, int, int]
+    spq: Tuple[int, ...]          # spq[3a+b] = sum of p_a q_b
+    sd2: int
+
+    def as_array(self) -> np.ndarray:
+        """The eighteen int64 words in struct order."""
+        return np.array([self.considered, self.matched, *self.sp, *self.sq, *self.spq, self.sd2], dtype=np.int64)
+
+    @classmethod
+    def from_array(cls, a) -> "AlignSums":
+        v = [int(x) for x in np.asarray(a).reshape(-1)]
+        if len(v) != 18:
+            raise ValueError("alignment sums are 18 integers")
+        return cls(v[0], v[1], tuple(v[2:5]), tuple(v[5:8]), tuple(v[8:17]), v[17])
+
+    def to_c(self) -> AlignSumsC:
+        c = AlignSumsC()
+        c.considered, c.matched, c.sd2 = self.considered, self.matched, self.sd2
+        for k in range(3):
+            c.sp[k], c.sq[k] = self.sp[k], self.sq[k]
+        for k in range(9):
+            c.spq[k] = self.spq[k]
+        return c
+
+
+@dataclass
+class AlignReport:
+    """What pcs_align_payloads_device reports: the iterations run, the first and the last of them, why it stopped, the status the
+    call returned (0, or PCS_ERR_UNSUPPORTED when a solve refused) and the trace: F_k [n, 4, 4] float32 and S_k of every recorded
+    iteration."""
+    iterations: int
+    stop_reason: int
+    status: int
+    detail: str
+    first_matched: int
+    first_considered: int
+    last_matched: int
+    last_considered: int
+    first_rms_mm: float
+    last_rms_mm: float
+    trace_transforms: np.ndarray = field(default_factory=lambda: np.zeros((0, 4, 4), np.float32))
+    trace_sums: List[AlignSums] = field(default_factory=list)
 
 
 # --- the reference's surveyed extrinsics (data, not code) -------------------------------------
