@@ -779,6 +779,126 @@ int pcs_align_solve(const struct pcs_align_sums* sums, double delta[16], double*
 int pcs_align_payloads_device(pcs_ctx* ctx, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
                               const pcs_align_params* params, const float init[16], float out[16], pcs_align_report* report);
 
+/* ---- surface normals of a packed payload (not in the reference; modelled on PCL's NormalEstimation, parity unpinned) ------------- *
+ * n_points records of 5 shorts (0..2 = x, y, z signed int16 mm; colour is not read). The NEIGHBOURHOOD of record q is every record x
+ * of the payload with |x - q|^2 <= radius_mm^2 in integers of 32 bits or more — q itself and records equal to it included; m is its
+ * size. With delta = x - q: S1 = sum delta, S2 = sum delta delta^T (int64, exact), C = m S2 - S1 S1^T formed exactly in 128-bit
+ * integers and converted to double once; lambda0 <= lambda1 <= lambda2 and their unit eigenvectors from a cyclic Jacobi
+ * eigen-decomposition in double on the device; v = the eigenvector of lambda0. DESIGN.md section 3 "Surface normals" has the
+ * definition and what follows from it. A record is INVALID when m < min_neighbors, or lambda1 <= 1e-12 lambda2 (collinear or
+ * coincident neighbours), or flatness > 0 and flatness lambda0 > lambda1 (the neighbourhood is not flat enough to call it a plane).
+ * The sign of v: with use_viewpoint, v . (viewpoint_mm - q) >= 0 (at exactly 0 the rule below decides); without, the component of
+ * largest magnitude is positive, ties preferring z, then y, then x.
+ * Output: 4 shorts per record in record order — rint(16384 v_x), rint(16384 v_y), rint(16384 v_z), min(m, 32767) — or four zero
+ * shorts for an invalid record (short 3 is never 0 for a valid one). A record's shorts are a function of its coordinates and the
+ * payload as a multiset: equal records get equal shorts, the payload's order does not matter, every run gives the same bytes
+ * (tests/np_normals.py restates the definition with numpy's eigh; the two agree to one unit of a short).
+ * pcs_estimate_normals_device: asynchronous on the context's stream, no host round trip: the outlier filter's cell index over the
+ *   payload with cell edge radius_mm (6 launches), estimate (one lane per record in cell order), gather (back to record order).
+ *   d_payload 2-byte aligned; d_normals 8-byte aligned with room for 4 n_points shorts; *d_valid (optional, device, 4-byte aligned)
+ *   receives the number of valid records. n_points 0 launches nothing and writes a zero count. With pcs_kernel_timing one
+ *   interval per launch (8).
+ * pcs_estimate_normals: host pointers, staged through the context, synchronous.
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the argument), nothing launched, nothing written: a parameter out of range
+ *   (radius_mm 1..1000, min_neighbors 3..32767, flatness 0..1000, use_viewpoint 0 or 1, reserved 0), a NULL, odd or misaligned
+ *   pointer (payload and output may be NULL with a count of 0), a count outside 0..INT_MAX/10, any overlap of the ranges.
+ * Works on every context: flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH are not read. The calls know nothing of invalid
+ *   depth (a dense payload's zero-depth pixels sit on the camera origin): use payloads made with PCS_FLAG_DROP_INVALID, or cropped.
+ *   The workspace (the index, 40.2 bytes per record, and 8 more) lives in the context and grows on demand. A record costs the
+ *   population of the cells around it that it cannot rule out; there is no early exit, n identical records cost n^2 tests.          */
+#define PCS_NORMAL_RADIUS_MIN      1
+#define PCS_NORMAL_RADIUS_MAX      1000
+#define PCS_NORMAL_NEIGHBORS_MIN   3
+#define PCS_NORMAL_NEIGHBORS_MAX   32767
+#define PCS_NORMAL_FLATNESS_MAX    1000
+#define PCS_NORMAL_SHORTS          4
+#define PCS_NORMAL_BYTES           8
+typedef struct pcs_normal_params {
+    int32_t radius_mm;        /* 1..1000                                                     */
+    int32_t min_neighbors;    /* 3..32767: the neighbourhood's least size, the record included */
+    int32_t flatness;         /* 0 = off, else 1..1000: invalid when flatness lambda0 > lambda1 */
+    int32_t use_viewpoint;    /* 0 or 1                                                      */
+    int32_t viewpoint_mm[3];  /* the point valid normals are turned towards                  */
+    int32_t reserved;         /* 0                                                           */
+} pcs_normal_params;
+int pcs_estimate_normals_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const pcs_normal_params* params,
+                                int16_t* d_normals, int32_t* d_valid);
+int pcs_estimate_normals(pcs_ctx* ctx, const int16_t* payload, int n_points, const pcs_normal_params* params,
+                         int16_t* normals, int* valid);                           /* host pointers, staged, synchronous */
+
+/* ---- extrinsics refinement, point to plane: plane sums, the 6 x 6 solve, the loop (not in the reference) ------------------------ *
+ * Point-to-point alignment of two independent samples of a surface ends at the sampling pitch; against the target's surface normals
+ * it ends far below it. DESIGN.md section 3 "Plane sums" has the definitions and what follows from them.
+ * SUMS. Source and target payloads and max_dist_mm as for pcs_align_sums_device, plus target_normals: 4 shorts per target record,
+ *   8-byte aligned, what pcs_estimate_normals_device writes — or any int16 values, the call does not check them; a target record
+ *   has a valid normal iff its short 3 != 0. The MATCH of source record p is pcs_align_sums_device's, exactly. The NORMAL of a match
+ *   is the smallest valid four-short word, compared as one unsigned 64-bit little-endian number, among the target records whose
+ *   coordinates equal the match's; none: the pair is matched but not USED. By value: neither payload's order reaches the result.
+ *   Per used pair, in integers: n = the word's first three shorts, c = p x n, a = (c_x, c_y, c_z, n_x, n_y, n_z), b = n . (q - p).
+ *   Every a_i a_j, a_i b and b^2 fits int64 (|c| < 2^31) but their sums over a payload do not: each product t is summed as two
+ *   halves, lo = t & 0xFFFFFFFF (unsigned) and hi = t >> 32 (arithmetic), each below 2^60 for fewer than 2^28 records; the value is
+ *   hi 2^32 + lo in 128 bits. The result is pcs_align_plane_sums, sixty int64, exact, the same bits on every run
+ *   (tests/np_align_plane.py restates it); dist2 as pcs_align_sums_device's, over the matched pairs whether used or not.
+ * pcs_align_plane_sums_device: asynchronous on the context's stream, no host round trip: the index over the target (6 launches), the
+ *   normals scattered into cell order, match, reduce. *d_sums (8-byte aligned) is written whole. n_source == 0 or n_target == 0: a
+ *   zeroed struct with considered = n_source. With pcs_kernel_timing one interval per launch (9; 2 with an empty target, 1 with an
+ *   empty source). pcs_align_plane_sums: host pointers, staged through the context, synchronous.
+ * SOLVE. pcs_align_plane_solve: host code, no context, errors in pcs_last_error(NULL). The sums recombined in 128-bit integers, then
+ *   double; A^T A scaled symmetrically to a unit diagonal; a Jacobi eigen-decomposition of the scaled 6 x 6; x = (omega, t) solves
+ *   A^T A x = A^T b. delta: rotation exp([omega]x) (Rodrigues, a series below 1e-4 rad), translation t / 1000 METRES, row-major 4x4,
+ *   last row 0 0 0 1; *rms_mm (optional) = sqrt(sb2 / used) / 16384, the distance to the planes. PCS_ERR_UNSUPPORTED when used < 6,
+ *   when a diagonal entry is zero, or when the scaled matrix's smallest eigenvalue is at most 1e-9 of its largest: the pose is not
+ *   determined — a target that is one plane, or parallel planes, is the case users meet.
+ * LOOP. pcs_align_payloads_plane_device: pcs_align_payloads_device's loop with the plane sums and the plane solve. The target's
+ *   normals are estimated once per call (params->normals; their sign does not matter), the index is built and the normals scattered
+ *   once; per iteration three launches (transform, match, reduce) and one 480-byte copy to the host. The stop rules, the refusals
+ *   and out = the last good (float)T_k are pcs_align_payloads_device's; the report carries `used` beside `matched`, and its rms is
+ *   still sqrt(sd2 / matched). With pcs_kernel_timing: 15 intervals once, 3 per iteration.
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the argument), nothing launched, nothing written: as the point-to-point
+ *   calls, and a NULL or misaligned d_target_normals (it may be NULL with n_target 0), a normal parameter out of range.            */
+struct pcs_align_plane_sums {   /* (a tag only, as pcs_align_sums) */
+    int64_t considered;         /* the source records looked at                                  */
+    int64_t matched;            /* ... that found a match                                        */
+    int64_t used;               /* ... whose match has a valid normal                            */
+    int64_t ata_lo[21];         /* sum of (a_i a_j) & 0xFFFFFFFF, upper triangle row-major        */
+    int64_t ata_hi[21];         /* sum of (a_i a_j) >> 32                                        */
+    int64_t atb_lo[6];          /* sum of (a_i b) & 0xFFFFFFFF                                   */
+    int64_t atb_hi[6];          /* sum of (a_i b) >> 32                                          */
+    int64_t sb2_lo, sb2_hi;     /* sum of b^2, likewise                                          */
+    int64_t sd2;                /* sum of d^2 over the matched pairs                             */
+};
+typedef struct pcs_align_plane_params {
+    int32_t max_dist_mm;        /* 1..1000 */
+    int32_t iterations;         /* 1..100  */
+    int32_t source_stride;      /* >= 1    */
+    int32_t reserved;           /* 0       */
+    double  eps_rot_rad;        /* >= 0; with eps_trans_mm: both 0 = never stop early */
+    double  eps_trans_mm;       /* >= 0    */
+    pcs_normal_params normals;  /* how the target's normals are estimated             */
+} pcs_align_plane_params;
+typedef struct pcs_align_plane_report {
+    int32_t iterations;                                   /* out: sums computed                               */
+    int32_t stop_reason;                                  /* out: PCS_ALIGN_STOP_*                            */
+    int64_t first_matched, first_used, first_considered;  /* out: of iteration 0                              */
+    int64_t last_matched, last_used, last_considered;     /* out: of the last iteration run                   */
+    double  first_rms_mm, last_rms_mm;                    /* out: sqrt(sd2 / matched), 0 with nothing matched */
+    int32_t trace_capacity;                               /* in                                               */
+    int32_t trace_count;                                  /* out                                              */
+    float*  trace_transforms;                             /* in, optional: trace_capacity x 16 floats (host)  */
+    struct pcs_align_plane_sums* trace_sums;              /* in, optional: trace_capacity entries (host)      */
+} pcs_align_plane_report;
+#define PCS_ALIGN_PLANE_USED_MIN   6
+int pcs_align_plane_sums_device(pcs_ctx* ctx, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
+                                const int16_t* d_target_normals, int max_dist_mm, struct pcs_align_plane_sums* d_sums,
+                                uint32_t* d_dist2);
+int pcs_align_plane_sums(pcs_ctx* ctx, const int16_t* source, int n_source, const int16_t* target, int n_target,
+                         const int16_t* target_normals, int max_dist_mm, struct pcs_align_plane_sums* out,
+                         uint32_t* dist2);                                        /* host pointers, staged, synchronous */
+int pcs_align_plane_solve(const struct pcs_align_plane_sums* sums, double delta[16], double* rms_mm);
+int pcs_align_payloads_plane_device(pcs_ctx* ctx, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
+                                    const pcs_align_plane_params* params, const float init[16], float out[16],
+                                    pcs_align_plane_report* report);
+
 /* ---- stream / timing plumbing ----------------------------------------------------------- */
 int   pcs_set_stream(pcs_ctx* ctx, void* hip_stream);   /* adopt a caller-owned hipStream_t (NULL = own stream) */
 void* pcs_get_stream(pcs_ctx* ctx);

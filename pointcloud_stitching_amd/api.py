@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (AlignParams, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, SpatialFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, SpatialFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -71,6 +71,25 @@ def align_solve(sums: AlignSums) -> Tuple[np.ndarray, float]:
     delta = (C.c_double * 16)()
     rms = C.c_double(0)
     rc = lib.pcs_align_solve(C.byref(c), delta, C.byref(rms))
+    if rc != 0:
+        d = lib.pcs_last_error(None)
+        raise PcsError(rc, d.decode() if d else "")
+    return np.array(delta[:], np.float64).reshape(4, 4), float(rms.value)
+
+
+def _plane_sums_from_c(c: AlignPlaneSumsC) -> AlignPlaneSums:
+    return AlignPlaneSums.from_array(np.frombuffer(bytes(c), np.int64))
+
+
+def align_plane_solve(sums: AlignPlaneSums) -> Tuple[np.ndarray, float]:
+    """pcs_align_plane_solve: the point-to-plane step of one set of plane sums on the host — no context, no GPU. Returns
+    (delta, rms_mm): delta a float64 [4, 4] in metres that moves the source towards the target's planes, rms_mm the distance to
+    them. Raises PcsError (PCS_ERR_UNSUPPORTED) with fewer than six used pairs or normals that do not determine the pose."""
+    lib = _libmod.load()
+    c = sums.to_c()
+    delta = (C.c_double * 16)()
+    rms = C.c_double(0)
+    rc = lib.pcs_align_plane_solve(C.byref(c), delta, C.byref(rms))
     if rc != 0:
         d = lib.pcs_last_error(None)
         raise PcsError(rc, d.decode() if d else "")
@@ -584,6 +603,28 @@ class PcsContext:
                                                                 int(radius_mm), int(min_neighbors), d_out or None, out_shorts,
                                                                 d_out_points or None))
 
+    # -- surface normals (defined by this build; see include/pcs_hip.h) -----------------------------
+    def estimate_normals(self, payload: np.ndarray, radius_mm: int, min_neighbors: int, flatness: int = 0, viewpoint_mm=None,
+                         want_valid: bool = False):
+        """Packed records (int16 [n,5]) -> int16 [n,4]: every record's unit normal times 16384 and its neighbour count, four zeros
+        where it has none (pcs_estimate_normals: host arrays, staged, synchronous). viewpoint_mm: the point valid normals are
+        turned towards (None: the component of largest magnitude is positive). With want_valid: (normals, valid count)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        out = np.zeros((max(p.shape[0], 1), NORMAL_SHORTS), np.int16)
+        params = NormalParams.make(radius_mm, min_neighbors, flatness, viewpoint_mm)
+        cnt = C.c_int(-1)
+        self._check(self._lib.pcs_estimate_normals(self._h, _ptr(p) if p.shape[0] else None, p.shape[0], C.byref(params),
+                                                   _ptr(out) if p.shape[0] else None, C.byref(cnt)))
+        out = out[:p.shape[0]].copy()
+        return (out, int(cnt.value)) if want_valid else out
+
+    def estimate_normals_device(self, d_payload: int, n_points: int, params: NormalParams, d_normals: int, d_valid: int = 0) -> None:
+        """Asynchronous; device pointers as ints; d_normals receives 4 n_points int16, *d_valid (optional, int32) the number of
+        valid records. params: NormalParams.make(radius_mm, min_neighbors, flatness, viewpoint_mm). See
+        pcs_estimate_normals_device."""
+        self._check(self._lib.pcs_estimate_normals_device(self._h, d_payload or None, int(n_points), C.byref(params) if params is not None else None,
+                                                          d_normals or None, d_valid or None))
+
     # -- extrinsics refinement (defined by this build; see include/pcs_hip.h) ----------------------
     def align_sums(self, source: np.ndarray, target: np.ndarray, max_dist_mm: int, want_dist2: bool = False):
         """Packed records (int16 [n,5]) of two overlapping payloads -> the alignment sums of the source against the target
@@ -651,6 +692,87 @@ class PcsContext:
             if t.nbytes:
                 self.memcpy_h2d(d_t, t)
             return self.align_payloads_device(d_s, s.shape[0], d_t, t.shape[0], **kw)
+        finally:
+            self.device_free(d_s)
+            self.device_free(d_t)
+
+    # -- extrinsics refinement, point to plane (defined by this build; see include/pcs_hip.h) -------
+    def align_plane_sums(self, source: np.ndarray, target: np.ndarray, target_normals: np.ndarray, max_dist_mm: int,
+                         want_dist2: bool = False):
+        """Packed records (int16 [n,5]) of two overlapping payloads and the target's normals (int16 [m,4], what estimate_normals
+        returns) -> the point-to-plane sums of the source against the target (pcs_align_plane_sums: host arrays, staged,
+        synchronous). With want_dist2: (sums, dist2) as align_sums."""
+        s = np.ascontiguousarray(source, np.int16).reshape(-1, POINT_SHORTS)
+        t = np.ascontiguousarray(target, np.int16).reshape(-1, POINT_SHORTS)
+        nrm = np.ascontiguousarray(target_normals, np.int16).reshape(-1, NORMAL_SHORTS)
+        if nrm.shape[0] != t.shape[0]:
+            raise ValueError("target_normals needs one row of four shorts per target record")
+        if nrm.shape[0] and nrm.ctypes.data % 8:
+            buf = np.empty(nrm.size + 4, np.int16)                     # (a view at an odd offset: copy to an 8-byte aligned place)
+            off = (-buf.ctypes.data % 8) // 2
+            buf[off:off + nrm.size] = nrm.reshape(-1)
+            nrm = buf[off:off + nrm.size].reshape(-1, NORMAL_SHORTS)
+        out = AlignPlaneSumsC()
+        dist2 = np.zeros(max(s.shape[0], 1), np.uint32) if want_dist2 else None
+        self._check(self._lib.pcs_align_plane_sums(self._h, _ptr(s) if s.shape[0] else None, s.shape[0], _ptr(t) if t.shape[0] else None,
+                                                   t.shape[0], nrm.ctypes.data if t.shape[0] else None, int(max_dist_mm), C.byref(out),
+                                                   _ptr(dist2) if want_dist2 else None))
+        sums = _plane_sums_from_c(out)
+        return (sums, dist2[:s.shape[0]].copy()) if want_dist2 else sums
+
+    def align_plane_sums_device(self, d_source: int, n_source: int, d_target: int, n_target: int, d_target_normals: int, max_dist_mm: int,
+                                d_sums: int, d_dist2: int = 0) -> None:
+        """Asynchronous; device pointers as ints; d_target_normals 4 n_target int16 (8-byte aligned); *d_sums receives sixty
+        int64, d_dist2 (optional) n_source uint32. See pcs_align_plane_sums_device."""
+        self._check(self._lib.pcs_align_plane_sums_device(self._h, d_source or None, int(n_source), d_target or None, int(n_target),
+                                                          d_target_normals or None, int(max_dist_mm), d_sums or None, d_dist2 or None))
+
+    def align_payloads_plane_device(self, d_source: int, n_source: int, d_target: int, n_target: int, *, max_dist_mm: int,
+                                    normals: NormalParams, iterations: int = 6, source_stride: int = 1, eps_rot_rad: float = 0.0,
+                                    eps_trans_mm: float = 0.0, init=None, trace: int = 0) -> Tuple[np.ndarray, AlignPlaneReport]:
+        """pcs_align_payloads_plane_device: the point-to-plane loop over two device payloads; `normals` (NormalParams.make(...))
+        says how the target's normals are estimated. Returns (matrix, report) as align_payloads_device; a loop whose solve refused
+        does not raise."""
+        m0 = np.ascontiguousarray(np.eye(4, dtype=np.float32) if init is None else np.asarray(init, np.float32)).reshape(-1)
+        if m0.size != 16:
+            raise ValueError("init is 16 floats, row-major 4x4")
+        params = AlignPlaneParams(int(max_dist_mm), int(iterations), int(source_stride), 0, float(eps_rot_rad), float(eps_trans_mm), normals)
+        out = np.zeros(16, np.float32)
+        ntr = max(int(trace), 0)
+        tf = np.zeros((max(ntr, 1), 16), np.float32)
+        ts = (AlignPlaneSumsC * max(ntr, 1))()
+        rep = AlignPlaneReportC()
+        rep.trace_capacity = ntr
+        rep.trace_transforms = tf.ctypes.data if ntr else None
+        rep.trace_sums = C.addressof(ts) if ntr else None
+        rc = self._lib.pcs_align_payloads_plane_device(self._h, d_source or None, int(n_source), d_target or None, int(n_target),
+                                                       C.byref(params), m0.ctypes.data_as(C.POINTER(C.c_float)),
+                                                       out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(rep))
+        detail = ""
+        if rc != 0:
+            d = self._lib.pcs_last_error(self._h)
+            detail = d.decode() if d else ""
+            if not (rc == -4 and rep.stop_reason == 2 and rep.iterations > 0):      # anything but a refused solve
+                raise PcsError(rc, detail)
+        n = int(rep.trace_count)
+        report = AlignPlaneReport(int(rep.iterations), int(rep.stop_reason), int(rc), detail, int(rep.first_matched), int(rep.first_used),
+                                  int(rep.first_considered), int(rep.last_matched), int(rep.last_used), int(rep.last_considered),
+                                  float(rep.first_rms_mm), float(rep.last_rms_mm), tf[:n].reshape(n, 4, 4).copy(),
+                                  [_plane_sums_from_c(ts[k]) for k in range(n)])
+        return out.reshape(4, 4), report
+
+    def align_payloads_plane(self, source: np.ndarray, target: np.ndarray, **kw) -> Tuple[np.ndarray, AlignPlaneReport]:
+        """Host-array convenience over align_payloads_plane_device: uploads both payloads (int16 [n,5]), runs the loop, frees them."""
+        s = np.ascontiguousarray(source, np.int16).reshape(-1, POINT_SHORTS)
+        t = np.ascontiguousarray(target, np.int16).reshape(-1, POINT_SHORTS)
+        d_s = self.device_malloc(max(s.nbytes, 16))
+        d_t = self.device_malloc(max(t.nbytes, 16))
+        try:
+            if s.nbytes:
+                self.memcpy_h2d(d_s, s)
+            if t.nbytes:
+                self.memcpy_h2d(d_t, t)
+            return self.align_payloads_plane_device(d_s, s.shape[0], d_t, t.shape[0], **kw)
         finally:
             self.device_free(d_s)
             self.device_free(d_t)

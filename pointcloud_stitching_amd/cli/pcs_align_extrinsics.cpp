@@ -1,15 +1,21 @@
 // pcs-align-extrinsics — refine the extrinsics of a multi-camera rig from the cameras' own payloads (include/pcs_hip.h:
-// pcs_align_payloads_device; DESIGN.md section 3 "Alignment sums"). Sits between calibration.py, which places every camera from four
-// surveyed markers, and the -T of pcs-multicamera-optimized, which consumes one matrix per camera:
+// pcs_align_payloads_device, pcs_align_payloads_plane_device; DESIGN.md section 3 "Alignment sums", "Plane sums"). Sits between
+// calibration.py, which places every camera from four surveyed markers, and the -T of pcs-multicamera-optimized, which consumes one
+// matrix per camera:
 //
-//     pcs-align-extrinsics -T in.txt -o out.txt [-A max_dist_mm,iterations[,stride]] [-R ref] [-g gpu] [-t] cam0.bin cam1.bin ...
+//     pcs-align-extrinsics -T in.txt -o out.txt [-A max_dist_mm,iterations[,stride]] [-p radius_mm,min_neighbors[,flatness]] [-R ref]
+//                          [-g gpu] [-t] cam0.bin cam1.bin ...
 //
 //   cam*.bin   [int32 bytes][records], what `pcs-camera-optimized -o` writes: one file, one camera, in its own frame. Records whose
 //              three coordinates are all zero (zero-depth pixels: the only way to get one) are dropped before upload, and counted.
 //   -T / -o    one line of 16 values per camera, row-major 4x4 in metres (the -T format of pcs-multicamera-optimized).
 //   -R ref     the camera the others are moved onto (default 0): the target is its payload moved by in[ref]. Its line is copied.
 //   -A         max_dist_mm 1..1000 (default 60), iterations 1..100 (default 30), every stride-th source record (default 1).
-//   -t         per camera: iterations, matched share, first and last rms.
+//   -p         point to plane instead of point to point: the target's surface normals are estimated from its neighbours within
+//              radius_mm 1..1000, at least min_neighbors 3..32767 of them, and kept where flatness (0 = off, else 1..1000) times the
+//              smallest eigenvalue of the neighbourhood does not exceed the middle one. Far fewer iterations reach a far smaller
+//              rotation error on independently sampled surfaces (-A 60,6 -p 120,6,20 is a start). Without -p nothing changes.
+//   -t         per camera: iterations, matched share, first and last rms (with -p: the method, and the share with a normal).
 // Every other camera is refined from in[i]; out.txt gets (float)T_K printed with %.9g, so the float survives the round trip. A camera
 // whose loop ends refused keeps in[i], with a `# camera i not refined: <reason>` comment before its line and a warning on stderr.
 // Exit status: 0 all cameras refined, 3 some camera not refined, 2 usage, 1 anything else.
@@ -25,13 +31,15 @@
 
 static void usage()
 {
-    std::cerr << "usage: pcs-align-extrinsics -T in.txt -o out.txt [-A max_dist_mm,iterations[,stride]] [-R ref] [-g gpu] [-t] cam0.bin cam1.bin ...\n"
+    std::cerr << "usage: pcs-align-extrinsics -T in.txt -o out.txt [-A max_dist_mm,iterations[,stride]] [-p radius_mm,min_neighbors[,flatness]]\n"
+              << "                            [-R ref] [-g gpu] [-t] cam0.bin cam1.bin ...\n"
               << " -T <file>   initial extrinsics, one line of 16 values per camera (row-major 4x4, metres)\n"
               << " -o <file>   refined extrinsics, same format\n"
               << " -A a,b[,c]  max_dist_mm 1..1000 (60), iterations 1..100 (30), source stride (1)\n"
+              << " -p a,b[,c]  point to plane: target normals from radius_mm 1..1000, min_neighbors 3..32767, flatness 0..1000 (0 = off)\n"
               << " -R <n>      reference camera (0): the others are moved onto it\n"
               << " -g <n>      GPU (0)\n"
-              << " -t          per camera: iterations, matched share, first and last rms\n"
+              << " -t          per camera: iterations, matched share, first and last rms (with -p: the method and the used share)\n"
               << " cam*.bin    [int32 bytes][records] as written by pcs-camera-optimized -o\n";
 }
 
@@ -125,6 +133,11 @@ int main(int argc, char** argv)
     pcs_align_params params;
     memset(&params, 0, sizeof params);
     params.max_dist_mm = opt.max_dist_mm; params.iterations = opt.iterations; params.source_stride = opt.stride;
+    pcs_align_plane_params plane;
+    memset(&plane, 0, sizeof plane);
+    plane.max_dist_mm = opt.max_dist_mm; plane.iterations = opt.iterations; plane.source_stride = opt.stride;
+    plane.normals.radius_mm = opt.normal_radius_mm; plane.normals.min_neighbors = opt.normal_min_neighbors;
+    plane.normals.flatness = opt.normal_flatness;
 
     std::vector<std::vector<float>> out = in;
     std::vector<std::string> note(n);
@@ -137,20 +150,32 @@ int main(int argc, char** argv)
         if (sb && (rc = pcs_memcpy_h2d(ctx, d_source, rec[i].data(), sb))) return die("pcs_memcpy_h2d");
         float refined[16];
         pcs_align_report rep;
+        pcs_align_plane_report prep;
         memset(&rep, 0, sizeof rep);
-        rc = pcs_align_payloads_device(ctx, static_cast<const int16_t*>(d_source), ns, static_cast<const int16_t*>(d_target), n_target, &params,
-                                       in[i].data(), refined, &rep);
+        memset(&prep, 0, sizeof prep);
+        if (opt.plane)
+            rc = pcs_align_payloads_plane_device(ctx, static_cast<const int16_t*>(d_source), ns, static_cast<const int16_t*>(d_target), n_target,
+                                                 &plane, in[i].data(), refined, &prep);
+        else
+            rc = pcs_align_payloads_device(ctx, static_cast<const int16_t*>(d_source), ns, static_cast<const int16_t*>(d_target), n_target, &params,
+                                           in[i].data(), refined, &rep);
         pcs_device_free(ctx, d_source);
         if (rc == PCS_ERR_UNSUPPORTED) {
             note[i] = pcs_last_error(ctx);
             std::cerr << "warning: camera " << i << " not refined: " << note[i] << std::endl;
             not_refined++;
         } else if (rc != PCS_OK) {
-            return die("pcs_align_payloads_device");
+            return die(opt.plane ? "pcs_align_payloads_plane_device" : "pcs_align_payloads_device");
         } else {
             out[i].assign(refined, refined + 16);
         }
-        if (opt.timing) {
+        if (opt.timing && opt.plane) {
+            const double share = prep.last_considered ? 100.0 * (double)prep.last_matched / (double)prep.last_considered : 0.0;
+            const double used = prep.last_considered ? 100.0 * (double)prep.last_used / (double)prep.last_considered : 0.0;
+            printf("Camera %zu: point to plane, %d iterations, matched %lld of %lld (%.1f %%), with a normal %lld (%.1f %%), rms %.3f -> %.3f mm\n",
+                   i, prep.iterations, (long long)prep.last_matched, (long long)prep.last_considered, share, (long long)prep.last_used, used,
+                   prep.first_rms_mm, prep.last_rms_mm);
+        } else if (opt.timing) {
             const double share = rep.last_considered ? 100.0 * (double)rep.last_matched / (double)rep.last_considered : 0.0;
             printf("Camera %zu: %d iterations, matched %lld of %lld (%.1f %%), rms %.3f -> %.3f mm\n", i, rep.iterations,
                    (long long)rep.last_matched, (long long)rep.last_considered, share, rep.first_rms_mm, rep.last_rms_mm);

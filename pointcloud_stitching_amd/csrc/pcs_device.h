@@ -385,6 +385,30 @@ hipError_t launch_align_match(const int16_t* d_source, uint32_t n_source, const 
                               long long* d_partials, uint32_t* d_dist2, hipStream_t st);
 hipError_t launch_align_reduce(const long long* d_partials, uint32_t n_partials, long long* d_sums, hipStream_t st);
 
+// Point-to-plane sums (pcs_align_plane_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Plane sums"): the same
+// index and match. launch_align_plane_scatter: the target's normals (4 shorts per record, 8-byte aligned) into d_pnorm[n_target],
+// parallel to xyz[] — the caller set it to all ones on the same stream first. launch_align_plane_match: one 480-byte partial per
+// workgroup into d_partials[align_partials(n_source)] (index nullptr for an empty target: d_pnorm is not read).
+// launch_align_plane_reduce: one workgroup sums the partials and writes *d_sums whole (n_partials 0: a zeroed struct).
+constexpr int kPlaneTerms = 60;              // pcs_align_plane_sums as int64 words
+hipError_t launch_align_plane_scatter(const int16_t* d_target, const int16_t* d_target_normals, uint32_t n_target,
+                                      const OutlierIndexView& index, int max_dist_mm, unsigned long long* d_pnorm, hipStream_t st);
+hipError_t launch_align_plane_match(const int16_t* d_source, uint32_t n_source, const OutlierIndexView* index, const unsigned long long* d_pnorm,
+                                    int max_dist_mm, long long* d_partials, uint32_t* d_dist2, hipStream_t st);
+hipError_t launch_align_plane_reduce(const long long* d_partials, uint32_t n_partials, long long* d_sums, hipStream_t st);
+
+// Surface normals (pcs_estimate_normals_device, pcs_kernels_normals.hip; the definition: DESIGN.md section 3 "Surface normals"). The
+// payload's index is the outlier filter's, cell edge radius_mm (stages 0 to 5 of launch_outlier_stage over the payload; `index` is
+// its view). launch_normals_estimate: one lane per xyz[] entry, its four shorts as one word into d_cell_normals[n_points], parallel
+// to xyz[] (cell order). launch_normals_gather: one lane per input record copies its word to d_normals[i] (8-byte aligned) and adds
+// the valid records to *d_valid (optional; zeroed by the caller on the same stream). NormalRule: pcs_normals_math.h.
+struct NormalRule;
+constexpr int kNormalLaunches = 2;           // estimate, gather (behind the index's six)
+hipError_t launch_normals_estimate(uint32_t n_points, const OutlierIndexView& index, const NormalRule& rule,
+                                   unsigned long long* d_cell_normals, hipStream_t st);
+hipError_t launch_normals_gather(const int16_t* d_in, uint32_t n_points, int radius_mm, const OutlierIndexView& index,
+                                 const unsigned long long* d_cell_normals, unsigned long long* d_normals, int32_t* d_valid, hipStream_t st);
+
 // a7 with stride.
 hipError_t launch_stitch(const int16_t* d_src, uint32_t src_points, int downsample,
                          int16_t* d_dst, hipStream_t st);

@@ -140,6 +140,10 @@ struct pcs_ctx {
     // grown on demand by ensure_outlier_ws's policy
     void*                           s_align_ws = nullptr; size_t s_align_ws_cap = 0;
 
+    // surface normals (pcs_capi_normals.cpp): the payload's cell index (the outlier filter's layout) and the normals in cell order,
+    // 8 bytes per record — one slab carved per call, grown on demand by ensure_outlier_ws's policy
+    void*                           s_normals_ws = nullptr; size_t s_normals_ws_cap = 0;
+
     std::string                     err;
 };
 
@@ -215,6 +219,11 @@ struct DeviceGuard {
 // The voxel workspace of a context, at least `need` bytes (grows with a quarter of headroom; growing waits for the stream).
 int ensure_voxel_ws(pcs_ctx* c, size_t need);
 int acquire_event_pair(pcs_ctx* c, std::pair<hipEvent_t, hipEvent_t>& pr);
+
+// Surface normals for a caller inside the library (pcs_capi_normals.cpp; the point-to-plane loop estimates its target's): the
+// parameter ranges of pcs_normal_params, `who` naming the entry point, and pcs_estimate_normals_device behind its checks.
+int check_normal_params(pcs_ctx* c, const char* who, const pcs_normal_params* params);
+int run_normals_device(pcs_ctx* c, const int16_t* d_payload, int n_points, const pcs_normal_params& P, int16_t* d_normals, int32_t* d_valid);
 
 // The kernel-timing bracket (pcs_kernel_timing) around the launches of one call: constructed before the first launch, finish() after the
 // last. One bracket is one interval of pcs_kernel_times_ms. Every exit between the two, a HIPCHK return included, hands the pair back.

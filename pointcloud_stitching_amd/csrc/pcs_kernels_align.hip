@@ -198,3 +198,225 @@ hipError_t launch_align_reduce(const long long* d_partials, uint32_t n_partials,
 }
 
 }  // namespace pcs
+
+// ---- point to plane -----------------------------------------------------------------------------------
+// pcs_align_plane_sums_device (DESIGN.md section 3 "Plane sums"): the same match, and per pair the row a = (p x n, n), b = n . (q - p)
+// of the linearised point-to-plane problem, n the three shorts of the match's normal; the pairs reduced to A^T A (upper triangle), A^T b,
+// sum b^2. |p x n| < 2^31 and |b| < 2^28 for any int16 normal, so every product fits int64; their SUM over a payload does not, so
+// each product t travels as two halves — t & 0xFFFFFFFF (unsigned) and t >> 32 (arithmetic) — summed separately (each below 2^60 for
+// fewer than 2^28 records) and recombined on the host as hi 2^32 + lo.
+//   scatter  the target's normals into cell order beside xyz[]: pnorm[] starts as all ones (the host layer's memset); one lane per
+//            target record with a valid normal (short 3 != 0) walks its own cell's run and does a 64-bit atomicMin of its key into
+//            every entry whose coordinates equal its own. The key is the four shorts as one little-endian number minus 2^48: valid
+//            words are exactly those >= 2^48, so the order is kept and all ones stays free to mean "no valid normal". Every entry
+//            of equal coordinates ends with the same key, the smallest: the order the atomics arrive in reaches no output bit.
+//   match    pcs_align_match_kernel's probe, pruning and (d^2, coordinate word) comparison, line for line, and the winner's position
+//            in xyz[] kept beside it: any position with the winner's coordinates holds the same key. The sixty terms are formed and
+//            summed over the wave one at a time (sixty live 64-bit words are not a register budget): one 480-byte partial per
+//            workgroup.
+//   reduce   one workgroup of 1 024: lane (g, t) adds term t of partials g, g + 16, ..., the sixteen groups meet in LDS; *d_sums is
+//            written whole.
+// Bounds: as the match above; pnorm[m] wherever xyz[m] is read or written (m < min(start[at + 1], capacity)), normals[i] with
+// i < n_target, partial blockIdx.x < align_partials(n_source). No floats.
+
+namespace pcs {
+
+namespace {
+
+constexpr unsigned long long kNoNormal   = ~0ull;
+constexpr unsigned long long kNormalBase = 1ull << 48;          // the smallest valid word: short 3 = 1, the rest 0
+constexpr uint32_t kPlaneReduceThreads = 1024;                   // the plane reduce workgroup: sixteen groups of 64 lanes, a term each
+constexpr int kAtaLo = 3, kAtaHi = 24, kAtbLo = 45, kAtbHi = 51, kSb2Lo = 57, kSb2Hi = 58, kPlaneSd2 = 59;      // pcs_align_plane_sums
+
+static_assert(kPlaneTerms == 60 && kPlaneTerms <= 64, "the reduce kernel gives a term to each of 64 lanes");
+
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_align_plane_scatter_kernel(const int16_t* __restrict__ target, const unsigned long long* __restrict__ normals, uint32_t n_target,
+                                    int radius, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ start,
+                                    uint32_t slots, const uint2* __restrict__ xyz, uint32_t capacity, unsigned long long* __restrict__ pnorm)
+{
+    const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (i >= n_target) return;
+    const unsigned long long word = normals[i];
+    if (word < kNormalBase) return;                                      // short 3 == 0: not a valid normal
+    const Xyz p = load_xyz(target, i);
+    const uint2 want = make_uint2((uint32_t)(uint16_t)p.x | (uint32_t)(uint16_t)p.y << 16, (uint32_t)(uint16_t)p.z);
+    const unsigned long long key = cell_key(cell_of(p.x, radius), cell_of(p.y, radius), cell_of(p.z, radius));
+    uint32_t s = first_slot(key, slots), at = kNoSlot;
+    for (uint32_t probe = 0; probe < slots; probe++) {                   // ends at the key or at the first empty slot; at most `slots` steps
+        const unsigned long long k = keys[s];
+        if (k == key) at = s;
+        if (k == key || k == kEmptyKey) break;
+        s = s + 1u == slots ? 0u : s + 1u;
+    }
+    if (at == kNoSlot) return;                                           // (cannot happen: the index holds every target record)
+    const uint32_t e = min(start[at + 1u], capacity);
+    for (uint32_t m = start[at]; m < e; m++) {
+        const uint2 q = xyz[m];
+        if (q.x == want.x && q.y == want.y) atomicMin(pnorm + m, word - kNormalBase);
+    }
+}
+
+// One term of the workgroup's partial: its wave sum into the wave's row of `lds`.
+__device__ __forceinline__ void put_term(long long* lds, int t, long long v)
+{
+    const long long w = wave_sum64(v);
+    if ((threadIdx.x & 63) == 0) lds[(threadIdx.x >> 6) * kPlaneTerms + t] = w;
+}
+
+// a product's two halves into terms lo and hi
+__device__ __forceinline__ void put_split(long long* lds, int lo, int hi, long long v)
+{
+    put_term(lds, lo, (long long)((unsigned long long)v & 0xFFFFFFFFull));
+    put_term(lds, hi, v >> 32);
+}
+
+// keys == nullptr: an empty target, nobody matches (no index was built).
+__global__ __launch_bounds__(kBlockThreads)
+void pcs_align_plane_match_kernel(const int16_t* __restrict__ source, uint32_t n_source, int radius,
+                                  const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ start, uint32_t slots,
+                                  const uint2* __restrict__ xyz, const unsigned long long* __restrict__ pnorm, uint32_t capacity,
+                                  long long* __restrict__ partials, uint32_t* __restrict__ dist2)
+{
+    __shared__ long long wsum[(kBlockThreads / 64) * kPlaneTerms];
+    const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
+    long long considered = 0, matched = 0, used = 0, sd2 = 0, b = 0;
+    long long a[6] = {0, 0, 0, 0, 0, 0};
+    if (i < n_source) {
+        const Xyz p = load_xyz(source, i);
+        uint32_t best_d2 = kNoMatch, best_m = 0;      // the minimum so far: (best_d2, best_q) at xyz[best_m]
+        unsigned long long best_q = 0;
+        if (keys) {
+            const int cx = cell_of(p.x, radius), cy = cell_of(p.y, radius), cz = cell_of(p.z, radius);
+            const int r2 = radius * radius;
+            const int fx = p.x - (cx - 32768) * radius, fy = p.y - (cy - 32768) * radius, fz = p.z - (cz - 32768) * radius;
+            const auto gap = [radius](int f, int o) { return o == 0 ? f + 1 : o == 1 ? 0 : radius - f; };
+            uint32_t bound = (uint32_t)r2;                               // min(r^2, the best d^2 so far)
+            for (int c = 0; c < 27; c++) {
+                const int cc = c + 13 < 27 ? c + 13 : c - 14;           // 13 = (0, 0, 0): the own cell first
+                const int ox = cc % 3, oy = (cc / 3) % 3, oz = cc / 9;
+                const int ex = gap(fx, ox), ey = gap(fy, oy), ez = gap(fz, oz);
+                const uint32_t low = (uint32_t)(ex * ex + ey * ey + ez * ez);
+                if (low > bound) continue;                              // (equal: it may hold a tie)
+                const int ax = cx + ox - 1, ay = cy + oy - 1, az = cz + oz - 1;
+                if ((uint32_t)ax > 65535u || (uint32_t)ay > 65535u || (uint32_t)az > 65535u) continue;   // no such cell: skipped, never wrapped
+                const unsigned long long key = cell_key(ax, ay, az);
+                uint32_t s = first_slot(key, slots), at = kNoSlot;
+                for (uint32_t probe = 0; probe < slots; probe++) {       // ends at the key or at the first empty slot; at most `slots` steps
+                    const unsigned long long k = keys[s];
+                    if (k == key) at = s;
+                    if (k == key || k == kEmptyKey) break;
+                    s = s + 1u == slots ? 0u : s + 1u;
+                }
+                if (at == kNoSlot) continue;
+                const uint32_t e = min(start[at + 1u], capacity);
+                for (uint32_t m = start[at]; m < e; m++) {
+                    const uint2 q = xyz[m];
+                    const int qx = (int)(int16_t)(q.x & 0xFFFFu), qy = (int)(int16_t)(q.x >> 16), qz = (int)(int16_t)(q.y & 0xFFFFu);
+                    const int dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
+                    const uint32_t d2 = (uint32_t)(dx * dx + dy * dy + dz * dz);
+                    if (d2 > (uint32_t)r2) continue;                    // beyond the radius: never entered
+                    const unsigned long long word = (unsigned long long)(uint32_t)(qz + 32768) << 32 |
+                                                    (unsigned long long)(uint32_t)(qy + 32768) << 16 | (unsigned long long)(uint32_t)(qx + 32768);
+                    if (d2 < best_d2 || (d2 == best_d2 && word < best_q)) { best_d2 = d2; best_q = word; best_m = m; }
+                }
+                if (best_d2 != kNoMatch) bound = best_d2;
+            }
+        }
+        considered = 1;
+        if (best_d2 != kNoMatch) {
+            matched = 1;
+            sd2 = (long long)best_d2;
+            const unsigned long long nk = pnorm[best_m];                 // (best_m < capacity: it indexed xyz[])
+            if (nk != kNoNormal) {
+                const unsigned long long w = nk + kNormalBase;
+                const long long nx = (int16_t)(uint16_t)w, ny = (int16_t)(uint16_t)(w >> 16), nz = (int16_t)(uint16_t)(w >> 32);
+                const long long qx = (long long)(uint32_t)(best_q & 0xFFFFu) - 32768, qy = (long long)(uint32_t)((best_q >> 16) & 0xFFFFu) - 32768,
+                                qz = (long long)(uint32_t)((best_q >> 32) & 0xFFFFu) - 32768;
+                const long long px = p.x, py = p.y, pz = p.z;
+                used = 1;
+                a[0] = py * nz - pz * ny; a[1] = pz * nx - px * nz; a[2] = px * ny - py * nx;      // c = p x n
+                a[3] = nx; a[4] = ny; a[5] = nz;
+                b = nx * (qx - px) + ny * (qy - py) + nz * (qz - pz);
+            }
+        }
+        if (dist2) dist2[i] = best_d2;                                   // (kNoMatch is the unmatched word)
+    }
+    put_term(wsum, 0, considered);
+    put_term(wsum, 1, matched);
+    put_term(wsum, 2, used);
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+#pragma unroll
+        for (int c = r; c < 6; c++, k++) put_split(wsum, kAtaLo + k, kAtaHi + k, a[r] * a[c]);       // (an unused pair: a = 0)
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) put_split(wsum, kAtbLo + r, kAtbHi + r, a[r] * b);
+    put_split(wsum, kSb2Lo, kSb2Hi, b * b);
+    put_term(wsum, kPlaneSd2, sd2);
+    __syncthreads();
+    if (threadIdx.x < kPlaneTerms) {
+        long long total = 0;
+        for (int w = 0; w < (int)(kBlockThreads / 64); w++) total += wsum[w * kPlaneTerms + threadIdx.x];
+        partials[(size_t)blockIdx.x * kPlaneTerms + threadIdx.x] = total;
+    }
+}
+
+// One workgroup of kPlaneReduceThreads: lane (g, t) adds term t of partials g, g + 16, ... (a wave reads 480 contiguous bytes of one
+// partial; eight loads in flight per lane), the sixteen groups meet in LDS.
+__global__ __launch_bounds__(kPlaneReduceThreads)
+void pcs_align_plane_reduce_kernel(const long long* __restrict__ partials, uint32_t n_partials, long long* __restrict__ sums)
+{
+    constexpr uint32_t kGroups = kPlaneReduceThreads / 64;
+    __shared__ long long gsum[kGroups * 64];
+    const uint32_t t = threadIdx.x & 63u, g = threadIdx.x >> 6;
+    long long total = 0;
+    if (t < (uint32_t)kPlaneTerms) {
+#pragma unroll 8
+        for (uint32_t j = g; j < n_partials; j += kGroups) total += partials[(size_t)j * kPlaneTerms + t];
+    }
+    gsum[threadIdx.x] = total;
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)kPlaneTerms) {
+        long long all = 0;
+        for (uint32_t w = 0; w < kGroups; w++) all += gsum[w * 64 + threadIdx.x];
+        sums[threadIdx.x] = all;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_align_plane_scatter(const int16_t* d_target, const int16_t* d_target_normals, uint32_t n_target,
+                                      const OutlierIndexView& index, int max_dist_mm, unsigned long long* d_pnorm, hipStream_t st)
+{
+    if (!n_target || !d_target || !d_target_normals || ((uintptr_t)d_target_normals & 7u) || !d_pnorm || !index.keys || !index.start ||
+        !index.xyz || !index.slots || n_target > index.capacity || max_dist_mm < PCS_ALIGN_DIST_MIN || max_dist_mm > PCS_ALIGN_DIST_MAX)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pcs_align_plane_scatter_kernel, dim3((n_target + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, st,
+                       d_target, reinterpret_cast<const unsigned long long*>(d_target_normals), n_target, max_dist_mm, index.keys, index.start,
+                       index.slots, index.xyz, index.capacity, d_pnorm);
+    return hipGetLastError();
+}
+
+hipError_t launch_align_plane_match(const int16_t* d_source, uint32_t n_source, const OutlierIndexView* index, const unsigned long long* d_pnorm,
+                                    int max_dist_mm, long long* d_partials, uint32_t* d_dist2, hipStream_t st)
+{
+    if (!n_source || !d_source || !d_partials || max_dist_mm < PCS_ALIGN_DIST_MIN || max_dist_mm > PCS_ALIGN_DIST_MAX)
+        return hipErrorInvalidValue;
+    if (index && (!index->keys || !index->start || !index->xyz || !index->slots || !index->capacity || !d_pnorm)) return hipErrorInvalidValue;
+    const OutlierIndexView none{nullptr, nullptr, nullptr, 0u, 0u};
+    const OutlierIndexView& v = index ? *index : none;
+    hipLaunchKernelGGL(pcs_align_plane_match_kernel, dim3(align_partials(n_source)), dim3(kBlockThreads), 0, st, d_source, n_source,
+                       max_dist_mm, v.keys, v.start, v.slots, v.xyz, d_pnorm, v.capacity, d_partials, d_dist2);
+    return hipGetLastError();
+}
+
+hipError_t launch_align_plane_reduce(const long long* d_partials, uint32_t n_partials, long long* d_sums, hipStream_t st)
+{
+    if (!d_sums || (n_partials && !d_partials)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pcs_align_plane_reduce_kernel, dim3(1), dim3(kPlaneReduceThreads), 0, st, d_partials, n_partials, d_sums);
+    return hipGetLastError();
+}
+
+}  // namespace pcs

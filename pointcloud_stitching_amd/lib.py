@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import AlignParams, AlignReportC, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, PayloadDesc, SpatialFilterConfig, StreamConfig
+from .types import AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, SpatialFilterConfig, StreamConfig
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -89,6 +89,13 @@ SYMBOLS = [
     ("pcs_align_solve", C.c_int, [_P(AlignSumsC), _P(C.c_double), _P(C.c_double)]),
     ("pcs_align_payloads_device", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _P(AlignParams), _P(C.c_float), _P(C.c_float),
                                             _P(AlignReportC)]),
+    ("pcs_estimate_normals_device", C.c_int, [_VP, _VP, C.c_int, _P(NormalParams), _VP, _VP]),
+    ("pcs_estimate_normals", C.c_int, [_VP, _VP, C.c_int, _P(NormalParams), _VP, _P(C.c_int)]),
+    ("pcs_align_plane_sums_device", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, _VP, _VP]),
+    ("pcs_align_plane_sums", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, _P(AlignPlaneSumsC), _VP]),
+    ("pcs_align_plane_solve", C.c_int, [_P(AlignPlaneSumsC), _P(C.c_double), _P(C.c_double)]),
+    ("pcs_align_payloads_plane_device", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _P(AlignPlaneParams), _P(C.c_float), _P(C.c_float),
+                                                  _P(AlignPlaneReportC)]),
     ("pcs_set_stream", C.c_int, [_VP, _VP]),
     ("pcs_get_stream", _VP, [_VP]),
     ("pcs_synchronize", C.c_int, [_VP]),

@@ -34,6 +34,15 @@ ALIGN_STOP_ITERATIONS, ALIGN_STOP_CONVERGED, ALIGN_STOP_REFUSED = 0, 1, 2
 ALIGN_INDEX_LAUNCHES = 6                                  # kernel_times_ms intervals: the target's index, once per call
 ALIGN_SUMS_LAUNCHES = 8                                   # ... one align_sums call (index, match, reduce)
 ALIGN_ITERATION_LAUNCHES = 3                              # ... one iteration of the loop (transform, match, reduce)
+ALIGN_PLANE_INDEX_LAUNCHES = 15                           # ... the plane loop, once per call: the target's normals (8), its index, the scatter
+ALIGN_PLANE_SUMS_LAUNCHES = 9                             # ... one align_plane_sums call (index, scatter, match, reduce)
+ALIGN_PLANE_ITERATION_LAUNCHES = 3                        # ... one iteration of the plane loop (transform, match, reduce)
+ALIGN_PLANE_USED_MIN = 6                                  # pcs_align_plane_solve refuses below it
+NORMAL_RADIUS_MIN, NORMAL_RADIUS_MAX = 1, 1000            # pcs_estimate_normals*: radius_mm
+NORMAL_NEIGHBORS_MIN, NORMAL_NEIGHBORS_MAX = 3, 32767     # ... min_neighbors
+NORMAL_FLATNESS_MAX = 1000                                # ... flatness (0 = off)
+NORMAL_SHORTS, NORMAL_BYTES = 4, 8                        # a record's normal: nx, ny, nz (x 16384), the neighbour count
+NORMAL_LAUNCHES = 8                                       # kernel_times_ms intervals of one estimate_normals call (index, estimate, gather)
 
 DISTORTION_NONE = 0
 DISTORTION_MODIFIED_BROWN_CONRADY = 1
@@ -108,6 +117,17 @@ class CompressedInfo(C.Structure):
     _fields_ = [("n_points", C.c_uint32), ("n_blocks", C.c_uint32), ("total_bytes", C.c_uint32), ("data_offset", C.c_uint32)]
 
 
+class NormalParams(C.Structure):
+    """pcs_normal_params."""
+    _fields_ = [("radius_mm", C.c_int32), ("min_neighbors", C.c_int32), ("flatness", C.c_int32), ("use_viewpoint", C.c_int32),
+                ("viewpoint_mm", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, radius_mm: int, min_neighbors: int, flatness: int = 0, viewpoint_mm=None, reserved: int = 0) -> "NormalParams":
+        vp = (0, 0, 0) if viewpoint_mm is None else tuple(int(v) for v in viewpoint_mm)
+        return cls(int(radius_mm), int(min_neighbors), int(flatness), int(viewpoint_mm is not None), (C.c_int32 * 3)(*vp), int(reserved))
+
+
 class AlignSumsC(C.Structure):
     """struct pcs_align_sums: eighteen int64."""
     _fields_ = [("considered", C.c_int64), ("matched", C.c_int64), ("sp", C.c_int64 * 3), ("sq", C.c_int64 * 3),
@@ -128,6 +148,90 @@ class AlignReportC(C.Structure):
                 ("first_rms_mm", C.c_double), ("last_rms_mm", C.c_double),
                 ("trace_capacity", C.c_int32), ("trace_count", C.c_int32),
                 ("trace_transforms", C.c_void_p), ("trace_sums", C.c_void_p)]
+
+
+class AlignPlaneSumsC(C.Structure):
+    """struct pcs_align_plane_sums: sixty int64."""
+    _fields_ = [("considered", C.c_int64), ("matched", C.c_int64), ("used", C.c_int64), ("ata_lo", C.c_int64 * 21),
+                ("ata_hi", C.c_int64 * 21), ("atb_lo", C.c_int64 * 6), ("atb_hi", C.c_int64 * 6), ("sb2_lo", C.c_int64),
+                ("sb2_hi", C.c_int64), ("sd2", C.c_int64)]
+
+
+class AlignPlaneParams(C.Structure):
+    """pcs_align_plane_params."""
+    _fields_ = [("max_dist_mm", C.c_int32), ("iterations", C.c_int32), ("source_stride", C.c_int32), ("reserved", C.c_int32),
+                ("eps_rot_rad", C.c_double), ("eps_trans_mm", C.c_double), ("normals", NormalParams)]
+
+
+class AlignPlaneReportC(C.Structure):
+    """pcs_align_plane_report."""
+    _fields_ = [("iterations", C.c_int32), ("stop_reason", C.c_int32),
+                ("first_matched", C.c_int64), ("first_used", C.c_int64), ("first_considered", C.c_int64),
+                ("last_matched", C.c_int64), ("last_used", C.c_int64), ("last_considered", C.c_int64),
+                ("first_rms_mm", C.c_double), ("last_rms_mm", C.c_double),
+                ("trace_capacity", C.c_int32), ("trace_count", C.c_int32),
+                ("trace_transforms", C.c_void_p), ("trace_sums", C.c_void_p)]
+
+
+@dataclass(frozen=True)
+class AlignPlaneSums:
+    """The point-to-plane sums of one correspondence step: the sixty int64 words as the library wrote them (Python integers), the
+    halves of every product kept apart; ata / atb / sb2 recombine them (hi 2^32 + lo: exact)."""
+    words: Tuple[int, ...]
+
+    considered = property(lambda self: self.words[0])
+    matched = property(lambda self: self.words[1])
+    used = property(lambda self: self.words[2])
+    sd2 = property(lambda self: self.words[59])
+
+    def as_array(self) -> np.ndarray:
+        """The sixty int64 words in struct order."""
+        return np.array(self.words, dtype=np.int64)
+
+    @classmethod
+    def from_array(cls, a) -> "AlignPlaneSums":
+        v = tuple(int(x) for x in np.asarray(a).reshape(-1))
+        if len(v) != 60:
+            raise ValueError("point-to-plane sums are 60 integers")
+        return cls(v)
+
+    @property
+    def ata(self) -> List[int]:
+        """The upper triangle of A^T A, row-major, 21 exact integers."""
+        return [(self.words[24 + k] << 32) + self.words[3 + k] for k in range(21)]
+
+    @property
+    def atb(self) -> List[int]:
+        return [(self.words[51 + k] << 32) + self.words[45 + k] for k in range(6)]
+
+    @property
+    def sb2(self) -> int:
+        return (self.words[58] << 32) + self.words[57]
+
+    def to_c(self) -> AlignPlaneSumsC:
+        c = AlignPlaneSumsC()
+        C.memmove(C.addressof(c), self.as_array().ctypes.data, C.sizeof(c))
+        return c
+
+
+@dataclass
+class AlignPlaneReport:
+    """What pcs_align_payloads_plane_device reports: AlignReport's fields with `used` beside `matched`, the trace's sums as
+    AlignPlaneSums."""
+    iterations: int
+    stop_reason: int
+    status: int
+    detail: str
+    first_matched: int
+    first_used: int
+    first_considered: int
+    last_matched: int
+    last_used: int
+    last_considered: int
+    first_rms_mm: float
+    last_rms_mm: float
+    trace_transforms: np.ndarray = field(default_factory=lambda: np.zeros((0, 4, 4), np.float32))
+    trace_sums: List[AlignPlaneSums] = field(default_factory=list)
 
 
 @dataclass(frozen=True)
