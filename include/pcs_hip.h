@@ -700,6 +700,66 @@ int pcs_radius_outlier_device_counted(pcs_ctx* ctx, const int16_t* d_payload, co
 int pcs_radius_outlier(pcs_ctx* ctx, const int16_t* payload, int n_points, int radius_mm, int min_neighbors,
                        int16_t* out, size_t out_shorts, int* out_points);   /* host pointers, staged, synchronous */
 
+/* ---- statistical outlier removal on a packed payload (not in the reference) ------------------------------------------------------ *
+ * The radius filter's threshold is absolute; this one is relative to the cloud's own density. n records of 5 shorts (0..2 = x, y, z
+ * as signed int16 millimetres; colour is not read), mean_k 1..64, std_mul_milli 0..10000 (thousandths), max_dist_mm 1..1000 (the
+ * cell edge of the index and the search bound). Everything is integer; no float is converted, compared or stored.
+ *   N_i       = { j != i : d2_ij <= max_dist_mm^2 }, d2 in integers of 32 bits or more from the sign-extended shorts (nothing wraps
+ *               at 16 bits); j != i is by index: a record with another's coordinates is its neighbour at distance 0.
+ *   SPARSE    record i iff |N_i| < mean_k: dropped, and not part of the statistics.
+ *   D_i       otherwise: the sum of isqrt(65536 d2) over the mean_k smallest d2 of N_i (a multiset: ties are interchangeable), isqrt
+ *               the exact integer floor square root. Unit 1/256 mm, summed, not divided by mean_k; below 2^24.
+ *   M, S1, S2 the number of non-sparse records, sum D_i, sum D_i^2 (exact: each D_i^2 as t & 0xFFFFFFFF and t >> 32, summed apart:
+ *               S2 = s2_lo + 2^32 s2_hi). W = M S2 - S1^2 in 128-bit integers.
+ *   T         sigma_q = isqrt(floor((W << 16) / (M (M - 1)))) for M >= 2, else 0 (the sample deviation in 1/256 of a D unit);
+ *               T = floor((256000 S1 + std_mul_milli M sigma_q) / (256000 M)), 0 when M = 0.
+ *   KEPT      record i iff it is not sparse and D_i <= T.
+ * The output is the kept records in input order, all 10 bytes of each unchanged, their count, and (optional) the statistics block
+ * of eight int64: considered, dense (= M), s1, s2_lo, s2_hi, threshold (= T), kept, reserved (0). Exact and deterministic: a function
+ * of the payload as a multiset except for the output's own order, the same bytes on every run (tests/np_stat_outlier.py restates it
+ * as brute force). Modelled on PCL's StatisticalOutlierRemoval; parity with PCL is unpinned. DESIGN.md section 3 has the definition
+ * and what follows from it: a dense payload's zero-depth pixels sit on one point, have D = 0 and drag the mean down (run the filter
+ * behind PCS_FLAG_DROP_INVALID or a crop box); max_dist_mm bounds both the cost and who counts as sparse; std_mul_milli 0 drops
+ * about half of a smooth cloud.
+ * pcs_stat_outlier_device: asynchronous on the context's stream, no host round trip: the radius filter's cell index with edge
+ *   max_dist_mm (six launches), a k-nearest search per record over its 27 cells, the sums, the threshold (one lane, 128-bit
+ *   integers), the keep bits, then that filter's ordered compaction (three launches) and, with d_stats, the block: 14 launches, 13
+ *   without. d_out needs room for the worst case: out_shorts >= 5 n_points is checked up front; nothing outside the first 10 * kept
+ *   bytes of d_out is written. *d_out_points (device, 4-byte aligned, required) receives kept; d_stats (device, 8-byte aligned,
+ *   optional) the block. n_points 0 launches nothing and writes a zero count and a zeroed block (considered = 0).
+ * pcs_stat_outlier_device_counted: the count is read from *d_n_points (device, 4-byte aligned) when the kernels run, clamped to
+ *   0..max_points; max_points sizes the workspace, the grids and the output check. It takes pcs_radius_outlier_device_counted's
+ *   output and count, and its own feed pcs_voxel_grid_device_counted.
+ * pcs_stat_outlier: host pointers, staged through the context, synchronous; stats optional.
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the function and the argument), nothing launched, nothing written: a
+ *   parameter out of range or reserved != 0, NULL params, a negative count, a NULL pointer (payload and output may be NULL with a
+ *   count of 0), an odd payload or output address, a misaligned count or stats address, out_shorts below the worst case, any
+ *   overlap among the input, output, count and stats ranges.
+ * Works on every context: flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH are not read. The workspace (the radius filter's
+ *   40.2 bytes per record of n_points / max_points plus 4.1: csrc/pcs_kernels_stat.hip) lives in the context and grows on demand.
+ *   Cost: a record costs the population of the cells around it that it cannot rule out (a cell whose nearest corner is no nearer
+ *   than the record's mean_k-th value so far is skipped), plus 2 log2(mean_k + 1) list reads per value that enters its full list;
+ *   there is no early exit: n identical records cost n^2 distance tests. With pcs_kernel_timing enabled a call yields one
+ *   interval per launch. Measured: DESIGN.md section 10 (f12), profiles/stat_outlier_probe.txt.                                    */
+#define PCS_STAT_K_MIN          1
+#define PCS_STAT_K_MAX          64
+#define PCS_STAT_MUL_MILLI_MAX  10000
+#define PCS_STAT_DIST_MIN       1
+#define PCS_STAT_DIST_MAX       1000
+typedef struct pcs_stat_outlier_params {
+    int32_t mean_k, std_mul_milli, max_dist_mm, reserved;   /* reserved is 0 */
+} pcs_stat_outlier_params;
+struct pcs_stat_outlier_stats {
+    int64_t considered, dense, s1, s2_lo, s2_hi, threshold, kept, reserved;
+};
+int pcs_stat_outlier_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const pcs_stat_outlier_params* params,
+                            int16_t* d_out, size_t out_shorts, int32_t* d_out_points, struct pcs_stat_outlier_stats* d_stats);
+int pcs_stat_outlier_device_counted(pcs_ctx* ctx, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                    const pcs_stat_outlier_params* params, int16_t* d_out, size_t out_shorts,
+                                    int32_t* d_out_points, struct pcs_stat_outlier_stats* d_stats);
+int pcs_stat_outlier(pcs_ctx* ctx, const int16_t* payload, int n_points, const pcs_stat_outlier_params* params,
+                     int16_t* out, size_t out_shorts, int* out_points, struct pcs_stat_outlier_stats* stats);   /* host pointers, staged, synchronous */
+
 /* ---- extrinsics refinement: nearest-neighbour alignment sums, the rigid fit, the ICP loop (not in the reference) ---------------- *
  * transform[i] comes from four surveyed markers (calibration.py); these calls refine it from the data: move one camera's payload
  * onto another's where they overlap. DESIGN.md section 3 "Alignment sums" has the definition and what follows from it.

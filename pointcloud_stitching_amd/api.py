@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, SpatialFilterConfig, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -602,6 +602,35 @@ class PcsContext:
         self._check(self._lib.pcs_radius_outlier_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
                                                                 int(radius_mm), int(min_neighbors), d_out or None, out_shorts,
                                                                 d_out_points or None))
+
+    # -- statistical outlier removal (defined by this build; see include/pcs_hip.h) ----------------
+    def stat_outlier(self, payload: np.ndarray, mean_k: int, std_mul_milli: int, max_dist_mm: int):
+        """Packed records (int16 [n,5]) -> (the records whose summed distance to their mean_k nearest neighbours within
+        max_dist_mm is at most mean + std_mul_milli / 1000 deviations of the cloud's, input order; the statistics block as a
+        dict) (pcs_stat_outlier: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        out = np.zeros((max(p.shape[0], 1), POINT_SHORTS), np.int16)
+        cnt = C.c_int(0)
+        stats = StatOutlierStatsC()
+        params = StatOutlierParams.make(mean_k, std_mul_milli, max_dist_mm)
+        self._check(self._lib.pcs_stat_outlier(self._h, _ptr(p), p.shape[0], C.byref(params), _ptr(out), p.shape[0] * POINT_SHORTS,
+                                               C.byref(cnt), C.byref(stats)))
+        return out[:cnt.value].copy(), stats.as_dict()
+
+    def stat_outlier_device(self, d_payload: int, n_points: int, params: StatOutlierParams, d_out: int, out_shorts: int,
+                            d_out_points: int, d_stats: int = 0) -> None:
+        """Asynchronous; device pointers as ints; *d_out_points (int32, required) receives the kept count, d_stats (eight int64,
+        optional) the statistics block. params may be None (refused). See pcs_stat_outlier_device."""
+        self._check(self._lib.pcs_stat_outlier_device(self._h, d_payload or None, int(n_points), C.byref(params) if params is not None else None,
+                                                      d_out or None, out_shorts, d_out_points or None, d_stats or None))
+
+    def stat_outlier_device_counted(self, d_payload: int, d_n_points: int, max_points: int, params: StatOutlierParams, d_out: int,
+                                    out_shorts: int, d_out_points: int, d_stats: int = 0) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run. See
+        pcs_stat_outlier_device_counted."""
+        self._check(self._lib.pcs_stat_outlier_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
+                                                              C.byref(params) if params is not None else None, d_out or None, out_shorts,
+                                                              d_out_points or None, d_stats or None))
 
     # -- surface normals (defined by this build; see include/pcs_hip.h) -----------------------------
     def estimate_normals(self, payload: np.ndarray, radius_mm: int, min_neighbors: int, flatness: int = 0, viewpoint_mm=None,

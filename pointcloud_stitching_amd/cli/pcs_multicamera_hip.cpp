@@ -46,6 +46,14 @@
 //                      the payload is built on the device (pcs_process_frames_device), filtered by the counted form, then voxelised
 //                      or copied out. -t prints `Outlier removal: <in> -> <kept> points` per frame-set. Not with -G: the node library
 //                      has no such filter. The filter knows nothing of invalid depth: with -i give -Z (or -B).
+//              -K <mean_k,std_mul_milli,max_dist_mm>  statistical outlier removal on the stitched cloud (pcs_stat_outlier_device: a
+//                      record stays iff it has mean_k others within max_dist_mm and the summed distance to the nearest mean_k is at
+//                      most the cloud's mean + std_mul_milli / 1000 deviations): after -T, -B / -d and -O, before -V. With -c it
+//                      runs on the stitched device payload, or on -O's output and device count through the counted form; with -i
+//                      on the device payload's count, or -O's; with -V its output and device count feed
+//                      pcs_voxel_grid_device_counted. -t prints `Statistical outlier removal: <in> -> <kept> points (dense <M>,
+//                      threshold <T>/256 per k)` per frame-set. Not with -G: the node library has no such filter. Zero-depth pixels
+//                      sit on one point and drag the mean down: with -i give -Z (or -B).
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
@@ -62,6 +70,7 @@
 
 #include "pcs_cropbox.h"
 #include "pcs_outlier.h"
+#include "pcs_statoutlier.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
 #include "../../include/pcs_node.h"
@@ -82,6 +91,8 @@ static bool crop = false;
 static int16_t crop_lo[3], crop_hi[3];
 static bool outlier = false;
 static int outlier_radius = 0, outlier_neighbors = 0;
+static bool statout = false;
+static pcs_stat_outlier_params statout_params{};
 
 static void usage()
 {
@@ -104,6 +115,9 @@ static void usage()
               << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
               << " -O <radius_mm,min_neighbors>  radius outlier removal on the stitched cloud: a record stays iff at least min_neighbors\n"
               << "                  others lie within radius_mm (1..1000, 1..255); after -T and -B / -d, before -V; not with -G\n"
+              << " -K <mean_k,std_mul_milli,max_dist_mm>  statistical outlier removal on the stitched cloud: a record stays iff it has mean_k\n"
+              << "                  others within max_dist_mm (1..64, 1..1000) and its summed distance to the nearest mean_k is at most the\n"
+              << "                  cloud's mean + std_mul_milli / 1000 (0..10000) deviations; after -T, -B / -d and -O, before -V; not with -G\n"
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
@@ -114,7 +128,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -155,6 +169,12 @@ int main(int argc, char** argv)
                 outlier = true;
                 break;
             }
+            case 'K': {
+                std::string why;
+                if (!pcs_statoutlier::parse(optarg, statout_params, why)) { std::cerr << "-K " << optarg << ": " << why << std::endl; return 2; }
+                statout = true;
+                break;
+            }
             case 's': case 'v': case 'n':
                 std::cerr << "-" << (char)c << " drives the reference's PCL viewer / PLY writer, which this build does not include" << std::endl;
                 return 2;
@@ -164,6 +184,7 @@ int main(int argc, char** argv)
     if (downsample < 1) { std::cerr << "downsample must be >= 1" << std::endl; return 2; }
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
     if (outlier && n_gpus > 0) { std::cerr << "-O is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
+    if (statout && n_gpus > 0) { std::cerr << "-K is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
     if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
     if (!source && !cameras) source = "synth:1280x720";      // no live cameras on this node: the synthetic generator
@@ -303,7 +324,7 @@ int main(int argc, char** argv)
     }
     // -B with -i -V: the cropped payload and its counts stay on the device between the two calls
     void *d_pay = nullptr, *d_pay_counts = nullptr;
-    if (source && ((crop && voxel_leaf) || outlier)) {
+    if (source && ((crop && voxel_leaf) || outlier || statout)) {
         if (pcs_device_malloc(ctx, &d_pay, pcs_max_payload_shorts(ctx) * sizeof(int16_t) + 64) != PCS_OK ||
             pcs_device_malloc(ctx, &d_pay_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
@@ -316,6 +337,24 @@ int main(int argc, char** argv)
             std::cerr << pcs_last_error(ctx) << std::endl; return 1;
         }
     }
+
+    // -K: the same, and the statistics block for -t
+    void *d_stat = nullptr, *d_nstat = nullptr, *d_stat_block = nullptr;
+    if (statout) {
+        const size_t bytes = source ? pcs_max_payload_shorts(ctx) * sizeof(int16_t) : (size_t)n_streams * cam_cap_bytes;
+        if (pcs_device_malloc(ctx, &d_stat, bytes + 64) != PCS_OK || pcs_device_malloc(ctx, &d_nstat, 64) != PCS_OK ||
+            pcs_device_malloc(ctx, &d_stat_block, sizeof(pcs_stat_outlier_stats)) != PCS_OK) {
+            std::cerr << pcs_last_error(ctx) << std::endl; return 1;
+        }
+    }
+    // what -t prints for -K: the block's numbers, after the frame-set's last launch
+    auto print_statout = [&]() {
+        pcs_stat_outlier_stats st{};
+        if (pcs_memcpy_d2h(ctx, &st, d_stat_block, sizeof st) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
+        std::cout << "Statistical outlier removal: " << st.considered << " -> " << st.kept << " points (dense " << st.dense << ", threshold "
+                  << st.threshold << "/256 per k)" << std::endl;
+        return true;
+    };
 
     // -V: device-resident rasters (with -i) and the voxel cloud
     std::vector<void*> d_depth, d_color;
@@ -331,7 +370,7 @@ int main(int argc, char** argv)
                       pcs_device_malloc(ctx, &d_nvox, 64) != PCS_OK)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
         if (!stitched.resize(PCS_HEADER_SHORTS + vox_cap_points * PCS_POINT_SHORTS)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
-    if ((voxel_leaf || outlier) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
+    if ((voxel_leaf || outlier || statout) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
         d_depth.resize(n_streams, nullptr); d_color.resize(n_streams, nullptr);
         for (int s = 0; s < n_streams; s++) {
             const size_t db = (size_t)cfgs[s].depth.width * cfgs[s].depth.height * 2;
@@ -509,7 +548,7 @@ int main(int argc, char** argv)
                     std::cout << "Voxel grid over " << n_gpus << " GPU(s): kernels " << vstats.kernels_ms << " ms, exchange " << vstats.exchange_ms
                               << " ms (" << vstats.exchanged_bytes << " B), root " << vstats.root_voxel_ms << " ms, " << vstats.partials
                               << (voxel_route == PCS_NODE_VOXEL_PARTIALS ? " partials -> " : " points -> ") << vstats.voxels << " voxels" << std::endl;
-            } else if (outlier) {
+            } else if (outlier || statout) {
                 // the payload on the device (under -Z / -B / -d as ever), the filter on its device count, then the voxel grid on the
                 // filter's device count or the kept records out: no count leaves the device in between
                 for (int s = 0; s < n_streams; s++) {
@@ -522,29 +561,42 @@ int main(int argc, char** argv)
                 rc = pcs_process_frames_device(ctx, reinterpret_cast<const uint16_t* const*>(d_depth.data()),
                                                reinterpret_cast<const uint8_t* const*>(d_color.data()), static_cast<int16_t*>(d_pay), max_shorts,
                                                static_cast<int32_t*>(d_pay_counts));
-                if (rc == PCS_OK)
-                    rc = pcs_radius_outlier_device_counted(ctx, static_cast<const int16_t*>(d_pay), d_total, max_points, outlier_radius, outlier_neighbors,
+                // (the last filter's output and device count: what the next stage reads)
+                const int16_t* d_last = static_cast<const int16_t*>(d_pay);
+                const int32_t* d_nlast = d_total;
+                if (rc == PCS_OK && outlier) {
+                    rc = pcs_radius_outlier_device_counted(ctx, d_last, d_nlast, max_points, outlier_radius, outlier_neighbors,
                                                            static_cast<int16_t*>(d_filtered), max_shorts, static_cast<int32_t*>(d_nfiltered));
+                    d_last = static_cast<const int16_t*>(d_filtered); d_nlast = static_cast<const int32_t*>(d_nfiltered);
+                }
+                if (rc == PCS_OK && statout) {
+                    rc = pcs_stat_outlier_device_counted(ctx, d_last, d_nlast, max_points, &statout_params, static_cast<int16_t*>(d_stat), max_shorts,
+                                                         static_cast<int32_t*>(d_nstat), static_cast<pcs_stat_outlier_stats*>(d_stat_block));
+                    d_last = static_cast<const int16_t*>(d_stat); d_nlast = static_cast<const int32_t*>(d_nstat);
+                }
                 if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
                 if (voxel_leaf) {
                     auto run_voxel = [&]() {
-                        return pcs_voxel_grid_device_counted(ctx, static_cast<const int16_t*>(d_filtered), static_cast<const int32_t*>(d_nfiltered),
+                        return pcs_voxel_grid_device_counted(ctx, d_last, d_nlast,
                                                              max_points, voxel_leaf, static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS,
                                                              static_cast<int32_t*>(d_nvox));
                     };
                     rc = run_voxel();
                     if (rc != PCS_OK || !fetch_voxels(run_voxel)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
                 }
-                int32_t n_in = 0, n_kept = 0;
-                if (pcs_memcpy_d2h(ctx, &n_in, d_total, sizeof n_in) != PCS_OK || pcs_memcpy_d2h(ctx, &n_kept, d_nfiltered, sizeof n_kept) != PCS_OK ||
+                int32_t n_in = 0, n_kept = 0, n_last = 0;
+                if (pcs_memcpy_d2h(ctx, &n_in, d_total, sizeof n_in) != PCS_OK ||
+                    (outlier && pcs_memcpy_d2h(ctx, &n_kept, d_nfiltered, sizeof n_kept) != PCS_OK) ||
+                    pcs_memcpy_d2h(ctx, &n_last, d_nlast, sizeof n_last) != PCS_OK ||
                     pcs_synchronize(ctx) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
                 if (!voxel_leaf) {
-                    size_bytes = n_kept * PCS_POINT_BYTES;
-                    if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, d_filtered, (size_t)size_bytes) != PCS_OK) return 1;
+                    size_bytes = n_last * PCS_POINT_BYTES;
+                    if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, d_last, (size_t)size_bytes) != PCS_OK) return 1;
                     pcs_synchronize(ctx);
                     memcpy(stitched.data(), &size_bytes, sizeof(int));
                 }
-                if (timer) std::cout << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl;
+                if (timer && outlier) std::cout << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl;
+                if (timer && statout && !print_statout()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
             } else if (voxel_leaf) {
                 for (int s = 0; s < n_streams; s++) {
                     if (pcs_memcpy_h2d(ctx, d_depth[s], depth[s].data(), depth[s].size() * 2) != PCS_OK ||
@@ -644,8 +696,30 @@ int main(int argc, char** argv)
                     if (!voxel_leaf) total_pts = kept;
                 }
             }
+            if (statout) {
+                // behind -O: its output and its device count, through the counted form; else the stitched payload and its host count
+                const size_t out_shorts = (size_t)n_streams * cam_cap_bytes / 2;
+                rc = outlier ? pcs_stat_outlier_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nfiltered), outlier_in, &statout_params,
+                                                               static_cast<int16_t*>(d_stat), out_shorts, static_cast<int32_t*>(d_nstat),
+                                                               static_cast<pcs_stat_outlier_stats*>(d_stat_block))
+                             : pcs_stat_outlier_device(ctx, d_result, total_pts, &statout_params, static_cast<int16_t*>(d_stat), out_shorts,
+                                                       static_cast<int32_t*>(d_nstat), static_cast<pcs_stat_outlier_stats*>(d_stat_block));
+                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                d_result = static_cast<const int16_t*>(d_stat);
+                if (!voxel_leaf) {      // (with -V the voxel grid reads the count where it is)
+                    int32_t kept = 0;
+                    if (pcs_memcpy_d2h(ctx, &kept, d_nstat, sizeof kept) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) {
+                        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
+                    }
+                    total_pts = kept;
+                }
+                if (timer && !print_statout()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+            }
             if (voxel_leaf) {
                 auto run_voxel = [&]() {
+                    if (statout)
+                        return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nstat), outlier_in, voxel_leaf,
+                                                             static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
                     if (outlier)
                         return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nfiltered), outlier_in, voxel_leaf,
                                                              static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
@@ -688,7 +762,7 @@ int main(int argc, char** argv)
     if (d_vox) pcs_device_free(ctx, d_vox);
     if (d_nvox) pcs_device_free(ctx, d_nvox);
     if (d_stitched) pcs_device_free(ctx, d_stitched);
-    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts, d_filtered, d_nfiltered}) if (p) pcs_device_free(ctx, p);
+    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts, d_filtered, d_nfiltered, d_stat, d_nstat, d_stat_block}) if (p) pcs_device_free(ctx, p);
     if (node) pcs_node_destroy(node);
     stitched.release();
     pcs_destroy(ctx);

@@ -373,6 +373,25 @@ struct OutlierIndexView {
     uint32_t                  slots, capacity;
 };
 hipError_t  outlier_index_view(uint32_t capacity, void* d_ws, size_t ws_bytes, OutlierIndexView* view);
+// What stage 0 leaves and stages 7 to 9 read, for a flag kernel other than the radius filter's (pcs_kernels_stat.hip): the control
+// block (the record count) and keep_bits[w] = the keep bits of records 64 w .. 64 w + 63, a bit at or beyond the count 0.
+struct OutlierKeepView {
+    const OutlierCtl*   ctl;
+    unsigned long long* keep_bits;
+};
+hipError_t  outlier_keep_view(uint32_t capacity, void* d_ws, size_t ws_bytes, OutlierKeepView* view);
+
+// Statistical outlier removal (pcs_stat_outlier_device, pcs_kernels_stat.hip; the definition: DESIGN.md section 3 "Statistical
+// outlier removal"): kStatStages launches on one stream, each its own call as launch_outlier_stage's are. Stages 0 to 5 are that
+// filter's index with cell edge max_dist_mm, 6 to 9 knn, sums, threshold and flag, 10 to 12 that filter's tile count, tile scan and
+// emit, 13 (only with d_stats: eight int64, 8-byte aligned) the statistics block. d_ws: stat_workspace_bytes(capacity) bytes,
+// 256-byte aligned; count and capacity as launch_outlier_stage's.
+constexpr int kStatStages = 14;
+size_t      stat_workspace_bytes(uint32_t capacity);
+const char* stat_stage_name(int stage);
+hipError_t  launch_stat_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity, int mean_k,
+                              int std_mul_milli, int max_dist_mm, void* d_ws, size_t ws_bytes, int16_t* d_out, int32_t* d_out_points,
+                              long long* d_stats, hipStream_t st);
 
 // Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
 // index is the outlier filter's, cell edge max_dist_mm (stages 0 to 5 of launch_outlier_stage over the target; `index` is its view,

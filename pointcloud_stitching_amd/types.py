@@ -28,6 +28,14 @@ OUTLIER_RADIUS_MIN, OUTLIER_RADIUS_MAX = 1, 1000          # pcs_radius_outlier*:
 OUTLIER_NEIGHBORS_MIN, OUTLIER_NEIGHBORS_MAX = 1, 255     # ... min_neighbors
 OUTLIER_LAUNCHES = 10                                     # intervals one call adds to kernel_times_ms under kernel_timing
 
+STAT_K_MIN, STAT_K_MAX = 1, 64                            # pcs_stat_outlier*: mean_k
+STAT_MUL_MILLI_MAX = 10000                                # ... std_mul_milli, 0..
+STAT_DIST_MIN, STAT_DIST_MAX = 1, 1000                    # ... max_dist_mm
+STAT_OUTLIER_LAUNCHES = 14                                # kernel_times_ms intervals of one call with a statistics block (13 without)
+STAT_OUTLIER_STAGES = ("clear", "insert", "cell sums", "cell scan", "cell starts", "scatter", "knn", "sums", "threshold", "flag",
+                       "tile count", "tile scan", "emit", "finish")
+STAT_STATS_FIELDS = ("considered", "dense", "s1", "s2_lo", "s2_hi", "threshold", "kept", "reserved")
+
 ALIGN_DIST_MIN, ALIGN_DIST_MAX = 1, 1000                  # pcs_align_*: max_dist_mm
 ALIGN_ITERATIONS_MAX = 100
 ALIGN_STOP_ITERATIONS, ALIGN_STOP_CONVERGED, ALIGN_STOP_REFUSED = 0, 1, 2
@@ -126,6 +134,23 @@ class NormalParams(C.Structure):
     def make(cls, radius_mm: int, min_neighbors: int, flatness: int = 0, viewpoint_mm=None, reserved: int = 0) -> "NormalParams":
         vp = (0, 0, 0) if viewpoint_mm is None else tuple(int(v) for v in viewpoint_mm)
         return cls(int(radius_mm), int(min_neighbors), int(flatness), int(viewpoint_mm is not None), (C.c_int32 * 3)(*vp), int(reserved))
+
+
+class StatOutlierParams(C.Structure):
+    """pcs_stat_outlier_params."""
+    _fields_ = [("mean_k", C.c_int32), ("std_mul_milli", C.c_int32), ("max_dist_mm", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, mean_k: int, std_mul_milli: int, max_dist_mm: int, reserved: int = 0) -> "StatOutlierParams":
+        return cls(int(mean_k), int(std_mul_milli), int(max_dist_mm), int(reserved))
+
+
+class StatOutlierStatsC(C.Structure):
+    """struct pcs_stat_outlier_stats: eight int64."""
+    _fields_ = [(name, C.c_int64) for name in STAT_STATS_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in STAT_STATS_FIELDS}
 
 
 class AlignSumsC(C.Structure):
