@@ -330,22 +330,13 @@ void finish_stitched(const pcs_ctx* c, const int32_t* h, int16_t* stitched, int 
 
 namespace pcs_host {
 
-// The voxel workspace. Growing it means: wait for the stream (the old one may be in use), free, allocate — a device-wide stall.
-// A caller whose sizes creep upwards (the node's root reduces a different number of partials every frame-set) must not pay that
-// at every new maximum: a workspace that has to grow takes a quarter more than asked.
+// The voxel workspace: ensure_ws's policy (the node's root reduces a different number of partials every frame-set: the headroom is for it).
 int ensure_voxel_ws(pcs_ctx* c, size_t need)
 {
     if (need <= c->s_voxel_ws_cap && c->s_voxel_ws) return PCS_OK;
-    const size_t exact = need;
-    if (c->s_voxel_ws) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        need += need / 4;
-    }
     c->vox_state.clean = false;                                                   // (a new one may land on the same address)
     c->vox_state.spl_leaf = 0;
-    int rc = ensure(c, c->s_voxel_ws, c->s_voxel_ws_cap, need);
-    if (rc == PCS_ERR_NOMEM && need != exact) rc = ensure(c, c->s_voxel_ws, c->s_voxel_ws_cap, exact);      // the headroom is a wish
-    return rc;
+    return ensure_ws(c, c->s_voxel_ws, c->s_voxel_ws_cap, need);
 }
 
 int acquire_event_pair(pcs_ctx* c, std::pair<hipEvent_t, hipEvent_t>& pr)

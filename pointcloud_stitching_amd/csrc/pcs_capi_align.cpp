@@ -1,11 +1,12 @@
-// pcs_capi_align.cpp — extrinsics refinement's part of the C ABI (include/pcs_hip.h, "extrinsics refinement"): the argument checks,
-// the workspace and the launches of pcs_kernels_align.hip over the outlier filter's index (the definition: DESIGN.md section 3; the
-// kernels: section 5), the rigid fit on the host (pcs_align_solve: exact 128-bit covariance, a one-sided Jacobi SVD in double) and the
-// ICP loop. The calls read no context predicate — flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH do not matter: the loop moves
-// the source through launch_transform_payloads itself, pcs_transform_payloads_device's arithmetic without its context checks.
-// The point-to-plane forms (pcs_align_plane_*, pcs_align_payloads_plane_device) follow in the file's second half.
+// pcs_capi_align.cpp — extrinsics refinement's part of the C ABI (include/pcs_hip.h, "extrinsics refinement" and "extrinsics
+// refinement, point to plane"): the argument checks, the workspace and the launches of pcs_kernels_align.hip over the outlier filter's
+// index (the definition: DESIGN.md section 3 "Alignment sums" and "Plane sums"; the kernels: section 5), the two fits on the host
+// (pcs_align_solve: exact 128-bit covariance, a one-sided Jacobi SVD in double; pcs_align_plane_solve: the 6 x 6 normal equations) and
+// the ICP loop, written once for both. The calls read no context predicate — flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH do
+// not matter: the loop moves the source through launch_transform_payloads itself, pcs_transform_payloads_device's arithmetic without
+// its context checks. The plane forms have the target's normals beside the index: everything else is shared, told apart by the
+// number of int64 terms of the sums (kAlignTerms / kPlaneTerms).
 
-#include <climits>
 #include <cmath>
 #include <cstring>
 #include <exception>
@@ -14,22 +15,14 @@
 
 using namespace pcs_host;
 
-using AlignSums = struct pcs_align_sums;          // (the bare name is the host form, a function)
+using AlignSums = struct pcs_align_sums;          // (the bare names are the host forms, functions)
+using PlaneSums = struct pcs_align_plane_sums;
 
 static_assert(sizeof(AlignSums) == kAlignTerms * sizeof(int64_t), "pcs_align_sums is kAlignTerms int64 words, no padding");
+static_assert(sizeof(PlaneSums) == kPlaneTerms * sizeof(int64_t), "pcs_align_plane_sums is kPlaneTerms int64 words, no padding");
+static_assert(sizeof(pcs_align_plane_params) == 64, "pcs_align_plane_params: pcs_align_params' fields, then pcs_normal_params");
 
 namespace {
-
-constexpr int kMaxPoints = INT_MAX / PCS_POINT_BYTES;      // a payload's byte count fits an int32
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// [a, a + na) and [b, b + nb) share a byte
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
-}
 
 // What the sums forms and the loop check about their payloads; `who` names the entry point.
 int check_payloads(pcs_ctx* c, const char* who, const void* source, const char* s_name, int n_source, const void* target,
@@ -64,79 +57,131 @@ int check_sums_args(pcs_ctx* c, const char* who, const void* source, const char*
     return PCS_OK;
 }
 
-// The align workspace of a context, at least `need` bytes: ensure_outlier_ws's policy (a quarter of headroom when it grows; growing
-// waits for the stream; it never shrinks).
-int ensure_align_ws(pcs_ctx* c, size_t need)
+int check_plane_sums_args(pcs_ctx* c, const char* who, const void* source, const char* s_name, int n_source, const void* target,
+                          const char* t_name, int n_target, const void* normals, const char* n_name, int max_dist_mm, const void* sums,
+                          const char* sums_name, const void* dist2, const char* dist2_name)
 {
-    if (need <= c->s_align_ws_cap && c->s_align_ws) return PCS_OK;
-    const size_t exact = need;
-    if (c->s_align_ws) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        need += need / 4;
-    }
-    int rc = ensure(c, c->s_align_ws, c->s_align_ws_cap, need);
-    if (rc == PCS_ERR_NOMEM && need != exact) rc = ensure(c, c->s_align_ws, c->s_align_ws_cap, exact);      // the headroom is a wish
-    return rc;
+    if (int rc = check_payloads(c, who, source, s_name, n_source, target, t_name, n_target, max_dist_mm)) return rc;
+    if (n_target && !normals) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is NULL", who, n_name);
+    if ((uintptr_t)normals & 7u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 8-byte aligned", who, n_name);
+    if (!sums) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is NULL", who, sums_name);
+    if ((uintptr_t)sums & 7u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 8-byte aligned", who, sums_name);
+    if ((uintptr_t)dist2 & 3u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 4-byte aligned", who, dist2_name);
+    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES, db = (size_t)n_source * 4,
+                 nb = (size_t)n_target * PCS_NORMAL_BYTES;
+    if (ranges_overlap(sums, sizeof(PlaneSums), source, sb) || ranges_overlap(sums, sizeof(PlaneSums), target, tb) ||
+        ranges_overlap(sums, sizeof(PlaneSums), normals, nb))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s, %s or %s", who, sums_name, s_name, t_name, n_name);
+    if (ranges_overlap(dist2, db, source, sb) || ranges_overlap(dist2, db, target, tb) || ranges_overlap(dist2, db, normals, nb))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s, %s or %s", who, dist2_name, s_name, t_name, n_name);
+    if (ranges_overlap(dist2, db, sums, sizeof(PlaneSums)))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s", who, dist2_name, sums_name);
+    return PCS_OK;
 }
 
-// One call's carve of the workspace: the target's index first (outlier_workspace_bytes(n_target), 256-byte aligned as the slab is),
-// then the partials, then what the form asked for.
+// One call's carve of the align workspace: the target's index first (outlier_workspace_bytes(n_target), 256-byte aligned as the slab
+// is), then the partials (`terms` int64 each), the plane forms' normals in cell order, then what the form asked for.
 struct AlignWs {
-    void*           index = nullptr;  size_t index_bytes = 0;
-    long long*      partials = nullptr;
-    int16_t*        moved = nullptr;          // the loop's moved source
-    AlignSums* sums = nullptr;           // the loop's / the host form's sums
-    uint32_t*       dist2 = nullptr;          // the host form's dist2
+    void*               index = nullptr;  size_t index_bytes = 0;
+    long long*          partials = nullptr;
+    unsigned long long* pnorm = nullptr;  size_t pnorm_bytes = 0;      // plane: parallel to the index's xyz[]
+    int16_t*            moved = nullptr;          // the loop's moved source
+    long long*          sums = nullptr;           // the loop's / the host form's sums, `terms` words
+    uint32_t*           dist2 = nullptr;          // the host form's dist2
+    int16_t*            normals = nullptr;        // plane: the host form's staged / the loop's estimated target normals (record order)
 };
-int carve_align_ws(pcs_ctx* c, int n_source, int n_target, bool want_moved, bool want_sums, bool want_dist2, AlignWs* ws)
+enum : unsigned { kWsMoved = 1, kWsSums = 2, kWsDist2 = 4, kWsNormals = 8 };
+int carve_align_ws(pcs_ctx* c, int terms, int n_source, int n_target, unsigned want, AlignWs* ws)
 {
     const size_t index_bytes = n_target ? up256(outlier_workspace_bytes((uint32_t)n_target)) : 0;
-    const size_t part_bytes = up256((size_t)align_partials((uint32_t)n_source) * kAlignTerms * sizeof(long long));
-    const size_t moved_bytes = want_moved ? up256((size_t)n_source * PCS_POINT_BYTES) : 0;
-    const size_t sums_bytes = want_sums ? up256(sizeof(AlignSums)) : 0;
-    const size_t dist2_bytes = want_dist2 ? up256((size_t)n_source * 4) : 0;
-    if (int rc = ensure_align_ws(c, index_bytes + part_bytes + moved_bytes + sums_bytes + dist2_bytes)) return rc;
+    const size_t part_bytes = up256((size_t)align_partials((uint32_t)n_source) * terms * sizeof(long long));
+    const size_t pnorm_bytes = terms == kPlaneTerms ? up256((size_t)n_target * PCS_NORMAL_BYTES) : 0;
+    const size_t moved_bytes = (want & kWsMoved) ? up256((size_t)n_source * PCS_POINT_BYTES) : 0;
+    const size_t sums_bytes = (want & kWsSums) ? up256((size_t)terms * sizeof(long long)) : 0;
+    const size_t dist2_bytes = (want & kWsDist2) ? up256((size_t)n_source * 4) : 0;
+    const size_t normals_bytes = (want & kWsNormals) ? up256((size_t)n_target * PCS_NORMAL_BYTES) : 0;
+    if (int rc = ensure_ws(c, c->s_align_ws, c->s_align_ws_cap,
+                           index_bytes + part_bytes + pnorm_bytes + moved_bytes + sums_bytes + dist2_bytes + normals_bytes))
+        return rc;
     uint8_t* w = static_cast<uint8_t*>(c->s_align_ws);
     ws->index = w; ws->index_bytes = index_bytes; w += index_bytes;
     ws->partials = reinterpret_cast<long long*>(w); w += part_bytes;
+    ws->pnorm = reinterpret_cast<unsigned long long*>(w); ws->pnorm_bytes = (size_t)n_target * PCS_NORMAL_BYTES; w += pnorm_bytes;
     ws->moved = reinterpret_cast<int16_t*>(w); w += moved_bytes;
-    ws->sums = reinterpret_cast<AlignSums*>(w); w += sums_bytes;
-    ws->dist2 = reinterpret_cast<uint32_t*>(w);
+    ws->sums = reinterpret_cast<long long*>(w); w += sums_bytes;
+    ws->dist2 = reinterpret_cast<uint32_t*>(w); w += dist2_bytes;
+    ws->normals = reinterpret_cast<int16_t*>(w);
     return PCS_OK;
 }
 
-// Stages 0 to 5 of the outlier filter over the target, cell edge max_dist_mm, one timing bracket per launch; its view into *view.
-// n_target == 0: nothing launched, *have = false.
-int build_index(pcs_ctx* c, const int16_t* d_target, int n_target, int max_dist_mm, const AlignWs& ws, OutlierIndexView* view, bool* have)
+// The target's cell index, cell edge max_dist_mm, and with d_target_normals (the plane forms) those normals scattered beside it:
+// pnorm set to all ones on the stream, then one launch. n_target == 0: nothing launched, *have = false.
+int build_target_index(pcs_ctx* c, const int16_t* d_target, int n_target, const int16_t* d_target_normals, int max_dist_mm, const AlignWs& ws,
+                       OutlierIndexView* view, bool* have)
 {
     *have = n_target > 0;
     if (!*have) return PCS_OK;
-    for (int stage = 0; stage <= 5; stage++) {
-        KernelTimer timer(c);
-        if (timer.rc) return timer.rc;
-        // (min_neighbors: stages 0 to 5 do not read it; 1 passes the launcher's range check)
-        HIPCHK(c, launch_outlier_stage(stage, d_target, (uint32_t)n_target, nullptr, (uint32_t)n_target, max_dist_mm, 1, ws.index,
-                                       ws.index_bytes, nullptr, nullptr, c->stream));
-        if (int rc = timer.finish()) return rc;
-    }
-    HIPCHK(c, outlier_index_view((uint32_t)n_target, ws.index, ws.index_bytes, view));
+    if (int rc = build_cell_index(c, d_target, n_target, max_dist_mm, ws.index, ws.index_bytes, view)) return rc;
+    if (!d_target_normals) return PCS_OK;
+    HIPCHK(c, hipMemsetAsync(ws.pnorm, 0xFF, ws.pnorm_bytes, c->stream));
+    PCS_TIMED(c, launch_align_plane_scatter(d_target, d_target_normals, (uint32_t)n_target, *view, max_dist_mm, ws.pnorm, c->stream));
     return PCS_OK;
 }
 
-// match + reduce of n_source records at d_source into *d_sums (and d_dist2): two launches, one with an empty source.
-int run_match(pcs_ctx* c, const int16_t* d_source, int n_source, const OutlierIndexView* view, int max_dist_mm, const AlignWs& ws,
-              AlignSums* d_sums, uint32_t* d_dist2)
+// match + reduce of n_source records at d_source into d_sums[terms] (and d_dist2): two launches, one with an empty source.
+int run_match(pcs_ctx* c, int terms, const int16_t* d_source, int n_source, const OutlierIndexView* view, int max_dist_mm, const AlignWs& ws,
+              long long* d_sums, uint32_t* d_dist2)
 {
-    if (n_source) {
-        KernelTimer timer(c);
-        if (timer.rc) return timer.rc;
-        HIPCHK(c, launch_align_match(d_source, (uint32_t)n_source, view, max_dist_mm, ws.partials, d_dist2, c->stream));
-        if (int rc = timer.finish()) return rc;
+    const uint32_t n = (uint32_t)n_source;
+    if (terms == kPlaneTerms) {
+        if (n) PCS_TIMED(c, launch_align_plane_match(d_source, n, view, ws.pnorm, max_dist_mm, ws.partials, d_dist2, c->stream));
+        PCS_TIMED(c, launch_align_plane_reduce(ws.partials, align_partials(n), d_sums, c->stream));
+    } else {
+        if (n) PCS_TIMED(c, launch_align_match(d_source, n, view, max_dist_mm, ws.partials, d_dist2, c->stream));
+        PCS_TIMED(c, launch_align_reduce(ws.partials, align_partials(n), d_sums, c->stream));
     }
-    KernelTimer timer(c);
-    if (timer.rc) return timer.rc;
-    HIPCHK(c, launch_align_reduce(ws.partials, align_partials((uint32_t)n_source), reinterpret_cast<long long*>(d_sums), c->stream));
-    return timer.finish();
+    return PCS_OK;
+}
+
+// The sums forms behind their checks. Device: d_target_normals is the caller's (nullptr: point to point). Host: source, target and
+// normals staged (the normals in the align workspace), the sums and dist2 fetched; *out is written whole, at the end.
+int sums_device(pcs_ctx* c, int terms, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
+                const int16_t* d_target_normals, int max_dist_mm, void* d_sums, uint32_t* d_dist2)
+{
+    DeviceGuard guard(c->device);
+    AlignWs ws;
+    if (int rc = carve_align_ws(c, terms, n_source, n_source ? n_target : 0, 0, &ws)) return rc;
+    OutlierIndexView view{};
+    bool have = false;
+    if (n_source)          // (an empty source needs no index)
+        if (int rc = build_target_index(c, d_target, n_target, d_target_normals, max_dist_mm, ws, &view, &have)) return rc;
+    return run_match(c, terms, d_source, n_source, have ? &view : nullptr, max_dist_mm, ws, static_cast<long long*>(d_sums), d_dist2);
+}
+
+int sums_host(pcs_ctx* c, int terms, const int16_t* source, int n_source, const int16_t* target, int n_target, const int16_t* target_normals,
+              int max_dist_mm, void* out, uint32_t* dist2)
+{
+    DeviceGuard guard(c->device);
+    const bool plane = terms == kPlaneTerms;
+    const size_t tb = (size_t)n_target * PCS_POINT_BYTES;
+    if (int rc = stage_payload(c, source, (size_t)n_source * PCS_POINT_BYTES, tb)) return rc;
+    AlignWs ws;
+    if (int rc = carve_align_ws(c, terms, n_source, n_source ? n_target : 0, kWsSums | (dist2 ? kWsDist2 : 0) | (plane ? kWsNormals : 0), &ws))
+        return rc;
+    if (tb && n_source) {
+        HIPCHK(c, hipMemcpyAsync(c->s_voxel_out, target, tb, hipMemcpyHostToDevice, c->stream));
+        if (plane) HIPCHK(c, hipMemcpyAsync(ws.normals, target_normals, (size_t)n_target * PCS_NORMAL_BYTES, hipMemcpyHostToDevice, c->stream));
+    }
+    OutlierIndexView view{};
+    bool have = false;
+    if (n_source)
+        if (int rc = build_target_index(c, c->s_voxel_out, n_target, plane ? ws.normals : nullptr, max_dist_mm, ws, &view, &have)) return rc;
+    if (int rc = run_match(c, terms, c->s_voxel_in, n_source, have ? &view : nullptr, max_dist_mm, ws, ws.sums, dist2 ? ws.dist2 : nullptr)) return rc;
+    long long got[kPlaneTerms];
+    if (int rc = fetch(c, got, ws.sums, (size_t)terms * sizeof(long long))) return rc;
+    if (dist2 && n_source) HIPCHK(c, hipMemcpy(dist2, ws.dist2, (size_t)n_source * 4, hipMemcpyDeviceToHost));
+    std::memcpy(out, got, (size_t)terms * sizeof(long long));
+    return PCS_OK;
 }
 
 // ---- the rigid fit -----------------------------------------------------------------------------------
@@ -241,283 +286,6 @@ int solve_sums(const AlignSums& s, double delta[16], double* rms_mm)
     return PCS_OK;
 }
 
-double rms_of(const AlignSums& s) { return s.matched > 0 ? std::sqrt((double)s.sd2 / (double)s.matched) : 0.0; }
-
-}  // namespace
-
-extern "C" {
-
-int pcs_align_sums_device(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target, int max_dist_mm,
-                          AlignSums* d_sums, uint32_t* d_dist2)
-{
-    if (!c) return PCS_ERR_INVALID_ARG;
-    if (int rc = check_sums_args(c, "pcs_align_sums_device", d_source, "d_source", n_source, d_target, "d_target", n_target, max_dist_mm,
-                                 d_sums, "d_sums", d_dist2, "d_dist2"))
-        return rc;
-    DeviceGuard guard(c->device);
-    AlignWs ws;
-    if (int rc = carve_align_ws(c, n_source, n_source ? n_target : 0, false, false, false, &ws)) return rc;
-    OutlierIndexView view{};
-    bool have = false;
-    if (n_source)          // (an empty source needs no index)
-        if (int rc = build_index(c, d_target, n_target, max_dist_mm, ws, &view, &have)) return rc;
-    return run_match(c, d_source, n_source, have ? &view : nullptr, max_dist_mm, ws, d_sums, d_dist2);
-}
-
-int pcs_align_sums(pcs_ctx* c, const int16_t* source, int n_source, const int16_t* target, int n_target, int max_dist_mm,
-                   AlignSums* out, uint32_t* dist2)
-try {
-    if (!c) return PCS_ERR_INVALID_ARG;
-    if (int rc = check_sums_args(c, "pcs_align_sums", source, "source", n_source, target, "target", n_target, max_dist_mm, out, "out",
-                                 dist2, "dist2"))
-        return rc;
-    DeviceGuard guard(c->device);
-    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES;
-    // the host forms' payload staging (pcs_voxel_grid's and pcs_radius_outlier's: all synchronous, none leaves anything in it)
-    int rc;
-    if ((rc = ensure_idle(c, c->s_voxel_in, c->s_voxel_in_cap, sb))) return rc;
-    if ((rc = ensure_idle(c, c->s_voxel_out, c->s_voxel_out_cap, tb))) return rc;
-    AlignWs ws;
-    if ((rc = carve_align_ws(c, n_source, n_source ? n_target : 0, false, true, dist2 != nullptr, &ws))) return rc;
-    if (sb) HIPCHK(c, hipMemcpyAsync(c->s_voxel_in, source, sb, hipMemcpyHostToDevice, c->stream));
-    if (tb && n_source) HIPCHK(c, hipMemcpyAsync(c->s_voxel_out, target, tb, hipMemcpyHostToDevice, c->stream));
-    OutlierIndexView view{};
-    bool have = false;
-    if (n_source && (rc = build_index(c, c->s_voxel_out, n_target, max_dist_mm, ws, &view, &have))) return rc;
-    if ((rc = run_match(c, c->s_voxel_in, n_source, have ? &view : nullptr, max_dist_mm, ws, ws.sums, dist2 ? ws.dist2 : nullptr))) return rc;
-    AlignSums got;
-    HIPCHK(c, hipMemcpyAsync(&got, ws.sums, sizeof got, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (dist2 && n_source) HIPCHK(c, hipMemcpy(dist2, ws.dist2, (size_t)n_source * 4, hipMemcpyDeviceToHost));
-    *out = got;
-    return PCS_OK;
-} catch (const std::exception& ex) {
-    return fail(c, PCS_ERR_NOMEM, "pcs_align_sums: host allocation failed (%s)", ex.what());
-}
-
-int pcs_align_solve(const AlignSums* sums, double delta[16], double* rms_mm)
-{
-    if (!sums) return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: sums is NULL");
-    if (!delta) return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: delta is NULL");
-    if (sums->matched < 0 || sums->considered < sums->matched)
-        return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: matched %lld is outside 0..considered %lld", (long long)sums->matched,
-                    (long long)sums->considered);
-    double d[16], rms = 0;
-    if (int rc = solve_sums(*sums, d, &rms)) return rc;
-    std::memcpy(delta, d, sizeof d);
-    if (rms_mm) *rms_mm = rms;
-    return PCS_OK;
-}
-
-int pcs_align_payloads_device(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
-                              const pcs_align_params* params, const float init[16], float out[16], pcs_align_report* report)
-{
-    static const char who[] = "pcs_align_payloads_device";
-    if (!c) return PCS_ERR_INVALID_ARG;
-    if (!params) return fail(c, PCS_ERR_INVALID_ARG, "%s: params is NULL", who);
-    if (int rc = check_payloads(c, who, d_source, "d_source", n_source, d_target, "d_target", n_target, params->max_dist_mm)) return rc;
-    if (params->iterations < 1 || params->iterations > PCS_ALIGN_ITERATIONS_MAX)
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: iterations %d is outside 1..%d", who, params->iterations, PCS_ALIGN_ITERATIONS_MAX);
-    if (params->source_stride < 1) return fail(c, PCS_ERR_INVALID_ARG, "%s: source_stride %d < 1", who, params->source_stride);
-    if (!(params->eps_rot_rad >= 0) || !std::isfinite(params->eps_rot_rad))
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: eps_rot_rad is negative or not finite", who);
-    if (!(params->eps_trans_mm >= 0) || !std::isfinite(params->eps_trans_mm))
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: eps_trans_mm is negative or not finite", who);
-    if (!init) return fail(c, PCS_ERR_INVALID_ARG, "%s: init is NULL", who);
-    if (!out) return fail(c, PCS_ERR_INVALID_ARG, "%s: out is NULL", who);
-    for (int k = 0; k < 16; k++)
-        if (!std::isfinite(init[k])) return fail(c, PCS_ERR_INVALID_ARG, "%s: init[%d] is not finite", who, k);
-    int trace_cap = 0;
-    if (report) {
-        if (report->trace_capacity < 0) return fail(c, PCS_ERR_INVALID_ARG, "%s: report->trace_capacity %d < 0", who, report->trace_capacity);
-        trace_cap = report->trace_capacity;
-    }
-    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES;
-    struct { const void* p; size_t n; const char* name; } outs[] = {
-        {out, 16 * sizeof(float), "out"},
-        {report, report ? sizeof *report : 0, "report"},
-        {report ? report->trace_transforms : nullptr, (size_t)trace_cap * 16 * sizeof(float), "report->trace_transforms"},
-        {report ? report->trace_sums : nullptr, (size_t)trace_cap * sizeof(AlignSums), "report->trace_sums"}};
-    for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) {
-        if (ranges_overlap(outs[i].p, outs[i].n, d_source, sb) || ranges_overlap(outs[i].p, outs[i].n, d_target, tb) ||
-            ranges_overlap(outs[i].p, outs[i].n, init, 16 * sizeof(float)) || ranges_overlap(outs[i].p, outs[i].n, params, sizeof *params))
-            return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps an input", who, outs[i].name);
-        for (size_t j = 0; j < i; j++)
-            if (ranges_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n))
-                return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s", who, outs[i].name, outs[j].name);
-    }
-
-    DeviceGuard guard(c->device);
-    const pcs_align_params P = *params;
-    float* const trace_f = report ? report->trace_transforms : nullptr;
-    AlignSums* const trace_s = report ? report->trace_sums : nullptr;
-    const int n_moved = n_source / P.source_stride;          // FLOOR, pcs_transform_payloads_device's rule
-    AlignWs ws;
-    if (int rc = carve_align_ws(c, n_moved, n_moved ? n_target : 0, true, true, false, &ws)) return rc;
-    OutlierIndexView view{};
-    bool have = false;
-    if (n_moved)
-        if (int rc = build_index(c, d_target, n_target, P.max_dist_mm, ws, &view, &have)) return rc;      // once per call
-
-    double T[16];
-    for (int k = 0; k < 16; k++) T[k] = init[k];
-    pcs_align_report rep{};
-    rep.trace_capacity = trace_cap; rep.trace_transforms = trace_f; rep.trace_sums = trace_s;
-    rep.stop_reason = PCS_ALIGN_STOP_ITERATIONS;
-    int status = PCS_OK;
-    const bool may_stop = P.eps_rot_rad > 0 || P.eps_trans_mm > 0;
-    for (int k = 0; k < P.iterations; k++) {
-        float F[16];
-        for (int j = 0; j < 16; j++) F[j] = (float)T[j];
-        if (n_moved) {
-            XformBatch xb;
-            std::memset(&xb, 0, sizeof xb);
-            xb.c[0].in = d_source;
-            xb.c[0].out = reinterpret_cast<uint8_t*>(ws.moved);
-            xb.c[0].n_out = (uint32_t)n_moved;
-            xb.c[0].ds = (uint32_t)P.source_stride;
-            std::memcpy(xb.c[0].M, F, sizeof xb.c[0].M);
-            KernelTimer timer(c);
-            if (timer.rc) return timer.rc;
-            HIPCHK(c, launch_transform_payloads(xb, 1, (uint32_t)n_moved, c->stream));
-            if (int rc = timer.finish()) return rc;
-        }
-        if (int rc = run_match(c, ws.moved, n_moved, have ? &view : nullptr, P.max_dist_mm, ws, ws.sums, nullptr)) return rc;
-        AlignSums S;
-        HIPCHK(c, hipMemcpyAsync(&S, ws.sums, sizeof S, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (k < trace_cap) {
-            if (trace_f) std::memcpy(trace_f + 16 * (size_t)k, F, sizeof F);
-            if (trace_s) trace_s[k] = S;
-            rep.trace_count = k + 1;
-        }
-        rep.iterations = k + 1;
-        if (k == 0) { rep.first_matched = S.matched; rep.first_considered = S.considered; rep.first_rms_mm = rms_of(S); }
-        rep.last_matched = S.matched; rep.last_considered = S.considered; rep.last_rms_mm = rms_of(S);
-        double D[16];
-        const int rc = solve_sums(S, D, nullptr);
-        if (rc) {
-            // the solve speaks through pcs_last_error(NULL); the loop's caller has a context
-            status = fail(c, rc, "%s: iteration %d: %s", who, k, pcs_last_error(nullptr));
-            rep.stop_reason = PCS_ALIGN_STOP_REFUSED;
-            break;
-        }
-        double N[16];
-        for (int a = 0; a < 4; a++)
-            for (int b = 0; b < 4; b++) N[4 * a + b] = D[4 * a] * T[b] + D[4 * a + 1] * T[4 + b] + D[4 * a + 2] * T[8 + b] + D[4 * a + 3] * T[12 + b];
-        std::memcpy(T, N, sizeof T);
-        if (may_stop) {
-            // the angle from both the trace and the antisymmetric part: exact for small angles, where acos(trace) is not
-            const double sx = D[9] - D[6], sy = D[2] - D[8], sz = D[4] - D[1];
-            const double angle = std::atan2(0.5 * std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0] + D[5] + D[10] - 1.0));
-            const double trans_mm = 1000.0 * std::sqrt(D[3] * D[3] + D[7] * D[7] + D[11] * D[11]);
-            if (angle <= P.eps_rot_rad && trans_mm <= P.eps_trans_mm) { rep.stop_reason = PCS_ALIGN_STOP_CONVERGED; break; }
-        }
-    }
-    for (int j = 0; j < 16; j++) out[j] = (float)T[j];
-    if (report) *report = rep;
-    return status;
-}
-
-}  // extern "C"
-
-// ---- point to plane ------------------------------------------------------------------------------------
-// pcs_align_plane_sums*, pcs_align_plane_solve, pcs_align_payloads_plane_device (include/pcs_hip.h, "extrinsics refinement, point to
-// plane"; DESIGN.md section 3 "Plane sums"): the same checks, index and loop with the target's normals beside the index.
-
-using PlaneSums = struct pcs_align_plane_sums;
-
-static_assert(sizeof(PlaneSums) == kPlaneTerms * sizeof(int64_t), "pcs_align_plane_sums is kPlaneTerms int64 words, no padding");
-static_assert(sizeof(pcs_align_plane_params) == 64, "pcs_align_plane_params: pcs_align_params' fields, then pcs_normal_params");
-
-namespace {
-
-// One plane call's carve of the align workspace: the target's index, the partials (480 bytes each), the normals in cell order, then
-// what the form asked for.
-struct PlaneWs {
-    void*               index = nullptr;  size_t index_bytes = 0;
-    long long*          partials = nullptr;
-    unsigned long long* pnorm = nullptr;  size_t pnorm_bytes = 0;      // parallel to the index's xyz[]
-    int16_t*            moved = nullptr;          // the loop's moved source
-    PlaneSums*          sums = nullptr;           // the loop's / the host form's sums
-    uint32_t*           dist2 = nullptr;          // the host form's dist2
-    int16_t*            normals = nullptr;        // the host form's staged / the loop's estimated target normals (record order)
-};
-int carve_plane_ws(pcs_ctx* c, int n_source, int n_target, bool want_moved, bool want_sums, bool want_dist2, bool want_normals, PlaneWs* ws)
-{
-    const size_t index_bytes = n_target ? up256(outlier_workspace_bytes((uint32_t)n_target)) : 0;
-    const size_t part_bytes = up256((size_t)align_partials((uint32_t)n_source) * kPlaneTerms * sizeof(long long));
-    const size_t pnorm_bytes = up256((size_t)n_target * PCS_NORMAL_BYTES);
-    const size_t moved_bytes = want_moved ? up256((size_t)n_source * PCS_POINT_BYTES) : 0;
-    const size_t sums_bytes = want_sums ? up256(sizeof(PlaneSums)) : 0;
-    const size_t dist2_bytes = want_dist2 ? up256((size_t)n_source * 4) : 0;
-    const size_t normals_bytes = want_normals ? up256((size_t)n_target * PCS_NORMAL_BYTES) : 0;
-    if (int rc = ensure_align_ws(c, index_bytes + part_bytes + pnorm_bytes + moved_bytes + sums_bytes + dist2_bytes + normals_bytes)) return rc;
-    uint8_t* w = static_cast<uint8_t*>(c->s_align_ws);
-    ws->index = w; ws->index_bytes = index_bytes; w += index_bytes;
-    ws->partials = reinterpret_cast<long long*>(w); w += part_bytes;
-    ws->pnorm = reinterpret_cast<unsigned long long*>(w); ws->pnorm_bytes = (size_t)n_target * PCS_NORMAL_BYTES; w += pnorm_bytes;
-    ws->moved = reinterpret_cast<int16_t*>(w); w += moved_bytes;
-    ws->sums = reinterpret_cast<PlaneSums*>(w); w += sums_bytes;
-    ws->dist2 = reinterpret_cast<uint32_t*>(w); w += dist2_bytes;
-    ws->normals = reinterpret_cast<int16_t*>(w);
-    return PCS_OK;
-}
-
-// The target's index (build_index's six launches) and its normals scattered beside it: pnorm set to all ones on the stream, then one
-// launch. n_target == 0: nothing launched, *have = false.
-int build_plane_index(pcs_ctx* c, const int16_t* d_target, int n_target, const int16_t* d_target_normals, int max_dist_mm, const PlaneWs& ws,
-                      OutlierIndexView* view, bool* have)
-{
-    AlignWs index_only;
-    index_only.index = ws.index; index_only.index_bytes = ws.index_bytes;
-    if (int rc = build_index(c, d_target, n_target, max_dist_mm, index_only, view, have)) return rc;
-    if (!*have) return PCS_OK;
-    HIPCHK(c, hipMemsetAsync(ws.pnorm, 0xFF, ws.pnorm_bytes, c->stream));
-    KernelTimer timer(c);
-    if (timer.rc) return timer.rc;
-    HIPCHK(c, launch_align_plane_scatter(d_target, d_target_normals, (uint32_t)n_target, *view, max_dist_mm, ws.pnorm, c->stream));
-    return timer.finish();
-}
-
-// match + reduce of n_source records at d_source into *d_sums (and d_dist2): two launches, one with an empty source.
-int run_plane_match(pcs_ctx* c, const int16_t* d_source, int n_source, const OutlierIndexView* view, int max_dist_mm, const PlaneWs& ws,
-                    PlaneSums* d_sums, uint32_t* d_dist2)
-{
-    if (n_source) {
-        KernelTimer timer(c);
-        if (timer.rc) return timer.rc;
-        HIPCHK(c, launch_align_plane_match(d_source, (uint32_t)n_source, view, ws.pnorm, max_dist_mm, ws.partials, d_dist2, c->stream));
-        if (int rc = timer.finish()) return rc;
-    }
-    KernelTimer timer(c);
-    if (timer.rc) return timer.rc;
-    HIPCHK(c, launch_align_plane_reduce(ws.partials, align_partials((uint32_t)n_source), reinterpret_cast<long long*>(d_sums), c->stream));
-    return timer.finish();
-}
-
-int check_plane_sums_args(pcs_ctx* c, const char* who, const void* source, const char* s_name, int n_source, const void* target,
-                          const char* t_name, int n_target, const void* normals, const char* n_name, int max_dist_mm, const void* sums,
-                          const char* sums_name, const void* dist2, const char* dist2_name)
-{
-    if (int rc = check_payloads(c, who, source, s_name, n_source, target, t_name, n_target, max_dist_mm)) return rc;
-    if (n_target && !normals) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is NULL", who, n_name);
-    if ((uintptr_t)normals & 7u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 8-byte aligned", who, n_name);
-    if (!sums) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is NULL", who, sums_name);
-    if ((uintptr_t)sums & 7u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 8-byte aligned", who, sums_name);
-    if ((uintptr_t)dist2 & 3u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 4-byte aligned", who, dist2_name);
-    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES, db = (size_t)n_source * 4,
-                 nb = (size_t)n_target * PCS_NORMAL_BYTES;
-    if (ranges_overlap(sums, sizeof(PlaneSums), source, sb) || ranges_overlap(sums, sizeof(PlaneSums), target, tb) ||
-        ranges_overlap(sums, sizeof(PlaneSums), normals, nb))
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s, %s or %s", who, sums_name, s_name, t_name, n_name);
-    if (ranges_overlap(dist2, db, source, sb) || ranges_overlap(dist2, db, target, tb) || ranges_overlap(dist2, db, normals, nb))
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s, %s or %s", who, dist2_name, s_name, t_name, n_name);
-    if (ranges_overlap(dist2, db, sums, sizeof(PlaneSums)))
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s", who, dist2_name, sums_name);
-    return PCS_OK;
-}
-
 // ---- the 6 x 6 solve ----------------------------------------------------------------------------------
 // Cyclic Jacobi on a symmetric n x n (row-major, n = 6): A -> diagonal, V the accumulated rotations (columns: eigenvectors).
 void jacobi_symmetric6(double A[36], double V[36])
@@ -611,11 +379,191 @@ int solve_plane_sums(const PlaneSums& s, double delta[16], double* rms_mm)
     return PCS_OK;
 }
 
-double rms_of(const PlaneSums& s) { return s.matched > 0 ? std::sqrt((double)s.sd2 / (double)s.matched) : 0.0; }
+template <class Sums>
+double rms_of(const Sums& s) { return s.matched > 0 ? std::sqrt((double)s.sd2 / (double)s.matched) : 0.0; }
+
+// ---- the ICP loop ------------------------------------------------------------------------------------
+// What the two loops differ in: the types, how the target is prepared once per call, the solve, and the `used` words of the report.
+// Params begins with max_dist_mm, iterations, source_stride, eps_rot_rad, eps_trans_mm in both (the static_assert above).
+struct PointLoop {
+    using Sums = AlignSums; using Params = pcs_align_params; using Report = pcs_align_report;
+    static constexpr const char* who = "pcs_align_payloads_device";
+    static constexpr int      terms = kAlignTerms;
+    static constexpr unsigned want = kWsMoved | kWsSums;
+    static int check(pcs_ctx*, const Params&) { return PCS_OK; }
+    static int prepare(pcs_ctx* c, const int16_t* d_target, int n_target, const Params& P, const AlignWs& ws, OutlierIndexView* view, bool* have)
+    {
+        return build_target_index(c, d_target, n_target, nullptr, P.max_dist_mm, ws, view, have);
+    }
+    static int solve(const Sums& s, double D[16]) { return solve_sums(s, D, nullptr); }
+    static void used(Report&, const Sums&, bool) {}
+};
+struct PlaneLoop {
+    using Sums = PlaneSums; using Params = pcs_align_plane_params; using Report = pcs_align_plane_report;
+    static constexpr const char* who = "pcs_align_payloads_plane_device";
+    static constexpr int      terms = kPlaneTerms;
+    static constexpr unsigned want = kWsMoved | kWsSums | kWsNormals;
+    static int check(pcs_ctx* c, const Params& P) { return check_normal_params(c, who, &P.normals); }
+    // the target's normals, its index, the normals beside it
+    static int prepare(pcs_ctx* c, const int16_t* d_target, int n_target, const Params& P, const AlignWs& ws, OutlierIndexView* view, bool* have)
+    {
+        if (n_target)
+            if (int rc = run_normals_device(c, d_target, n_target, P.normals, ws.normals, nullptr)) return rc;
+        return build_target_index(c, d_target, n_target, ws.normals, P.max_dist_mm, ws, view, have);
+    }
+    static int solve(const Sums& s, double D[16]) { return solve_plane_sums(s, D, nullptr); }
+    static void used(Report& r, const Sums& s, bool first) { (first ? r.first_used : r.last_used) = s.used; }
+};
+
+template <class K>
+int align_loop(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target, const typename K::Params* params,
+               const float init[16], float out[16], typename K::Report* report)
+{
+    using Sums = typename K::Sums;
+    const char* const who = K::who;
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (!params) return fail(c, PCS_ERR_INVALID_ARG, "%s: params is NULL", who);
+    if (int rc = check_payloads(c, who, d_source, "d_source", n_source, d_target, "d_target", n_target, params->max_dist_mm)) return rc;
+    if (params->iterations < 1 || params->iterations > PCS_ALIGN_ITERATIONS_MAX)
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: iterations %d is outside 1..%d", who, params->iterations, PCS_ALIGN_ITERATIONS_MAX);
+    if (params->source_stride < 1) return fail(c, PCS_ERR_INVALID_ARG, "%s: source_stride %d < 1", who, params->source_stride);
+    if (!(params->eps_rot_rad >= 0) || !std::isfinite(params->eps_rot_rad))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: eps_rot_rad is negative or not finite", who);
+    if (!(params->eps_trans_mm >= 0) || !std::isfinite(params->eps_trans_mm))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: eps_trans_mm is negative or not finite", who);
+    if (int rc = K::check(c, *params)) return rc;
+    if (!init) return fail(c, PCS_ERR_INVALID_ARG, "%s: init is NULL", who);
+    if (!out) return fail(c, PCS_ERR_INVALID_ARG, "%s: out is NULL", who);
+    for (int k = 0; k < 16; k++)
+        if (!std::isfinite(init[k])) return fail(c, PCS_ERR_INVALID_ARG, "%s: init[%d] is not finite", who, k);
+    int trace_cap = 0;
+    if (report) {
+        if (report->trace_capacity < 0) return fail(c, PCS_ERR_INVALID_ARG, "%s: report->trace_capacity %d < 0", who, report->trace_capacity);
+        trace_cap = report->trace_capacity;
+    }
+    float* const trace_f = report ? report->trace_transforms : nullptr;
+    Sums* const trace_s = report ? report->trace_sums : nullptr;
+    const NamedRange ins[] = {{d_source, (size_t)n_source * PCS_POINT_BYTES, "d_source"}, {d_target, (size_t)n_target * PCS_POINT_BYTES, "d_target"},
+                              {init, 16 * sizeof(float), "init"}, {params, sizeof *params, "params"}};
+    const NamedRange outs[] = {{out, 16 * sizeof(float), "out"}, {report, sizeof *report, "report"},
+                               {trace_f, (size_t)trace_cap * 16 * sizeof(float), "report->trace_transforms"},
+                               {trace_s, (size_t)trace_cap * sizeof(Sums), "report->trace_sums"}};
+    const NamedRange* with = nullptr;
+    if (const NamedRange* bad = first_overlap(outs, 4, ins, 4, &with))
+        return with ? fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s", who, bad->name, with->name)
+                    : fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps an input", who, bad->name);
+
+    DeviceGuard guard(c->device);
+    const typename K::Params P = *params;
+    const int n_moved = n_source / P.source_stride;          // FLOOR, pcs_transform_payloads_device's rule
+    AlignWs ws;
+    if (int rc = carve_align_ws(c, K::terms, n_moved, n_moved ? n_target : 0, K::want, &ws)) return rc;
+    OutlierIndexView view{};
+    bool have = false;
+    if (n_moved)
+        if (int rc = K::prepare(c, d_target, n_target, P, ws, &view, &have)) return rc;      // once per call
+
+    double T[16];
+    for (int k = 0; k < 16; k++) T[k] = init[k];
+    typename K::Report rep{};
+    rep.trace_capacity = trace_cap; rep.trace_transforms = trace_f; rep.trace_sums = trace_s;
+    rep.stop_reason = PCS_ALIGN_STOP_ITERATIONS;
+    int status = PCS_OK;
+    const bool may_stop = P.eps_rot_rad > 0 || P.eps_trans_mm > 0;
+    for (int k = 0; k < P.iterations; k++) {
+        float F[16];
+        for (int j = 0; j < 16; j++) F[j] = (float)T[j];
+        if (n_moved) {
+            XformBatch xb;
+            std::memset(&xb, 0, sizeof xb);
+            xb.c[0].in = d_source;
+            xb.c[0].out = reinterpret_cast<uint8_t*>(ws.moved);
+            xb.c[0].n_out = (uint32_t)n_moved;
+            xb.c[0].ds = (uint32_t)P.source_stride;
+            std::memcpy(xb.c[0].M, F, sizeof xb.c[0].M);
+            PCS_TIMED(c, launch_transform_payloads(xb, 1, (uint32_t)n_moved, c->stream));
+        }
+        if (int rc = run_match(c, K::terms, ws.moved, n_moved, have ? &view : nullptr, P.max_dist_mm, ws, ws.sums, nullptr)) return rc;
+        Sums S;
+        if (int rc = fetch(c, &S, ws.sums, sizeof S)) return rc;
+        if (k < trace_cap) {
+            if (trace_f) std::memcpy(trace_f + 16 * (size_t)k, F, sizeof F);
+            if (trace_s) trace_s[k] = S;
+            rep.trace_count = k + 1;
+        }
+        rep.iterations = k + 1;
+        if (k == 0) { rep.first_matched = S.matched; rep.first_considered = S.considered; rep.first_rms_mm = rms_of(S); K::used(rep, S, true); }
+        rep.last_matched = S.matched; rep.last_considered = S.considered; rep.last_rms_mm = rms_of(S); K::used(rep, S, false);
+        double D[16];
+        const int rc = K::solve(S, D);
+        if (rc) {
+            // the solve speaks through pcs_last_error(NULL); the loop's caller has a context
+            status = fail(c, rc, "%s: iteration %d: %s", who, k, pcs_last_error(nullptr));
+            rep.stop_reason = PCS_ALIGN_STOP_REFUSED;
+            break;
+        }
+        double N[16];
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) N[4 * a + b] = D[4 * a] * T[b] + D[4 * a + 1] * T[4 + b] + D[4 * a + 2] * T[8 + b] + D[4 * a + 3] * T[12 + b];
+        std::memcpy(T, N, sizeof T);
+        if (may_stop) {
+            // the angle from both the trace and the antisymmetric part: exact for small angles, where acos(trace) is not
+            const double sx = D[9] - D[6], sy = D[2] - D[8], sz = D[4] - D[1];
+            const double angle = std::atan2(0.5 * std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0] + D[5] + D[10] - 1.0));
+            const double trans_mm = 1000.0 * std::sqrt(D[3] * D[3] + D[7] * D[7] + D[11] * D[11]);
+            if (angle <= P.eps_rot_rad && trans_mm <= P.eps_trans_mm) { rep.stop_reason = PCS_ALIGN_STOP_CONVERGED; break; }
+        }
+    }
+    for (int j = 0; j < 16; j++) out[j] = (float)T[j];
+    if (report) *report = rep;
+    return status;
+}
 
 }  // namespace
 
 extern "C" {
+
+int pcs_align_sums_device(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target, int max_dist_mm,
+                          AlignSums* d_sums, uint32_t* d_dist2)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (int rc = check_sums_args(c, "pcs_align_sums_device", d_source, "d_source", n_source, d_target, "d_target", n_target, max_dist_mm,
+                                 d_sums, "d_sums", d_dist2, "d_dist2"))
+        return rc;
+    return sums_device(c, kAlignTerms, d_source, n_source, d_target, n_target, nullptr, max_dist_mm, d_sums, d_dist2);
+}
+
+int pcs_align_sums(pcs_ctx* c, const int16_t* source, int n_source, const int16_t* target, int n_target, int max_dist_mm,
+                   AlignSums* out, uint32_t* dist2)
+try {
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (int rc = check_sums_args(c, "pcs_align_sums", source, "source", n_source, target, "target", n_target, max_dist_mm, out, "out",
+                                 dist2, "dist2"))
+        return rc;
+    return sums_host(c, kAlignTerms, source, n_source, target, n_target, nullptr, max_dist_mm, out, dist2);
+} catch (const std::exception& ex) {
+    return fail(c, PCS_ERR_NOMEM, "pcs_align_sums: host allocation failed (%s)", ex.what());
+}
+
+int pcs_align_solve(const AlignSums* sums, double delta[16], double* rms_mm)
+{
+    if (!sums) return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: sums is NULL");
+    if (!delta) return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: delta is NULL");
+    if (sums->matched < 0 || sums->considered < sums->matched)
+        return fail(nullptr, PCS_ERR_INVALID_ARG, "pcs_align_solve: matched %lld is outside 0..considered %lld", (long long)sums->matched,
+                    (long long)sums->considered);
+    double d[16], rms = 0;
+    if (int rc = solve_sums(*sums, d, &rms)) return rc;
+    std::memcpy(delta, d, sizeof d);
+    if (rms_mm) *rms_mm = rms;
+    return PCS_OK;
+}
+
+int pcs_align_payloads_device(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
+                              const pcs_align_params* params, const float init[16], float out[16], pcs_align_report* report)
+{
+    return align_loop<PointLoop>(c, d_source, n_source, d_target, n_target, params, init, out, report);
+}
 
 int pcs_align_plane_sums_device(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
                                 const int16_t* d_target_normals, int max_dist_mm, PlaneSums* d_sums, uint32_t* d_dist2)
@@ -624,14 +572,7 @@ int pcs_align_plane_sums_device(pcs_ctx* c, const int16_t* d_source, int n_sourc
     if (int rc = check_plane_sums_args(c, "pcs_align_plane_sums_device", d_source, "d_source", n_source, d_target, "d_target", n_target,
                                        d_target_normals, "d_target_normals", max_dist_mm, d_sums, "d_sums", d_dist2, "d_dist2"))
         return rc;
-    DeviceGuard guard(c->device);
-    PlaneWs ws;
-    if (int rc = carve_plane_ws(c, n_source, n_source ? n_target : 0, false, false, false, false, &ws)) return rc;
-    OutlierIndexView view{};
-    bool have = false;
-    if (n_source)          // (an empty source needs no index)
-        if (int rc = build_plane_index(c, d_target, n_target, d_target_normals, max_dist_mm, ws, &view, &have)) return rc;
-    return run_plane_match(c, d_source, n_source, have ? &view : nullptr, max_dist_mm, ws, d_sums, d_dist2);
+    return sums_device(c, kPlaneTerms, d_source, n_source, d_target, n_target, d_target_normals, max_dist_mm, d_sums, d_dist2);
 }
 
 int pcs_align_plane_sums(pcs_ctx* c, const int16_t* source, int n_source, const int16_t* target, int n_target, const int16_t* target_normals,
@@ -641,30 +582,7 @@ try {
     if (int rc = check_plane_sums_args(c, "pcs_align_plane_sums", source, "source", n_source, target, "target", n_target, target_normals,
                                        "target_normals", max_dist_mm, out, "out", dist2, "dist2"))
         return rc;
-    DeviceGuard guard(c->device);
-    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES, nb = (size_t)n_target * PCS_NORMAL_BYTES;
-    // the host forms' payload staging (pcs_align_sums's); the normals are staged in the align workspace
-    int rc;
-    if ((rc = ensure_idle(c, c->s_voxel_in, c->s_voxel_in_cap, sb))) return rc;
-    if ((rc = ensure_idle(c, c->s_voxel_out, c->s_voxel_out_cap, tb))) return rc;
-    PlaneWs ws;
-    if ((rc = carve_plane_ws(c, n_source, n_source ? n_target : 0, false, true, dist2 != nullptr, true, &ws))) return rc;
-    if (sb) HIPCHK(c, hipMemcpyAsync(c->s_voxel_in, source, sb, hipMemcpyHostToDevice, c->stream));
-    if (tb && n_source) {
-        HIPCHK(c, hipMemcpyAsync(c->s_voxel_out, target, tb, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(ws.normals, target_normals, nb, hipMemcpyHostToDevice, c->stream));
-    }
-    OutlierIndexView view{};
-    bool have = false;
-    if (n_source && (rc = build_plane_index(c, c->s_voxel_out, n_target, ws.normals, max_dist_mm, ws, &view, &have))) return rc;
-    if ((rc = run_plane_match(c, c->s_voxel_in, n_source, have ? &view : nullptr, max_dist_mm, ws, ws.sums, dist2 ? ws.dist2 : nullptr)))
-        return rc;
-    PlaneSums got;
-    HIPCHK(c, hipMemcpyAsync(&got, ws.sums, sizeof got, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (dist2 && n_source) HIPCHK(c, hipMemcpy(dist2, ws.dist2, (size_t)n_source * 4, hipMemcpyDeviceToHost));
-    *out = got;
-    return PCS_OK;
+    return sums_host(c, kPlaneTerms, source, n_source, target, n_target, target_normals, max_dist_mm, out, dist2);
 } catch (const std::exception& ex) {
     return fail(c, PCS_ERR_NOMEM, "pcs_align_plane_sums: host allocation failed (%s)", ex.what());
 }
@@ -686,113 +604,7 @@ int pcs_align_plane_solve(const PlaneSums* sums, double delta[16], double* rms_m
 int pcs_align_payloads_plane_device(pcs_ctx* c, const int16_t* d_source, int n_source, const int16_t* d_target, int n_target,
                                     const pcs_align_plane_params* params, const float init[16], float out[16], pcs_align_plane_report* report)
 {
-    static const char who[] = "pcs_align_payloads_plane_device";
-    if (!c) return PCS_ERR_INVALID_ARG;
-    if (!params) return fail(c, PCS_ERR_INVALID_ARG, "%s: params is NULL", who);
-    if (int rc = check_payloads(c, who, d_source, "d_source", n_source, d_target, "d_target", n_target, params->max_dist_mm)) return rc;
-    if (params->iterations < 1 || params->iterations > PCS_ALIGN_ITERATIONS_MAX)
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: iterations %d is outside 1..%d", who, params->iterations, PCS_ALIGN_ITERATIONS_MAX);
-    if (params->source_stride < 1) return fail(c, PCS_ERR_INVALID_ARG, "%s: source_stride %d < 1", who, params->source_stride);
-    if (!(params->eps_rot_rad >= 0) || !std::isfinite(params->eps_rot_rad))
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: eps_rot_rad is negative or not finite", who);
-    if (!(params->eps_trans_mm >= 0) || !std::isfinite(params->eps_trans_mm))
-        return fail(c, PCS_ERR_INVALID_ARG, "%s: eps_trans_mm is negative or not finite", who);
-    if (int rc = check_normal_params(c, who, &params->normals)) return rc;
-    if (!init) return fail(c, PCS_ERR_INVALID_ARG, "%s: init is NULL", who);
-    if (!out) return fail(c, PCS_ERR_INVALID_ARG, "%s: out is NULL", who);
-    for (int k = 0; k < 16; k++)
-        if (!std::isfinite(init[k])) return fail(c, PCS_ERR_INVALID_ARG, "%s: init[%d] is not finite", who, k);
-    int trace_cap = 0;
-    if (report) {
-        if (report->trace_capacity < 0) return fail(c, PCS_ERR_INVALID_ARG, "%s: report->trace_capacity %d < 0", who, report->trace_capacity);
-        trace_cap = report->trace_capacity;
-    }
-    const size_t sb = (size_t)n_source * PCS_POINT_BYTES, tb = (size_t)n_target * PCS_POINT_BYTES;
-    struct { const void* p; size_t n; const char* name; } outs[] = {
-        {out, 16 * sizeof(float), "out"},
-        {report, report ? sizeof *report : 0, "report"},
-        {report ? report->trace_transforms : nullptr, (size_t)trace_cap * 16 * sizeof(float), "report->trace_transforms"},
-        {report ? report->trace_sums : nullptr, (size_t)trace_cap * sizeof(PlaneSums), "report->trace_sums"}};
-    for (size_t i = 0; i < sizeof outs / sizeof outs[0]; i++) {
-        if (ranges_overlap(outs[i].p, outs[i].n, d_source, sb) || ranges_overlap(outs[i].p, outs[i].n, d_target, tb) ||
-            ranges_overlap(outs[i].p, outs[i].n, init, 16 * sizeof(float)) || ranges_overlap(outs[i].p, outs[i].n, params, sizeof *params))
-            return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps an input", who, outs[i].name);
-        for (size_t j = 0; j < i; j++)
-            if (ranges_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n))
-                return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s", who, outs[i].name, outs[j].name);
-    }
-
-    DeviceGuard guard(c->device);
-    const pcs_align_plane_params P = *params;
-    float* const trace_f = report ? report->trace_transforms : nullptr;
-    PlaneSums* const trace_s = report ? report->trace_sums : nullptr;
-    const int n_moved = n_source / P.source_stride;          // FLOOR, pcs_transform_payloads_device's rule
-    PlaneWs ws;
-    if (int rc = carve_plane_ws(c, n_moved, n_moved ? n_target : 0, true, true, false, true, &ws)) return rc;
-    OutlierIndexView view{};
-    bool have = false;
-    if (n_moved && n_target) {                                // once per call: the target's normals, its index, the normals beside it
-        if (int rc = run_normals_device(c, d_target, n_target, P.normals, ws.normals, nullptr)) return rc;
-        if (int rc = build_plane_index(c, d_target, n_target, ws.normals, P.max_dist_mm, ws, &view, &have)) return rc;
-    }
-
-    double T[16];
-    for (int k = 0; k < 16; k++) T[k] = init[k];
-    pcs_align_plane_report rep{};
-    rep.trace_capacity = trace_cap; rep.trace_transforms = trace_f; rep.trace_sums = trace_s;
-    rep.stop_reason = PCS_ALIGN_STOP_ITERATIONS;
-    int status = PCS_OK;
-    const bool may_stop = P.eps_rot_rad > 0 || P.eps_trans_mm > 0;
-    for (int k = 0; k < P.iterations; k++) {
-        float F[16];
-        for (int j = 0; j < 16; j++) F[j] = (float)T[j];
-        if (n_moved) {
-            XformBatch xb;
-            std::memset(&xb, 0, sizeof xb);
-            xb.c[0].in = d_source;
-            xb.c[0].out = reinterpret_cast<uint8_t*>(ws.moved);
-            xb.c[0].n_out = (uint32_t)n_moved;
-            xb.c[0].ds = (uint32_t)P.source_stride;
-            std::memcpy(xb.c[0].M, F, sizeof xb.c[0].M);
-            KernelTimer timer(c);
-            if (timer.rc) return timer.rc;
-            HIPCHK(c, launch_transform_payloads(xb, 1, (uint32_t)n_moved, c->stream));
-            if (int rc = timer.finish()) return rc;
-        }
-        if (int rc = run_plane_match(c, ws.moved, n_moved, have ? &view : nullptr, P.max_dist_mm, ws, ws.sums, nullptr)) return rc;
-        PlaneSums S;
-        HIPCHK(c, hipMemcpyAsync(&S, ws.sums, sizeof S, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (k < trace_cap) {
-            if (trace_f) std::memcpy(trace_f + 16 * (size_t)k, F, sizeof F);
-            if (trace_s) trace_s[k] = S;
-            rep.trace_count = k + 1;
-        }
-        rep.iterations = k + 1;
-        if (k == 0) { rep.first_matched = S.matched; rep.first_used = S.used; rep.first_considered = S.considered; rep.first_rms_mm = rms_of(S); }
-        rep.last_matched = S.matched; rep.last_used = S.used; rep.last_considered = S.considered; rep.last_rms_mm = rms_of(S);
-        double D[16];
-        const int rc = solve_plane_sums(S, D, nullptr);
-        if (rc) {
-            // the solve speaks through pcs_last_error(NULL); the loop's caller has a context
-            status = fail(c, rc, "%s: iteration %d: %s", who, k, pcs_last_error(nullptr));
-            rep.stop_reason = PCS_ALIGN_STOP_REFUSED;
-            break;
-        }
-        double N[16];
-        for (int a = 0; a < 4; a++)
-            for (int b = 0; b < 4; b++) N[4 * a + b] = D[4 * a] * T[b] + D[4 * a + 1] * T[4 + b] + D[4 * a + 2] * T[8 + b] + D[4 * a + 3] * T[12 + b];
-        std::memcpy(T, N, sizeof T);
-        if (may_stop) {
-            const double sx = D[9] - D[6], sy = D[2] - D[8], sz = D[4] - D[1];
-            const double angle = std::atan2(0.5 * std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0] + D[5] + D[10] - 1.0));
-            const double trans_mm = 1000.0 * std::sqrt(D[3] * D[3] + D[7] * D[7] + D[11] * D[11]);
-            if (angle <= P.eps_rot_rad && trans_mm <= P.eps_trans_mm) { rep.stop_reason = PCS_ALIGN_STOP_CONVERGED; break; }
-        }
-    }
-    for (int j = 0; j < 16; j++) out[j] = (float)T[j];
-    if (report) *report = rep;
-    return status;
+    return align_loop<PlaneLoop>(c, d_source, n_source, d_target, n_target, params, init, out, report);
 }
 
 }  // extern "C"

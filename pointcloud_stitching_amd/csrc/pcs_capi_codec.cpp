@@ -2,24 +2,12 @@
 // the host validator (pcs_codec_format.h), the device encode / decode calls over pcs_kernels_codec.hip and the host-pointer decode.
 // pcs_process_frames_compressed lives beside pcs_process_frames in pcs_capi.cpp, whose staging it shares.
 
-#include <climits>
 #include <exception>
 
 #include "pcs_codec_format.h"
 #include "pcs_host.h"
 
 using namespace pcs_host;
-
-namespace {
-
-// [a, a + na) and [b, b + nb) share a byte
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return na && nb && a0 < b0 + nb && b0 < a0 + na;
-}
-
-}  // namespace
 
 extern "C" {
 

@@ -350,22 +350,34 @@ hipError_t launch_codec_encode(const int16_t* d_payload, uint32_t n_points, uint
                                hipStream_t st);
 hipError_t launch_codec_decode(const void* d_in, uint32_t in_bytes, uint32_t n_points, int16_t* d_payload, hipStream_t st);
 
+// 256-byte granularity: how every workspace slab of the payload-cloud family is carved, on the host and in the launchers alike
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
 // Radius outlier removal (pcs_radius_outlier_device, pcs_kernels_outlier.hip): kOutlierStages launches on one stream, each its own
 // call so that the host layer can bracket them one by one (pcs_kernel_timing). `capacity` (n_points, or max_points of the counted
 // form) sizes every grid and the workspace; the record count the kernels use is n_points, or *d_n_points clamped to 0..capacity when
 // that pointer is given — read by stage 0, on the device. d_ws: outlier_workspace_bytes(capacity) bytes, 256-byte aligned. Stage 8
 // is launch_scan over the control block's one-entry table: it writes the kept count to d_out_points[0].
+// The stages are three groups, each with an entry point of its own for the callers that want only that group: 0 to 5 build the cell
+// index (launch_cell_index_stage: no filter parameter), 6 is this filter's flag, 7 to 9 compact by the keep bits
+// (launch_outlier_compact_stage, the filter's numbering). launch_outlier_stage runs any of the ten and forwards the two groups.
 constexpr int kOutlierStages = 10;
+constexpr int kIndexStages   = 6;
 struct OutlierCtl { StreamParams tab; };     // entry 0 of a scan table: n_points = the record count, tile_base = 0
 uint32_t    outlier_slots(uint32_t capacity);
 size_t      outlier_workspace_bytes(uint32_t capacity);
 const char* outlier_stage_name(int stage);
+hipError_t  launch_cell_index_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
+                                    int cell_mm, void* d_ws, size_t ws_bytes, hipStream_t st);
+hipError_t  launch_outlier_compact_stage(int stage, const int16_t* d_in, uint32_t capacity, void* d_ws, size_t ws_bytes, int16_t* d_out,
+                                         int32_t* d_out_points, hipStream_t st);
 hipError_t  launch_outlier_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
                                  int radius_mm, int min_neighbors, void* d_ws, size_t ws_bytes, int16_t* d_out, int32_t* d_out_points,
                                  hipStream_t st);
-// What stages 0 to 5 leave in a workspace, for a reader other than the flag kernel (pcs_kernels_align.hip): cell key of slot s in
-// keys[s] (all ones: empty; probe from first_slot, pcs_outlier_index.h), the cell's members at xyz[start[s] .. start[s + 1])
-// (x | y << 16, z), slots + 1 starts. Same arguments as launch_outlier_stage; nothing is launched.
+// What the kIndexStages launches of launch_cell_index_stage leave in a workspace, for a reader other than the flag kernel
+// (pcs_kernels_align.hip, pcs_kernels_normals.hip, pcs_kernels_stat.hip): cell key of slot s in keys[s] (all ones: empty; probe from
+// first_slot, pcs_outlier_index.h), the cell's members at xyz[start[s] .. start[s + 1]) (x | y << 16, z), slots + 1 starts. Nothing
+// is launched.
 struct OutlierIndexView {
     const unsigned long long* keys;
     const uint32_t*           start;
@@ -373,8 +385,8 @@ struct OutlierIndexView {
     uint32_t                  slots, capacity;
 };
 hipError_t  outlier_index_view(uint32_t capacity, void* d_ws, size_t ws_bytes, OutlierIndexView* view);
-// What stage 0 leaves and stages 7 to 9 read, for a flag kernel other than the radius filter's (pcs_kernels_stat.hip): the control
-// block (the record count) and keep_bits[w] = the keep bits of records 64 w .. 64 w + 63, a bit at or beyond the count 0.
+// What stage 0 leaves and launch_outlier_compact_stage reads, for a flag kernel other than the radius filter's (pcs_kernels_stat.hip):
+// the control block (the record count) and keep_bits[w] = the keep bits of records 64 w .. 64 w + 63, a bit at or beyond the count 0.
 struct OutlierKeepView {
     const OutlierCtl*   ctl;
     unsigned long long* keep_bits;
@@ -382,9 +394,9 @@ struct OutlierKeepView {
 hipError_t  outlier_keep_view(uint32_t capacity, void* d_ws, size_t ws_bytes, OutlierKeepView* view);
 
 // Statistical outlier removal (pcs_stat_outlier_device, pcs_kernels_stat.hip; the definition: DESIGN.md section 3 "Statistical
-// outlier removal"): kStatStages launches on one stream, each its own call as launch_outlier_stage's are. Stages 0 to 5 are that
-// filter's index with cell edge max_dist_mm, 6 to 9 knn, sums, threshold and flag, 10 to 12 that filter's tile count, tile scan and
-// emit, 13 (only with d_stats: eight int64, 8-byte aligned) the statistics block. d_ws: stat_workspace_bytes(capacity) bytes,
+// outlier removal"): kStatStages launches on one stream, each its own call as launch_outlier_stage's are. Stages 0 to 5 are the cell
+// index with cell edge max_dist_mm (launch_cell_index_stage), 6 to 9 knn, sums, threshold and flag, 10 to 12 the radius filter's tile
+// count, tile scan and emit (launch_outlier_compact_stage), 13 (only with d_stats: eight int64, 8-byte aligned) the statistics block. d_ws: stat_workspace_bytes(capacity) bytes,
 // 256-byte aligned; count and capacity as launch_outlier_stage's.
 constexpr int kStatStages = 14;
 size_t      stat_workspace_bytes(uint32_t capacity);
@@ -394,8 +406,8 @@ hipError_t  launch_stat_stage(int stage, const int16_t* d_in, uint32_t n_points,
                               long long* d_stats, hipStream_t st);
 
 // Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
-// index is the outlier filter's, cell edge max_dist_mm (stages 0 to 5 of launch_outlier_stage over the target; `index` is its view,
-// or nullptr for an empty target: nobody matches). launch_align_match: one lane per source record, one 144-byte partial per
+// index is the outlier filter's, cell edge max_dist_mm (launch_cell_index_stage over the target; `index` is its view, or nullptr for
+// an empty target: nobody matches). launch_align_match: one lane per source record, one 144-byte partial per
 // workgroup of kBlockThreads records into d_partials[align_partials(n_source)], dist2 (optional) written here.
 // launch_align_reduce: one workgroup sums the partials and writes *d_sums whole (n_partials 0: a zeroed struct).
 constexpr int kAlignTerms = 18;              // pcs_align_sums as int64 words
@@ -417,8 +429,7 @@ hipError_t launch_align_plane_match(const int16_t* d_source, uint32_t n_source, 
 hipError_t launch_align_plane_reduce(const long long* d_partials, uint32_t n_partials, long long* d_sums, hipStream_t st);
 
 // Surface normals (pcs_estimate_normals_device, pcs_kernels_normals.hip; the definition: DESIGN.md section 3 "Surface normals"). The
-// payload's index is the outlier filter's, cell edge radius_mm (stages 0 to 5 of launch_outlier_stage over the payload; `index` is
-// its view). launch_normals_estimate: one lane per xyz[] entry, its four shorts as one word into d_cell_normals[n_points], parallel
+// payload's index is the outlier filter's, cell edge radius_mm (launch_cell_index_stage over the payload; `index` is its view). launch_normals_estimate: one lane per xyz[] entry, its four shorts as one word into d_cell_normals[n_points], parallel
 // to xyz[] (cell order). launch_normals_gather: one lane per input record copies its word to d_normals[i] (8-byte aligned) and adds
 // the valid records to *d_valid (optional; zeroed by the caller on the same stream). NormalRule: pcs_normals_math.h.
 struct NormalRule;

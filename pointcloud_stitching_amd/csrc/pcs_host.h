@@ -1,10 +1,13 @@
-// pcs_host.h — what the translation units of the C ABI (pcs_capi.cpp: contexts, the a1 / a2 twins, the fused path, host forms, plumbing;
-// pcs_capi_voxel.cpp: the voxel grid, partials, sinks) share: the context itself and the few helpers both sides call. Internal to
-// libpcs_hip.so; nothing here is exported.
+// pcs_host.h — what the translation units of the C ABI share: the context itself and the helpers more than one of them calls.
+// pcs_capi.cpp: contexts, the a1 / a2 twins, the fused path, host forms, plumbing; pcs_capi_voxel.cpp: the voxel grid, partials, sinks;
+// pcs_capi_codec.cpp: the payload codec; and the payload-cloud family over the cell index — pcs_capi_outlier.cpp, pcs_capi_stat.cpp,
+// pcs_capi_normals.cpp, pcs_capi_align.cpp — whose common checks, slab policy, index build and staging live in pcs_capi_cloud.cpp.
+// Internal to libpcs_hip.so; nothing here is exported.
 #ifndef PCS_HOST_H
 #define PCS_HOST_H
 
 #include <algorithm>
+#include <climits>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -132,17 +135,17 @@ struct pcs_ctx {
     uint32_t*                       d_codec_bytes = nullptr; size_t codec_bytes_cap = 0;
 
     // radius outlier removal (pcs_capi_outlier.cpp): the cell index, keep bits and tile words of one call, sized from the call's
-    // n_points / max_points alone (outlier_workspace_bytes), grown on demand the way the voxel workspace is
+    // n_points / max_points alone (outlier_workspace_bytes), grown on demand by ensure_ws as the voxel workspace is
     // (statistical outlier removal, pcs_capi_stat.cpp, asks the same slab for stat_workspace_bytes: the index in front, its own words behind)
     void*                           s_outlier_ws = nullptr; size_t s_outlier_ws_cap = 0;
 
     // alignment sums and the ICP loop (pcs_capi_align.cpp): the target's cell index (the outlier filter's layout), the match
     // launch's per-workgroup partials, the loop's moved source and sums, the host form's sums and dist2 — one slab carved per call,
-    // grown on demand by ensure_outlier_ws's policy
+    // grown on demand by ensure_ws
     void*                           s_align_ws = nullptr; size_t s_align_ws_cap = 0;
 
     // surface normals (pcs_capi_normals.cpp): the payload's cell index (the outlier filter's layout) and the normals in cell order,
-    // 8 bytes per record — one slab carved per call, grown on demand by ensure_outlier_ws's policy
+    // 8 bytes per record — one slab carved per call, grown on demand by ensure_ws
     void*                           s_normals_ws = nullptr; size_t s_normals_ws_cap = 0;
 
     std::string                     err;
@@ -217,7 +220,24 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-// The voxel workspace of a context, at least `need` bytes (grows with a quarter of headroom; growing waits for the stream).
+// A workspace slab of a context, at least `need` bytes. Growing it means: wait for the stream (the old one may be in use), free,
+// allocate — a device-wide stall. A caller whose sizes creep upwards must not pay that at every new maximum: a slab that has to grow
+// takes a quarter more than asked. It never shrinks.
+template <class T>
+int ensure_ws(pcs_ctx* c, T*& p, size_t& cap, size_t need)
+{
+    if (need <= cap && p) return PCS_OK;
+    const size_t exact = need;
+    if (p) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        need += need / 4;
+    }
+    int rc = ensure(c, p, cap, need);
+    if (rc == PCS_ERR_NOMEM && need != exact) rc = ensure(c, p, cap, exact);      // the headroom is a wish
+    return rc;
+}
+
+// The voxel workspace of a context, at least `need` bytes: ensure_ws, and the control block's state forgotten when it moves.
 int ensure_voxel_ws(pcs_ctx* c, size_t need);
 int acquire_event_pair(pcs_ctx* c, std::pair<hipEvent_t, hipEvent_t>& pr);
 
@@ -261,6 +281,58 @@ private:
         return PCS_OK;
     }
 };
+
+// One launch inside one bracket: the four lines every per-launch bracket is. Returns from the calling function on every failure, as
+// HIPCHK does (whose message names the launch as written); the timer's destructor hands the pair back then.
+#define PCS_TIMED(c, launch)                              \
+    do {                                                  \
+        pcs_host::KernelTimer _timer(c);                  \
+        if (_timer.rc) return _timer.rc;                  \
+        HIPCHK((c), launch);                              \
+        if (int _rc = _timer.finish()) return _rc;        \
+    } while (0)
+
+// ---- the payload-cloud family (radius / statistical outlier removal, surface normals, alignment): pcs_capi_cloud.cpp -------------
+constexpr int kMaxPoints = INT_MAX / PCS_POINT_BYTES;      // a payload's byte count fits an int32 (as the PCZ1 container's)
+
+// [a, a + na) and [b, b + nb) share a byte. A NULL pointer is no range: it shares none, whatever length rides beside it.
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// The first output range, in table order, that shares a byte with an input (*with = nullptr) or with an earlier output (*with).
+struct NamedRange { const void* p; size_t n; const char* name; };
+inline const NamedRange* first_overlap(const NamedRange* outs, size_t n_outs, const NamedRange* ins, size_t n_ins, const NamedRange** with)
+{
+    for (size_t i = 0; i < n_outs; i++) {
+        *with = nullptr;
+        for (size_t k = 0; k < n_ins; k++)
+            if (ranges_overlap(outs[i].p, outs[i].n, ins[k].p, ins[k].n)) return &outs[i];
+        for (size_t j = 0; j < i; j++)
+            if (ranges_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) { *with = &outs[j]; return &outs[i]; }
+    }
+    return nullptr;
+}
+
+// What a filter of packed records checks about its payloads once its own parameters passed: the count's range, NULLs, 2-byte
+// alignment, the count word's alignment, out_shorts against the worst case, and that nothing overlaps. `who` names the entry point,
+// the *_name its own argument names; stats (optional, 8-byte aligned, stats_bytes long) may be NULL.
+int check_payload_io(pcs_ctx* c, const char* who, const void* in, const char* in_name, int n_points, const char* n_name, const void* out,
+                     const char* out_name, size_t out_shorts, const void* out_points, const char* points_name, unsigned points_align,
+                     const void* stats = nullptr, const char* stats_name = nullptr, size_t stats_bytes = 0);
+
+// The kIndexStages launches of the cell index over n > 0 records, cell edge cell_mm, one timing bracket each; its view into *view.
+int build_cell_index(pcs_ctx* c, const int16_t* d_payload, int n, int cell_mm, void* index, size_t index_bytes, OutlierIndexView* view);
+
+// The host forms' payload staging (pcs_voxel_grid's: every such call is synchronous, none leaves anything in it): s_voxel_in sized and
+// filled with in_bytes of `in` on the stream, s_voxel_out sized for out_bytes.
+int stage_payload(pcs_ctx* c, const void* in, size_t in_bytes, size_t out_bytes);
+// bytes from the device once the stream has run dry / the count word the kernels left in d_counts[0], refused outside 0..n_points
+// ("the kernels reported %d of %d records <what>").
+int fetch(pcs_ctx* c, void* dst, const void* d_src, size_t bytes);
+int fetch_count(pcs_ctx* c, const char* who, int n_points, const char* what, int32_t* count);
 
 // What the streams [s0, s0 + nl) of one launch have in common: the AND of their certificates, the OR of their distortions, the largest
 // raster. Every launch site of the fused path takes its arithmetic from this one fold (launch_math) and states its own reduction.

@@ -333,8 +333,6 @@ void pcs_outlier_emit_kernel(const int16_t* __restrict__ in, const OutlierCtl* _
     store_staged(stage, head, tile_kept * PCS_POINT_BYTES, gdst);
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 uint32_t outlier_slots(uint32_t capacity)
@@ -352,7 +350,7 @@ size_t outlier_workspace_bytes(uint32_t capacity)
 
 namespace {
 
-// Where the pieces of a workspace lie: the one carve launch_outlier_stage and outlier_index_view both read.
+// Where the pieces of a workspace lie: the one carve the stage launchers and the two views read.
 struct OutlierCarve {
     uint32_t            slots, tiles;
     OutlierCtl*         ctl;
@@ -392,57 +390,84 @@ const char* outlier_stage_name(int stage)
     return stage >= 0 && stage < kOutlierStages ? names[stage] : "?";
 }
 
-hipError_t launch_outlier_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
-                                int radius_mm, int min_neighbors, void* d_ws, size_t ws_bytes, int16_t* d_out, int32_t* d_out_points,
-                                hipStream_t st)
+namespace {
+
+// What every stage launcher refuses: no capacity, a workspace too small or off the slab's 256-byte granularity.
+bool bad_workspace(uint32_t capacity, const void* d_ws, size_t ws_bytes)
 {
-    if (!capacity || radius_mm < 1 || radius_mm > 1000 || min_neighbors < 1 || min_neighbors > 255 || ws_bytes < outlier_workspace_bytes(capacity) ||
-        ((uintptr_t)d_ws & 255u) || (!d_n_points && n_points > capacity))
+    return !capacity || ws_bytes < outlier_workspace_bytes(capacity) || ((uintptr_t)d_ws & 255u);
+}
+
+}  // namespace
+
+hipError_t launch_cell_index_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
+                                   int cell_mm, void* d_ws, size_t ws_bytes, hipStream_t st)
+{
+    if (bad_workspace(capacity, d_ws, ws_bytes) || cell_mm < 1 || cell_mm > 1000 || (!d_n_points && n_points > capacity))
         return hipErrorInvalidValue;
     const OutlierCarve cv(capacity, d_ws);
-    const uint32_t slots = cv.slots, tiles = cv.tiles;
-    OutlierCtl* const ctl = cv.ctl;
-    unsigned long long* const keys = cv.keys, * const keep_bits = cv.keep_bits;
-    uint32_t* const count = cv.count, * const sums = cv.sums, * const slot_of = cv.slot_of, * const rank = cv.rank,
-            * const tile_counts = cv.tile_counts, * const tile_prefix = cv.tile_prefix;
-    uint2* const xyz = cv.xyz;
-    const dim3 per_record((capacity + kBlockThreads - 1) / kBlockThreads), per_slot_tile(slots / kTilePoints), block(kBlockThreads);
+    const dim3 per_record((capacity + kBlockThreads - 1) / kBlockThreads), per_slot_tile(cv.slots / kTilePoints), block(kBlockThreads);
     switch (stage) {
     case 0:
-        hipLaunchKernelGGL(pcs_outlier_clear_kernel, dim3(slots / kBlockThreads + 1), block, 0, st, ctl, d_n_points, n_points, capacity, keys,
-                           count, slots);
+        hipLaunchKernelGGL(pcs_outlier_clear_kernel, dim3(cv.slots / kBlockThreads + 1), block, 0, st, cv.ctl, d_n_points, n_points, capacity,
+                           cv.keys, cv.count, cv.slots);
         break;
     case 1:
-        hipLaunchKernelGGL(pcs_outlier_insert_kernel, per_record, block, 0, st, d_in, ctl, radius_mm, keys, count, slots, slot_of, rank);
+        hipLaunchKernelGGL(pcs_outlier_insert_kernel, per_record, block, 0, st, d_in, cv.ctl, cell_mm, cv.keys, cv.count, cv.slots, cv.slot_of,
+                           cv.rank);
         break;
     case 2:
-        hipLaunchKernelGGL(pcs_outlier_cell_sums_kernel, per_slot_tile, block, 0, st, count, sums);
+        hipLaunchKernelGGL(pcs_outlier_cell_sums_kernel, per_slot_tile, block, 0, st, cv.count, cv.sums);
         break;
     case 3:
-        hipLaunchKernelGGL(pcs_outlier_cell_scan_kernel, dim3(1), dim3(1024), 0, st, sums, slots / kTilePoints, count + slots);
+        hipLaunchKernelGGL(pcs_outlier_cell_scan_kernel, dim3(1), dim3(1024), 0, st, cv.sums, cv.slots / kTilePoints, cv.count + cv.slots);
         break;
     case 4:
-        hipLaunchKernelGGL(pcs_outlier_cell_starts_kernel, per_slot_tile, block, 0, st, count, sums);
+        hipLaunchKernelGGL(pcs_outlier_cell_starts_kernel, per_slot_tile, block, 0, st, cv.count, cv.sums);
         break;
     case 5:
-        hipLaunchKernelGGL(pcs_outlier_scatter_kernel, per_record, block, 0, st, d_in, ctl, count, slot_of, rank, capacity, xyz);
-        break;
-    case 6:
-        hipLaunchKernelGGL(pcs_outlier_flag_kernel, per_record, block, 0, st, d_in, ctl, radius_mm, (uint32_t)min_neighbors + 1u, keys, count,
-                           slots, xyz, capacity, keep_bits);
-        break;
-    case 7:
-        hipLaunchKernelGGL(pcs_outlier_count_kernel, dim3(tiles), dim3(64), 0, st, ctl, keep_bits, tile_counts);
-        break;
-    case 8:     // the kept count is the scan's per-stream count: d_out_points[0], nothing behind it
-        return launch_scan(&ctl->tab, 1, 1, tile_counts, tile_prefix, nullptr, d_out_points, nullptr, st);
-    case 9:
-        hipLaunchKernelGGL(pcs_outlier_emit_kernel, dim3(tiles), block, 0, st, d_in, ctl, reinterpret_cast<const uint8_t*>(keep_bits),
-                           tile_prefix, reinterpret_cast<uint8_t*>(d_out));
+        hipLaunchKernelGGL(pcs_outlier_scatter_kernel, per_record, block, 0, st, d_in, cv.ctl, cv.count, cv.slot_of, cv.rank, capacity, cv.xyz);
         break;
     default:
         return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_outlier_compact_stage(int stage, const int16_t* d_in, uint32_t capacity, void* d_ws, size_t ws_bytes, int16_t* d_out,
+                                        int32_t* d_out_points, hipStream_t st)
+{
+    if (bad_workspace(capacity, d_ws, ws_bytes)) return hipErrorInvalidValue;
+    const OutlierCarve cv(capacity, d_ws);
+    switch (stage) {
+    case 7:
+        hipLaunchKernelGGL(pcs_outlier_count_kernel, dim3(cv.tiles), dim3(64), 0, st, cv.ctl, cv.keep_bits, cv.tile_counts);
+        break;
+    case 8:     // the kept count is the scan's per-stream count: d_out_points[0], nothing behind it
+        return launch_scan(&cv.ctl->tab, 1, 1, cv.tile_counts, cv.tile_prefix, nullptr, d_out_points, nullptr, st);
+    case 9:
+        hipLaunchKernelGGL(pcs_outlier_emit_kernel, dim3(cv.tiles), dim3(kBlockThreads), 0, st, d_in, cv.ctl,
+                           reinterpret_cast<const uint8_t*>(cv.keep_bits), cv.tile_prefix, reinterpret_cast<uint8_t*>(d_out));
+        break;
+    default:
+        return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_outlier_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
+                                int radius_mm, int min_neighbors, void* d_ws, size_t ws_bytes, int16_t* d_out, int32_t* d_out_points,
+                                hipStream_t st)
+{
+    if (bad_workspace(capacity, d_ws, ws_bytes) || radius_mm < 1 || radius_mm > 1000 || min_neighbors < 1 || min_neighbors > 255 ||
+        (!d_n_points && n_points > capacity))
+        return hipErrorInvalidValue;
+    if (stage >= 0 && stage < kIndexStages)
+        return launch_cell_index_stage(stage, d_in, n_points, d_n_points, capacity, radius_mm, d_ws, ws_bytes, st);
+    if (stage != 6) return launch_outlier_compact_stage(stage, d_in, capacity, d_ws, ws_bytes, d_out, d_out_points, st);
+    const OutlierCarve cv(capacity, d_ws);
+    hipLaunchKernelGGL(pcs_outlier_flag_kernel, dim3((capacity + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads), 0, st, d_in, cv.ctl,
+                       radius_mm, (uint32_t)min_neighbors + 1u, cv.keys, cv.count, cv.slots, cv.xyz, capacity, cv.keep_bits);
     return hipGetLastError();
 }
 

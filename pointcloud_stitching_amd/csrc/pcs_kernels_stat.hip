@@ -4,7 +4,7 @@
 // mean + std_mul x deviation of the D of the non-sparse records, everything in integers. Not in the reference; modelled on PCL's
 // StatisticalOutlierRemoval, parity unpinned.
 //
-// The neighbour search walks the radius filter's index (stages 0 to 5 of launch_outlier_stage with cell edge max_dist_mm,
+// The neighbour search walks the radius filter's index (launch_cell_index_stage's six launches with cell edge max_dist_mm,
 // pcs_outlier_index.h); the keep bits go where that filter's flag kernel puts them, so its stages 7 to 9 (tile count, scan, emit) run
 // unchanged behind these launches:
 //   knn        one lane per record, in record order: the own cell first, then the 26 others; keeps the mean_k + 1 smallest d^2 <=
@@ -278,7 +278,6 @@ void pcs_stat_finish_kernel(const long long* __restrict__ block, const int32_t* 
     if (threadIdx.x < 8) stats[threadIdx.x] = threadIdx.x == 6 ? (long long)*kept : block[threadIdx.x];
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline uint32_t stat_partials(uint32_t capacity) { return (capacity + kBlockThreads - 1) / kBlockThreads; }
 
 }  // namespace
@@ -303,11 +302,11 @@ hipError_t launch_stat_stage(int stage, const int16_t* d_in, uint32_t n_points, 
         max_dist_mm < PCS_STAT_DIST_MIN || max_dist_mm > PCS_STAT_DIST_MAX || ws_bytes < stat_workspace_bytes(capacity) ||
         ((uintptr_t)d_ws & 255u) || (!d_n_points && n_points > capacity))
         return hipErrorInvalidValue;
-    // the radius filter's stages over the front of the workspace: the index (0 to 5) and the compaction (its 7 to 9)
+    // over the front of the workspace: the cell index (0 to 5) and the radius filter's compaction (its 7 to 9)
     const size_t index_bytes = up256(outlier_workspace_bytes(capacity));
-    if (stage < 6 || (stage >= 10 && stage <= 12))
-        return launch_outlier_stage(stage < 6 ? stage : stage - 3, d_in, n_points, d_n_points, capacity, max_dist_mm, 1, d_ws, index_bytes, d_out,
-                                    d_out_points, st);
+    if (stage >= 0 && stage < kIndexStages)
+        return launch_cell_index_stage(stage, d_in, n_points, d_n_points, capacity, max_dist_mm, d_ws, index_bytes, st);
+    if (stage >= 10 && stage <= 12) return launch_outlier_compact_stage(stage - 3, d_in, capacity, d_ws, index_bytes, d_out, d_out_points, st);
     OutlierIndexView view{};
     OutlierKeepView kv{};
     if (hipError_t e = outlier_index_view(capacity, d_ws, index_bytes, &view)) return e;

@@ -1,6 +1,7 @@
 // pcs_outlier_index.h — the uniform-grid neighbour index's device-side vocabulary: what a kernel needs to find a cell's run in the
-// index that stages 0 to 5 of launch_outlier_stage build (pcs_kernels_outlier.hip has the build and its description). Included by
-// pcs_kernels_outlier.hip (radius outlier removal) and pcs_kernels_align.hip (alignment sums), never compiled alone.
+// index that the kIndexStages launches of launch_cell_index_stage build (pcs_kernels_outlier.hip has the build and its description).
+// Included by pcs_kernels_outlier.hip (radius outlier removal), pcs_kernels_stat.hip (statistical outlier removal),
+// pcs_kernels_align.hip (alignment sums) and pcs_kernels_normals.hip (surface normals), never compiled alone.
 #pragma once
 
 #include "pcs_kernels_common.h"
