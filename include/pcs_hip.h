@@ -760,6 +760,69 @@ int pcs_stat_outlier_device_counted(pcs_ctx* ctx, const int16_t* d_payload, cons
 int pcs_stat_outlier(pcs_ctx* ctx, const int16_t* payload, int n_points, const pcs_stat_outlier_params* params,
                      int16_t* out, size_t out_shorts, int* out_points, struct pcs_stat_outlier_stats* stats);   /* host pointers, staged, synchronous */
 
+/* ---- Euclidean cluster extraction and size filter on a packed payload (not in the reference) ------------------------------------ *
+ * Both outlier filters judge a record by its own neighbourhood; a DENSE blob of stray records passes both. This one finds the
+ * connected components and judges them by their size. n records of 5 shorts (0..2 = x, y, z as signed int16 millimetres; colour is
+ * not read), tolerance_mm 1..1000 (the cell edge of the index). Everything is integer; no float anywhere.
+ *   i ~ j     iff (xi-xj)^2 + (yi-yj)^2 + (zi-zj)^2 <= tolerance_mm^2, in integers of 32 bits or more from the sign-extended shorts
+ *               (nothing wraps at 16 bits). A record with another's coordinates is adjacent to it at distance 0.
+ *   CLUSTER   a connected component of ~. size(i) = the number of records in i's cluster (duplicates count one each).
+ *   label(i)  the smallest input index in i's cluster: label(i) <= i, a cluster's first record labels itself;
+ *               n_clusters = |{ i : label(i) == i }|.
+ *   KEPT      record i iff min_size <= size(i) and (max_size == 0 or size(i) <= max_size). min_size 1..INT_MAX; max_size 0 (no upper
+ *               bound) or >= min_size.
+ * The filter's output is the kept records in input order, all 10 bytes of each unchanged, their count, and (optional) the statistics
+ * block of eight int64: considered, clusters, kept_clusters, largest (the largest cluster's size), kept, reserved (0, 0, 0). Exact and
+ * deterministic: the same bytes on every run, whatever order the atomics arrive in; a function of the payload as a multiset except
+ * for the output's own order (and the labels' renaming under a permutation). tests/np_clusters.py restates it as brute force.
+ * Modelled on PCL's EuclideanClusterExtraction; parity with PCL is unpinned. DESIGN.md section 3 has the definition and what follows
+ * from it: the filter knows nothing of invalid depth (a dense payload's zero-depth pixels form one huge cluster on their camera's
+ * origin: run it behind PCS_FLAG_DROP_INVALID or a crop box).
+ * pcs_cluster_filter_device: asynchronous on the context's stream, no host round trip: the radius filter's cell index with edge
+ *   tolerance_mm (six launches), init, union (a lock-free union-find over the index's entries: one lane per entry unites it with
+ *   every entry below it within the tolerance), roots (every entry's final root, the sizes), flag (the keep bits), then that
+ *   filter's ordered compaction (three launches) and, with d_stats, the block: 14 launches, 13 without. d_out needs room for the
+ *   worst case: out_shorts >= 5 n_points is checked up front; nothing outside the first 10 * kept bytes of d_out is written.
+ *   *d_out_points (device, 4-byte aligned, required) receives kept; d_stats (device, 8-byte aligned, optional) the block. n_points 0
+ *   launches nothing and writes a zero count and a zeroed block.
+ * pcs_cluster_filter_device_counted: the count is read from *d_n_points (device, 4-byte aligned) when the kernels run, clamped to
+ *   0..max_points; max_points sizes the workspace, the grids and the output check. It takes the other filters' output and count,
+ *   and its own feed pcs_voxel_grid_device_counted.
+ * pcs_cluster_filter: host pointers, staged through the context, synchronous; stats optional.
+ * pcs_cluster_labels_device: labels instead of a filtered payload: d_labels (device, 4-byte aligned, n_points int32, required with
+ *   n_points > 0) receives label(i), d_sizes (the same shape, optional) size(i), *d_n_clusters (device, 4-byte aligned, required)
+ *   n_clusters; nothing at or beyond word n_points of either array is written. 11 launches. n_points 0 launches nothing and writes
+ *   zero clusters. pcs_cluster_labels: the host form, synchronous.
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the function and the argument), nothing launched, nothing written: a
+ *   parameter out of range, reserved != 0, max_size in 1..min_size-1, NULL params, a negative count, a NULL pointer (payload and
+ *   outputs may be NULL with a count of 0), an odd payload or output address, a misaligned count, stats, labels or sizes address,
+ *   out_shorts below the worst case, any overlap among the input and output ranges.
+ * Works on every context: flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH are not read. The workspace (the radius filter's
+ *   40.2 bytes per record of n_points / max_points plus 12: csrc/pcs_kernels_cluster.hip) lives in the context and grows on demand.
+ *   Cost: a record costs the population of the cells around it that it cannot rule out and two root searches per adjacent record;
+ *   there is no early exit: a cell of m records costs m^2 / 2 distance tests by definition (n identical records: n^2 / 2). With
+ *   pcs_kernel_timing enabled a call yields one interval per launch. Measured: DESIGN.md section 10 (f13),
+ *   profiles/cluster_probe.txt.                                                                                                    */
+#define PCS_CLUSTER_TOLERANCE_MIN  1
+#define PCS_CLUSTER_TOLERANCE_MAX  1000
+typedef struct pcs_cluster_params {
+    int32_t tolerance_mm, min_size, max_size, reserved;   /* max_size 0: no upper bound; reserved is 0 */
+} pcs_cluster_params;
+struct pcs_cluster_stats {
+    int64_t considered, clusters, kept_clusters, largest, kept, reserved[3];
+};
+int pcs_cluster_filter_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const pcs_cluster_params* params,
+                              int16_t* d_out, size_t out_shorts, int32_t* d_out_points, struct pcs_cluster_stats* d_stats);
+int pcs_cluster_filter_device_counted(pcs_ctx* ctx, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                      const pcs_cluster_params* params, int16_t* d_out, size_t out_shorts,
+                                      int32_t* d_out_points, struct pcs_cluster_stats* d_stats);
+int pcs_cluster_filter(pcs_ctx* ctx, const int16_t* payload, int n_points, const pcs_cluster_params* params,
+                       int16_t* out, size_t out_shorts, int* out_points, struct pcs_cluster_stats* stats);   /* host pointers, staged, synchronous */
+int pcs_cluster_labels_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, int tolerance_mm, int32_t* d_labels,
+                              int32_t* d_sizes, int32_t* d_n_clusters);
+int pcs_cluster_labels(pcs_ctx* ctx, const int16_t* payload, int n_points, int tolerance_mm, int32_t* labels, int32_t* sizes,
+                       int* n_clusters);   /* host pointers, staged, synchronous */
+
 /* ---- extrinsics refinement: nearest-neighbour alignment sums, the rigid fit, the ICP loop (not in the reference) ---------------- *
  * transform[i] comes from four surveyed markers (calibration.py); these calls refine it from the data: move one camera's payload
  * onto another's where they overlap. DESIGN.md section 3 "Alignment sums" has the definition and what follows from it.

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -631,6 +631,54 @@ class PcsContext:
         self._check(self._lib.pcs_stat_outlier_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
                                                               C.byref(params) if params is not None else None, d_out or None, out_shorts,
                                                               d_out_points or None, d_stats or None))
+
+    # -- Euclidean clusters (defined by this build; see include/pcs_hip.h) --------------------------
+    def cluster_filter(self, payload: np.ndarray, tolerance_mm: int, min_size: int, max_size: int = 0):
+        """Packed records (int16 [n,5]) -> (the records of the clusters — connected components of "within tolerance_mm of each
+        other" — that hold min_size..max_size records (max_size 0: no upper bound), input order; the statistics block as a dict)
+        (pcs_cluster_filter: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        out = np.zeros((max(p.shape[0], 1), POINT_SHORTS), np.int16)
+        cnt = C.c_int(0)
+        stats = ClusterStatsC()
+        params = ClusterParams.make(tolerance_mm, min_size, max_size)
+        self._check(self._lib.pcs_cluster_filter(self._h, _ptr(p), p.shape[0], C.byref(params), _ptr(out), p.shape[0] * POINT_SHORTS,
+                                                 C.byref(cnt), C.byref(stats)))
+        return out[:cnt.value].copy(), stats.as_dict()
+
+    def cluster_filter_device(self, d_payload: int, n_points: int, params: ClusterParams, d_out: int, out_shorts: int,
+                              d_out_points: int, d_stats: int = 0) -> None:
+        """Asynchronous; device pointers as ints; *d_out_points (int32, required) receives the kept count, d_stats (eight int64,
+        optional) the statistics block. params may be None (refused). See pcs_cluster_filter_device."""
+        self._check(self._lib.pcs_cluster_filter_device(self._h, d_payload or None, int(n_points), C.byref(params) if params is not None else None,
+                                                        d_out or None, out_shorts, d_out_points or None, d_stats or None))
+
+    def cluster_filter_device_counted(self, d_payload: int, d_n_points: int, max_points: int, params: ClusterParams, d_out: int,
+                                      out_shorts: int, d_out_points: int, d_stats: int = 0) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run. See
+        pcs_cluster_filter_device_counted."""
+        self._check(self._lib.pcs_cluster_filter_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
+                                                                C.byref(params) if params is not None else None, d_out or None, out_shorts,
+                                                                d_out_points or None, d_stats or None))
+
+    def cluster_labels(self, payload: np.ndarray, tolerance_mm: int):
+        """Packed records (int16 [n,5]) -> (labels int32 [n]: the smallest input index in every record's cluster; sizes int32 [n]:
+        its cluster's record count; the number of clusters) (pcs_cluster_labels: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        n = p.shape[0]
+        labels = np.zeros(max(n, 1), np.int32)
+        sizes = np.zeros(max(n, 1), np.int32)
+        cnt = C.c_int(-1)
+        self._check(self._lib.pcs_cluster_labels(self._h, _ptr(p) if n else None, n, int(tolerance_mm), _ptr(labels), _ptr(sizes),
+                                                 C.byref(cnt)))
+        return labels[:n].copy(), sizes[:n].copy(), int(cnt.value)
+
+    def cluster_labels_device(self, d_payload: int, n_points: int, tolerance_mm: int, d_labels: int, d_sizes: int,
+                              d_n_clusters: int) -> None:
+        """Asynchronous; device pointers as ints; d_labels receives n_points int32, d_sizes (optional, 0 for none) the same shape,
+        *d_n_clusters (int32, required) the number of clusters. See pcs_cluster_labels_device."""
+        self._check(self._lib.pcs_cluster_labels_device(self._h, d_payload or None, int(n_points), int(tolerance_mm), d_labels or None,
+                                                        d_sizes or None, d_n_clusters or None))
 
     # -- surface normals (defined by this build; see include/pcs_hip.h) -----------------------------
     def estimate_normals(self, payload: np.ndarray, radius_mm: int, min_neighbors: int, flatness: int = 0, viewpoint_mm=None,

@@ -54,6 +54,14 @@
 //                      pcs_voxel_grid_device_counted. -t prints `Statistical outlier removal: <in> -> <kept> points (dense <M>,
 //                      threshold <T>/256 per k)` per frame-set. Not with -G: the node library has no such filter. Zero-depth pixels
 //                      sit on one point and drag the mean down: with -i give -Z (or -B).
+//              -E <tolerance_mm,min_size[,max_size]>  Euclidean cluster filter on the stitched cloud (pcs_cluster_filter_device: records
+//                      within tolerance_mm of each other are connected; a record stays iff its connected component holds min_size to
+//                      max_size records, max_size 0 or absent: no upper bound): after -T, -B / -d, -O and -K, before -V. It takes
+//                      the stage in front of it through the counted form wherever that stage left a device count (-O, -K, and
+//                      every -i payload); with -V its output and device count feed pcs_voxel_grid_device_counted. -t prints
+//                      `Cluster filter: <in> -> <kept> points (<clusters> clusters, <kept_clusters> kept, largest <largest>)` per
+//                      frame-set. Not with -G: the node library has no such filter. Zero-depth pixels form one huge cluster on
+//                      their camera's origin: with -i give -Z (or -B).
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
@@ -68,6 +76,7 @@
 #include <getopt.h>
 #include <signal.h>
 
+#include "pcs_cluster.h"
 #include "pcs_cropbox.h"
 #include "pcs_outlier.h"
 #include "pcs_statoutlier.h"
@@ -93,6 +102,8 @@ static bool outlier = false;
 static int outlier_radius = 0, outlier_neighbors = 0;
 static bool statout = false;
 static pcs_stat_outlier_params statout_params{};
+static bool cluster = false;
+static pcs_cluster_params cluster_params{};
 
 static void usage()
 {
@@ -118,6 +129,7 @@ static void usage()
               << " -K <mean_k,std_mul_milli,max_dist_mm>  statistical outlier removal on the stitched cloud: a record stays iff it has mean_k\n"
               << "                  others within max_dist_mm (1..64, 1..1000) and its summed distance to the nearest mean_k is at most the\n"
               << "                  cloud's mean + std_mul_milli / 1000 (0..10000) deviations; after -T, -B / -d and -O, before -V; not with -G\n"
+              << pcs_cluster::help()
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
@@ -128,7 +140,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -175,6 +187,12 @@ int main(int argc, char** argv)
                 statout = true;
                 break;
             }
+            case 'E': {
+                std::string why;
+                if (!pcs_cluster::parse(optarg, cluster_params, why)) { std::cerr << "-E " << optarg << ": " << why << std::endl; return 2; }
+                cluster = true;
+                break;
+            }
             case 's': case 'v': case 'n':
                 std::cerr << "-" << (char)c << " drives the reference's PCL viewer / PLY writer, which this build does not include" << std::endl;
                 return 2;
@@ -185,6 +203,7 @@ int main(int argc, char** argv)
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
     if (outlier && n_gpus > 0) { std::cerr << "-O is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
     if (statout && n_gpus > 0) { std::cerr << "-K is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
+    if (cluster && n_gpus > 0) { std::cerr << "-E is not available with -G: the node library has no cluster filter" << std::endl; return 2; }
     if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
     if (!source && !cameras) source = "synth:1280x720";      // no live cameras on this node: the synthetic generator
@@ -324,7 +343,7 @@ int main(int argc, char** argv)
     }
     // -B with -i -V: the cropped payload and its counts stay on the device between the two calls
     void *d_pay = nullptr, *d_pay_counts = nullptr;
-    if (source && ((crop && voxel_leaf) || outlier || statout)) {
+    if (source && ((crop && voxel_leaf) || outlier || statout || cluster)) {
         if (pcs_device_malloc(ctx, &d_pay, pcs_max_payload_shorts(ctx) * sizeof(int16_t) + 64) != PCS_OK ||
             pcs_device_malloc(ctx, &d_pay_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
@@ -356,6 +375,24 @@ int main(int argc, char** argv)
         return true;
     };
 
+    // -E: the same
+    void *d_clu = nullptr, *d_nclu = nullptr, *d_clu_block = nullptr;
+    if (cluster) {
+        const size_t bytes = source ? pcs_max_payload_shorts(ctx) * sizeof(int16_t) : (size_t)n_streams * cam_cap_bytes;
+        if (pcs_device_malloc(ctx, &d_clu, bytes + 64) != PCS_OK || pcs_device_malloc(ctx, &d_nclu, 64) != PCS_OK ||
+            pcs_device_malloc(ctx, &d_clu_block, sizeof(pcs_cluster_stats)) != PCS_OK) {
+            std::cerr << pcs_last_error(ctx) << std::endl; return 1;
+        }
+    }
+    // what -t prints for -E: the block's numbers, after the frame-set's last launch
+    auto print_cluster = [&]() {
+        pcs_cluster_stats st{};
+        if (pcs_memcpy_d2h(ctx, &st, d_clu_block, sizeof st) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
+        std::cout << "Cluster filter: " << st.considered << " -> " << st.kept << " points (" << st.clusters << " clusters, " << st.kept_clusters
+                  << " kept, largest " << st.largest << ")" << std::endl;
+        return true;
+    };
+
     // -V: device-resident rasters (with -i) and the voxel cloud
     std::vector<void*> d_depth, d_color;
     void *d_vox = nullptr, *d_nvox = nullptr;
@@ -370,7 +407,7 @@ int main(int argc, char** argv)
                       pcs_device_malloc(ctx, &d_nvox, 64) != PCS_OK)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
         if (!stitched.resize(PCS_HEADER_SHORTS + vox_cap_points * PCS_POINT_SHORTS)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
-    if ((voxel_leaf || outlier || statout) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
+    if ((voxel_leaf || outlier || statout || cluster) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
         d_depth.resize(n_streams, nullptr); d_color.resize(n_streams, nullptr);
         for (int s = 0; s < n_streams; s++) {
             const size_t db = (size_t)cfgs[s].depth.width * cfgs[s].depth.height * 2;
@@ -548,7 +585,7 @@ int main(int argc, char** argv)
                     std::cout << "Voxel grid over " << n_gpus << " GPU(s): kernels " << vstats.kernels_ms << " ms, exchange " << vstats.exchange_ms
                               << " ms (" << vstats.exchanged_bytes << " B), root " << vstats.root_voxel_ms << " ms, " << vstats.partials
                               << (voxel_route == PCS_NODE_VOXEL_PARTIALS ? " partials -> " : " points -> ") << vstats.voxels << " voxels" << std::endl;
-            } else if (outlier || statout) {
+            } else if (outlier || statout || cluster) {
                 // the payload on the device (under -Z / -B / -d as ever), the filter on its device count, then the voxel grid on the
                 // filter's device count or the kept records out: no count leaves the device in between
                 for (int s = 0; s < n_streams; s++) {
@@ -574,6 +611,11 @@ int main(int argc, char** argv)
                                                          static_cast<int32_t*>(d_nstat), static_cast<pcs_stat_outlier_stats*>(d_stat_block));
                     d_last = static_cast<const int16_t*>(d_stat); d_nlast = static_cast<const int32_t*>(d_nstat);
                 }
+                if (rc == PCS_OK && cluster) {
+                    rc = pcs_cluster_filter_device_counted(ctx, d_last, d_nlast, max_points, &cluster_params, static_cast<int16_t*>(d_clu), max_shorts,
+                                                           static_cast<int32_t*>(d_nclu), static_cast<pcs_cluster_stats*>(d_clu_block));
+                    d_last = static_cast<const int16_t*>(d_clu); d_nlast = static_cast<const int32_t*>(d_nclu);
+                }
                 if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
                 if (voxel_leaf) {
                     auto run_voxel = [&]() {
@@ -597,6 +639,7 @@ int main(int argc, char** argv)
                 }
                 if (timer && outlier) std::cout << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl;
                 if (timer && statout && !print_statout()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                if (timer && cluster && !print_cluster()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
             } else if (voxel_leaf) {
                 for (int s = 0; s < n_streams; s++) {
                     if (pcs_memcpy_h2d(ctx, d_depth[s], depth[s].data(), depth[s].size() * 2) != PCS_OK ||
@@ -715,8 +758,31 @@ int main(int argc, char** argv)
                 }
                 if (timer && !print_statout()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
             }
+            if (cluster) {
+                // behind -O or -K: that filter's output and device count, through the counted form; else the stitched payload and
+                // its host count
+                const size_t out_shorts = (size_t)n_streams * cam_cap_bytes / 2;
+                const int32_t* d_nprev = static_cast<const int32_t*>(statout ? d_nstat : outlier ? d_nfiltered : nullptr);
+                rc = d_nprev ? pcs_cluster_filter_device_counted(ctx, d_result, d_nprev, outlier_in, &cluster_params, static_cast<int16_t*>(d_clu),
+                                                                 out_shorts, static_cast<int32_t*>(d_nclu), static_cast<pcs_cluster_stats*>(d_clu_block))
+                             : pcs_cluster_filter_device(ctx, d_result, total_pts, &cluster_params, static_cast<int16_t*>(d_clu), out_shorts,
+                                                         static_cast<int32_t*>(d_nclu), static_cast<pcs_cluster_stats*>(d_clu_block));
+                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                d_result = static_cast<const int16_t*>(d_clu);
+                if (!voxel_leaf) {      // (with -V the voxel grid reads the count where it is)
+                    int32_t kept = 0;
+                    if (pcs_memcpy_d2h(ctx, &kept, d_nclu, sizeof kept) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) {
+                        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
+                    }
+                    total_pts = kept;
+                }
+                if (timer && !print_cluster()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+            }
             if (voxel_leaf) {
                 auto run_voxel = [&]() {
+                    if (cluster)
+                        return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nclu), outlier_in, voxel_leaf,
+                                                             static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
                     if (statout)
                         return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nstat), outlier_in, voxel_leaf,
                                                              static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
@@ -762,7 +828,7 @@ int main(int argc, char** argv)
     if (d_vox) pcs_device_free(ctx, d_vox);
     if (d_nvox) pcs_device_free(ctx, d_nvox);
     if (d_stitched) pcs_device_free(ctx, d_stitched);
-    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts, d_filtered, d_nfiltered, d_stat, d_nstat, d_stat_block}) if (p) pcs_device_free(ctx, p);
+    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts, d_filtered, d_nfiltered, d_stat, d_nstat, d_stat_block, d_clu, d_nclu, d_clu_block}) if (p) pcs_device_free(ctx, p);
     if (node) pcs_node_destroy(node);
     stitched.release();
     pcs_destroy(ctx);

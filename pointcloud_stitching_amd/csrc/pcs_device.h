@@ -405,6 +405,24 @@ hipError_t  launch_stat_stage(int stage, const int16_t* d_in, uint32_t n_points,
                               int std_mul_milli, int max_dist_mm, void* d_ws, size_t ws_bytes, int16_t* d_out, int32_t* d_out_points,
                               long long* d_stats, hipStream_t st);
 
+// Euclidean clusters (pcs_cluster_filter_device, pcs_cluster_labels_device, pcs_kernels_cluster.hip; the definition: DESIGN.md section 3
+// "Euclidean clusters"): each launch its own call as launch_outlier_stage's are. The filter form runs stages 0 to kClusterStages - 1:
+// 0 to 5 the cell index with cell edge tolerance_mm (launch_cell_index_stage), 6 to 9 init, union, roots and flag, 10 to 12 the radius
+// filter's tile count, tile scan and emit (launch_outlier_compact_stage), 13 (only with d_stats: eight int64, 8-byte aligned, also
+// given to stage 6, which zeroes it) the statistics block. The labels form runs kClusterLabelStages launches, cluster_label_stage(k)
+// of them: 0 to 8, then 14 (label roots) and 15 (labels) with d_labels (n_points int32), d_sizes (optional) and d_n_clusters; it has
+// no counted variant (d_n_points NULL). d_ws: cluster_workspace_bytes(capacity) bytes, 256-byte aligned; count and capacity as
+// launch_outlier_stage's. cluster_stage_name names all sixteen.
+constexpr int kClusterStages      = 14;
+constexpr int kClusterLabelStages = 11;
+inline int  cluster_label_stage(int k) { return k < 9 ? k : k + 5; }
+size_t      cluster_workspace_bytes(uint32_t capacity);
+const char* cluster_stage_name(int stage);
+hipError_t  launch_cluster_stage(int stage, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
+                                 int tolerance_mm, int min_size, int max_size, void* d_ws, size_t ws_bytes, int16_t* d_out,
+                                 int32_t* d_out_points, long long* d_stats, int32_t* d_labels, int32_t* d_sizes, int32_t* d_n_clusters,
+                                 hipStream_t st);
+
 // Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
 // index is the outlier filter's, cell edge max_dist_mm (launch_cell_index_stage over the target; `index` is its view, or nullptr for
 // an empty target: nobody matches). launch_align_match: one lane per source record, one 144-byte partial per

@@ -136,7 +136,9 @@ struct pcs_ctx {
 
     // radius outlier removal (pcs_capi_outlier.cpp): the cell index, keep bits and tile words of one call, sized from the call's
     // n_points / max_points alone (outlier_workspace_bytes), grown on demand by ensure_ws as the voxel workspace is
-    // (statistical outlier removal, pcs_capi_stat.cpp, asks the same slab for stat_workspace_bytes: the index in front, its own words behind)
+    // (statistical outlier removal, pcs_capi_stat.cpp, asks the same slab for stat_workspace_bytes: the index in front, its own words behind;
+    // Euclidean clusters, pcs_capi_cluster.cpp, for cluster_workspace_bytes, carved the same way. Every call builds its index anew:
+    // nothing of one tenant's is read by the next)
     void*                           s_outlier_ws = nullptr; size_t s_outlier_ws_cap = 0;
 
     // alignment sums and the ICP loop (pcs_capi_align.cpp): the target's cell index (the outlier filter's layout), the match

@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig
+from .types import AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -87,6 +87,11 @@ SYMBOLS = [
     ("pcs_stat_outlier_device", C.c_int, [_VP, _VP, C.c_int, _P(StatOutlierParams), _VP, C.c_size_t, _VP, _VP]),
     ("pcs_stat_outlier_device_counted", C.c_int, [_VP, _VP, _VP, C.c_int, _P(StatOutlierParams), _VP, C.c_size_t, _VP, _VP]),
     ("pcs_stat_outlier", C.c_int, [_VP, _VP, C.c_int, _P(StatOutlierParams), _VP, C.c_size_t, _P(C.c_int), _P(StatOutlierStatsC)]),
+    ("pcs_cluster_filter_device", C.c_int, [_VP, _VP, C.c_int, _P(ClusterParams), _VP, C.c_size_t, _VP, _VP]),
+    ("pcs_cluster_filter_device_counted", C.c_int, [_VP, _VP, _VP, C.c_int, _P(ClusterParams), _VP, C.c_size_t, _VP, _VP]),
+    ("pcs_cluster_filter", C.c_int, [_VP, _VP, C.c_int, _P(ClusterParams), _VP, C.c_size_t, _P(C.c_int), _P(ClusterStatsC)]),
+    ("pcs_cluster_labels_device", C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
+    ("pcs_cluster_labels", C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _P(C.c_int)]),
     ("pcs_align_sums_device", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]),
     ("pcs_align_sums", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _P(AlignSumsC), _VP]),
     ("pcs_align_solve", C.c_int, [_P(AlignSumsC), _P(C.c_double), _P(C.c_double)]),

@@ -36,6 +36,14 @@ STAT_OUTLIER_STAGES = ("clear", "insert", "cell sums", "cell scan", "cell starts
                        "tile count", "tile scan", "emit", "finish")
 STAT_STATS_FIELDS = ("considered", "dense", "s1", "s2_lo", "s2_hi", "threshold", "kept", "reserved")
 
+CLUSTER_TOLERANCE_MIN, CLUSTER_TOLERANCE_MAX = 1, 1000    # pcs_cluster_*: tolerance_mm
+CLUSTER_LAUNCHES = 14                                     # kernel_times_ms intervals of one cluster_filter call with a statistics block (13 without)
+CLUSTER_STAGES = ("clear", "insert", "cell sums", "cell scan", "cell starts", "scatter", "init", "union", "roots", "flag", "tile count",
+                  "tile scan", "emit", "stats")
+CLUSTER_LABEL_LAUNCHES = 11                               # ... of one cluster_labels call
+CLUSTER_LABEL_STAGES = CLUSTER_STAGES[:9] + ("label roots", "labels")
+CLUSTER_STATS_FIELDS = ("considered", "clusters", "kept_clusters", "largest", "kept")      # three reserved words behind them
+
 ALIGN_DIST_MIN, ALIGN_DIST_MAX = 1, 1000                  # pcs_align_*: max_dist_mm
 ALIGN_ITERATIONS_MAX = 100
 ALIGN_STOP_ITERATIONS, ALIGN_STOP_CONVERGED, ALIGN_STOP_REFUSED = 0, 1, 2
@@ -151,6 +159,23 @@ class StatOutlierStatsC(C.Structure):
 
     def as_dict(self) -> dict:
         return {name: int(getattr(self, name)) for name in STAT_STATS_FIELDS}
+
+
+class ClusterParams(C.Structure):
+    """pcs_cluster_params."""
+    _fields_ = [("tolerance_mm", C.c_int32), ("min_size", C.c_int32), ("max_size", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, tolerance_mm: int, min_size: int, max_size: int = 0, reserved: int = 0) -> "ClusterParams":
+        return cls(int(tolerance_mm), int(min_size), int(max_size), int(reserved))
+
+
+class ClusterStatsC(C.Structure):
+    """struct pcs_cluster_stats: eight int64."""
+    _fields_ = [(name, C.c_int64) for name in CLUSTER_STATS_FIELDS] + [("reserved", C.c_int64 * 3)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in CLUSTER_STATS_FIELDS}
 
 
 class AlignSumsC(C.Structure):
