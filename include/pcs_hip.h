@@ -823,6 +823,94 @@ int pcs_cluster_labels_device(pcs_ctx* ctx, const int16_t* d_payload, int n_poin
 int pcs_cluster_labels(pcs_ctx* ctx, const int16_t* payload, int n_points, int tolerance_mm, int32_t* labels, int32_t* sizes,
                        int* n_clusters);   /* host pointers, staged, synchronous */
 
+/* ---- RANSAC plane segmentation on a packed payload (not in the reference) --------------------------------------------------------- *
+ * Connectivity is transitive: everything that stands on a floor is one cluster through the floor. This call takes the dominant planes
+ * (floor, walls, a table) out of the cloud, or hands them out, between the outlier filters and the cluster filter. n records of 5
+ * shorts (0..2 = x, y, z as signed int16 millimetres; colour is not read). Everything is integer; no float anywhere.
+ *   ROUND r   works on the m records that are in no plane accepted so far, in input order (round 0: all of them). Hypothesis h
+ *               (0 .. iterations - 1) draws three positions i_k = ((splitmix64(key) >> 32) * m) >> 32, key = seed << 32 | r << 20 |
+ *               h << 2 | k, k = 0, 1, 2 (splitmix64: z = key + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *               z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31, modulo 2^64).
+ *   PLANE     of the drawn records p0, p1, p2: N = (p1 - p0) x (p2 - p0) (|component| <= 2 * 65535^2, int64), off = N . p0,
+ *               T = isqrt(distance_mm^2 * |N|^2), the exact integer square root of a value below 2^88. N = 0 (equal or collinear
+ *               draws): the hypothesis is DEGENERATE and scores nothing. The sign of N is whatever the draws give.
+ *   INLIER    record p iff |N . p - off| <= T in int64: exactly (N . (p - p0))^2 <= distance_mm^2 |N|^2, a distance to the plane of at
+ *               most distance_mm.
+ *   WINNER    the hypothesis with the most inliers among the round's m records; on a tie the smallest h. m < 3, or a winner with fewer
+ *               than min_inliers inliers (every hypothesis degenerate: 0), ends the segmentation: n_planes = r. Otherwise plane r is
+ *               accepted: its inliers get label r and leave the cloud. No refit of the winner on its inliers. max_planes rounds at most.
+ *   OUTPUT    labels forms: int32 label(i) in {-1, 0, .., n_planes - 1} per record, and n_planes. Filter forms: the kept records in
+ *               input order, all 10 bytes of each unchanged, and their count; kept = the records in NO accepted plane (mode 0) or in
+ *               one (mode 1). Both: (optional) max_planes blocks of pcs_plane_model, those from n_planes on zeroed (sample[] = the INPUT
+ *               indices of the drawn records), and (optional) the statistics block of eight int64: considered, planes, inliers_total,
+ *               kept, largest_plane, degenerate_hypotheses (over the rounds that drew: those with m >= 3), 0, 0.
+ * Exact and deterministic: a function of the payload in its order, the parameters and the seed; the same bytes on every run, whatever
+ * order the atomics arrive in. tests/np_planes.py restates it as brute force. Modelled on PCL's SACSegmentation with SACMODEL_PLANE;
+ * parity with PCL is unpinned. DESIGN.md section 3 has the definition and what follows from it.
+ * pcs_plane_segment_device: asynchronous on the context's stream, no host round trip: init, then per round hypotheses (one lane per
+ *   hypothesis), score (iterations x m inlier tests: the hot launch), select and mark, between two rounds the radius filter's ordered
+ *   compaction (three launches) and the origin indices behind it; at the end finish (the keep bits of the whole input by label, the
+ *   model and statistics blocks) and that compaction once more: 8 max_planes + 1 launches. A round after the segmentation ended
+ *   launches and does nothing; no count leaves the device between rounds. d_out needs room for the worst case: out_shorts >=
+ *   5 n_points is checked up front; nothing outside the first 10 * kept bytes of d_out is written. *d_out_points (device, 4-byte
+ *   aligned, required) receives kept; d_models (device, 8-byte aligned, optional) max_planes blocks; d_stats (device, 8-byte aligned,
+ *   optional) the block. n_points 0 launches nothing and writes a zero count and zeroed blocks.
+ * pcs_plane_segment_device_counted: the count is read from *d_n_points (device, 4-byte aligned) when the kernels run, clamped to
+ *   0..max_points; max_points sizes the workspace, the grids and the output check. It takes the other filters' output and count,
+ *   and its own feed pcs_cluster_filter_device_counted and pcs_voxel_grid_device_counted.
+ * pcs_plane_segment: host pointers, staged through the context, synchronous; models and stats optional.
+ * pcs_plane_labels_device: labels instead of a filtered payload: d_labels (device, 4-byte aligned, n_points int32, required with
+ *   n_points > 0), *d_n_planes (device, 4-byte aligned, required); nothing at or beyond word n_points of d_labels is written.
+ *   8 max_planes - 2 launches. pcs_plane_labels: the host form, synchronous.
+ * pcs_plane_count_inliers_device: the caller's own candidate planes, n_models (1..4096) blocks in HOST memory (nx, ny, nz, off and
+ *   threshold are read), scored by the same score launch over a device payload: d_counts[j] (device, 8-byte aligned, n_models int64)
+ *   = the number of records with |N_j . p - off_j| <= threshold_j. The models leave the host before the call returns (the copy
+ *   waits for the stream's earlier work); the scoring is asynchronous. n_points 0 writes zero counts.
+ *   Refused: |nx|, |ny| or |nz| above 2^34, |off| above 2^52, threshold outside 0..2^52, nx = ny = nz = 0.
+ * pcs_plane_from_points: no context, no device: the model of three records p0, p1, p2 (3 shorts each are read) at distance_mm, as a
+ *   hypothesis that drew them would build it (inliers 0, sample 0 1 2, hypothesis 0). PCS_ERR_INVALID_ARG for a NULL pointer, a
+ *   distance out of range or a degenerate triple (*model is zeroed for the latter).
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the function and the argument), nothing launched, nothing written: a
+ *   parameter out of range, a reserved word != 0, NULL params, a negative count, a NULL pointer (payload and outputs may be NULL with a
+ *   count of 0), an odd payload or output address, a misaligned count, labels, models, counts or stats address, out_shorts below the
+ *   worst case, any overlap among the input and output ranges.
+ * Works on every context: flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH are not read. The workspace (the radius filter's
+ *   plus 32 bytes per record of n_points / max_points and 0.25 MB: csrc/pcs_kernels_plane.hip) lives in the context and grows on
+ *   demand. Cost: iterations x m inlier tests per round. With pcs_kernel_timing enabled a call yields one interval per launch.
+ *   Measured: DESIGN.md section 10 (f14), profiles/plane_probe.txt.                                                                 */
+#define PCS_PLANE_DISTANCE_MIN     1
+#define PCS_PLANE_DISTANCE_MAX     1000
+#define PCS_PLANE_ITERATIONS_MAX   4096
+#define PCS_PLANE_MAX_PLANES       8
+#define PCS_PLANE_MODE_REMOVE      0
+#define PCS_PLANE_MODE_KEEP        1
+typedef struct pcs_plane_params {
+    int32_t  distance_mm, iterations, min_inliers, max_planes;
+    uint32_t seed;
+    int32_t  mode, reserved[2];                           /* reserved words are 0 */
+} pcs_plane_params;
+typedef struct pcs_plane_model {
+    int64_t nx, ny, nz, off, threshold, inliers;
+    int32_t sample[3], hypothesis;
+} pcs_plane_model;
+struct pcs_plane_stats {
+    int64_t considered, planes, inliers_total, kept, largest_plane, degenerate_hypotheses, reserved[2];
+};
+int pcs_plane_segment_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const pcs_plane_params* params, int16_t* d_out,
+                             size_t out_shorts, int32_t* d_out_points, pcs_plane_model* d_models, struct pcs_plane_stats* d_stats);
+int pcs_plane_segment_device_counted(pcs_ctx* ctx, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                     const pcs_plane_params* params, int16_t* d_out, size_t out_shorts, int32_t* d_out_points,
+                                     pcs_plane_model* d_models, struct pcs_plane_stats* d_stats);
+int pcs_plane_segment(pcs_ctx* ctx, const int16_t* payload, int n_points, const pcs_plane_params* params, int16_t* out, size_t out_shorts,
+                      int* out_points, pcs_plane_model* models, struct pcs_plane_stats* stats);   /* host pointers, staged, synchronous */
+int pcs_plane_labels_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const pcs_plane_params* params, int32_t* d_labels,
+                            int32_t* d_n_planes, pcs_plane_model* d_models, struct pcs_plane_stats* d_stats);
+int pcs_plane_labels(pcs_ctx* ctx, const int16_t* payload, int n_points, const pcs_plane_params* params, int32_t* labels, int* n_planes,
+                     pcs_plane_model* models, struct pcs_plane_stats* stats);   /* host pointers, staged, synchronous */
+int pcs_plane_count_inliers_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const pcs_plane_model* models, int n_models,
+                                   int64_t* d_counts);
+int pcs_plane_from_points(const int16_t* p0, const int16_t* p1, const int16_t* p2, int distance_mm, pcs_plane_model* model);
+
 /* ---- extrinsics refinement: nearest-neighbour alignment sums, the rigid fit, the ICP loop (not in the reference) ---------------- *
  * transform[i] comes from four surveyed markers (calibration.py); these calls refine it from the data: move one camera's payload
  * onto another's where they overlap. DESIGN.md section 3 "Alignment sums" has the definition and what follows from it.

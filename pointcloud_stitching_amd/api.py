@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -55,6 +55,19 @@ def compressed_info(container) -> CompressedInfo:
         d = lib.pcs_last_error(None)
         raise PcsError(rc, d.decode() if d else "")
     return info
+
+
+def plane_from_points(p0, p1, p2, distance_mm: int) -> dict:
+    """pcs_plane_from_points: the plane model through three records (x, y, z in int16 millimetres) at distance_mm, as a hypothesis
+    that drew them builds it — no context, no GPU. Raises PcsError (PCS_ERR_INVALID_ARG) for a degenerate triple or a distance
+    outside 1..1000."""
+    lib = _libmod.load()
+    pts = [np.ascontiguousarray(np.asarray(p, np.int64)[:3].astype(np.int16)) for p in (p0, p1, p2)]
+    model = PlaneModel()
+    rc = lib.pcs_plane_from_points(_ptr(pts[0]), _ptr(pts[1]), _ptr(pts[2]), int(distance_mm), C.byref(model))
+    if rc != 0:
+        raise PcsError(rc, "pcs_plane_from_points: a degenerate triple or distance_mm outside 1..1000")
+    return model.as_dict()
 
 
 def _sums_from_c(c: AlignSumsC) -> AlignSums:
@@ -679,6 +692,61 @@ class PcsContext:
         *d_n_clusters (int32, required) the number of clusters. See pcs_cluster_labels_device."""
         self._check(self._lib.pcs_cluster_labels_device(self._h, d_payload or None, int(n_points), int(tolerance_mm), d_labels or None,
                                                         d_sizes or None, d_n_clusters or None))
+
+    # -- plane segmentation (defined by this build; see include/pcs_hip.h) --------------------------
+    def plane_segment(self, payload: np.ndarray, params: PlaneParams):
+        """Packed records (int16 [n,5]) -> (the records in no accepted plane (params.mode 0) or in one (mode 1), input order; the
+        accepted planes' models as dicts; the statistics block as a dict) (pcs_plane_segment: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        out = np.zeros((max(p.shape[0], 1), POINT_SHORTS), np.int16)
+        cnt = C.c_int(0)
+        models = (PlaneModel * max(int(params.max_planes), 1))()
+        stats = PlaneStats()
+        self._check(self._lib.pcs_plane_segment(self._h, _ptr(p), p.shape[0], C.byref(params), _ptr(out), p.shape[0] * POINT_SHORTS,
+                                                C.byref(cnt), models, C.byref(stats)))
+        return out[:cnt.value].copy(), [m.as_dict() for m in models], stats.as_dict()
+
+    def plane_segment_device(self, d_payload: int, n_points: int, params: PlaneParams, d_out: int, out_shorts: int, d_out_points: int,
+                             d_models: int = 0, d_stats: int = 0) -> None:
+        """Asynchronous; device pointers as ints; *d_out_points (int32, required) receives the kept count, d_models (max_planes
+        blocks of 64 bytes, optional) the models, d_stats (eight int64, optional) the statistics block. params may be None (refused).
+        See pcs_plane_segment_device."""
+        self._check(self._lib.pcs_plane_segment_device(self._h, d_payload or None, int(n_points), C.byref(params) if params is not None else None,
+                                                       d_out or None, out_shorts, d_out_points or None, d_models or None, d_stats or None))
+
+    def plane_segment_device_counted(self, d_payload: int, d_n_points: int, max_points: int, params: PlaneParams, d_out: int,
+                                     out_shorts: int, d_out_points: int, d_models: int = 0, d_stats: int = 0) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run. See
+        pcs_plane_segment_device_counted."""
+        self._check(self._lib.pcs_plane_segment_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
+                                                               C.byref(params) if params is not None else None, d_out or None, out_shorts,
+                                                               d_out_points or None, d_models or None, d_stats or None))
+
+    def plane_labels(self, payload: np.ndarray, params: PlaneParams):
+        """Packed records (int16 [n,5]) -> (labels int32 [n]: the accepted plane a record is an inlier of, -1 for none; the number of
+        accepted planes; the models as dicts; the statistics block as a dict) (pcs_plane_labels: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        n = p.shape[0]
+        labels = np.zeros(max(n, 1), np.int32)
+        cnt = C.c_int(-1)
+        models = (PlaneModel * max(int(params.max_planes), 1))()
+        stats = PlaneStats()
+        self._check(self._lib.pcs_plane_labels(self._h, _ptr(p) if n else None, n, C.byref(params), _ptr(labels), C.byref(cnt), models,
+                                               C.byref(stats)))
+        return labels[:n].copy(), int(cnt.value), [m.as_dict() for m in models], stats.as_dict()
+
+    def plane_labels_device(self, d_payload: int, n_points: int, params: PlaneParams, d_labels: int, d_n_planes: int, d_models: int = 0,
+                            d_stats: int = 0) -> None:
+        """Asynchronous; device pointers as ints; d_labels receives n_points int32, *d_n_planes (int32, required) the number of
+        accepted planes. See pcs_plane_labels_device."""
+        self._check(self._lib.pcs_plane_labels_device(self._h, d_payload or None, int(n_points), C.byref(params) if params is not None else None,
+                                                      d_labels or None, d_n_planes or None, d_models or None, d_stats or None))
+
+    def plane_count_inliers_device(self, d_payload: int, n_points: int, models, d_counts: int) -> None:
+        """models: a sequence of PlaneModel (host) — nx, ny, nz, off and threshold are read; d_counts receives one int64 per model:
+        the records with |N . p - off| <= threshold. See pcs_plane_count_inliers_device."""
+        arr = (PlaneModel * max(len(models), 1))(*models)
+        self._check(self._lib.pcs_plane_count_inliers_device(self._h, d_payload or None, int(n_points), arr, len(models), d_counts or None))
 
     # -- surface normals (defined by this build; see include/pcs_hip.h) -----------------------------
     def estimate_normals(self, payload: np.ndarray, radius_mm: int, min_neighbors: int, flatness: int = 0, viewpoint_mm=None,

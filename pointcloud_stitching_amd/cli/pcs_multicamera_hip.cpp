@@ -54,6 +54,14 @@
 //                      pcs_voxel_grid_device_counted. -t prints `Statistical outlier removal: <in> -> <kept> points (dense <M>,
 //                      threshold <T>/256 per k)` per frame-set. Not with -G: the node library has no such filter. Zero-depth pixels
 //                      sit on one point and drag the mean down: with -i give -Z (or -B).
+//              -M <distance_mm,iterations[,min_inliers[,max_planes[,seed]]]>  plane segmentation on the stitched cloud
+//                      (pcs_plane_segment_device, mode 0: up to max_planes rounds, each takes the plane through three drawn records that
+//                      has the most records within distance_mm, out of `iterations` such planes, out of the cloud while it has
+//                      min_inliers records; defaults 3, 1 and seed 1): after -T, -B / -d, -O and -K, before -E and -V. It takes the
+//                      stage in front of it through the counted form wherever that stage left a device count, and its output and
+//                      device count feed -E or -V the same way. -t prints `Plane segmentation: <in> -> <kept> points (<planes>
+//                      planes, <inliers> inliers)` and one line `Plane <r>: <inliers> inliers, normal (<nx>, <ny>, <nz>), offset <off>,
+//                      hypothesis <h>` per accepted plane and frame-set. Not with -G: the node library has no such filter.
 //              -E <tolerance_mm,min_size[,max_size]>  Euclidean cluster filter on the stitched cloud (pcs_cluster_filter_device: records
 //                      within tolerance_mm of each other are connected; a record stays iff its connected component holds min_size to
 //                      max_size records, max_size 0 or absent: no upper bound): after -T, -B / -d, -O and -K, before -V. It takes
@@ -79,6 +87,7 @@
 #include "pcs_cluster.h"
 #include "pcs_cropbox.h"
 #include "pcs_outlier.h"
+#include "pcs_plane.h"
 #include "pcs_statoutlier.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
@@ -102,6 +111,8 @@ static bool outlier = false;
 static int outlier_radius = 0, outlier_neighbors = 0;
 static bool statout = false;
 static pcs_stat_outlier_params statout_params{};
+static bool plane = false;
+static pcs_plane_params plane_params{};
 static bool cluster = false;
 static pcs_cluster_params cluster_params{};
 
@@ -129,6 +140,7 @@ static void usage()
               << " -K <mean_k,std_mul_milli,max_dist_mm>  statistical outlier removal on the stitched cloud: a record stays iff it has mean_k\n"
               << "                  others within max_dist_mm (1..64, 1..1000) and its summed distance to the nearest mean_k is at most the\n"
               << "                  cloud's mean + std_mul_milli / 1000 (0..10000) deviations; after -T, -B / -d and -O, before -V; not with -G\n"
+              << pcs_plane::help()
               << pcs_cluster::help()
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
@@ -140,7 +152,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -187,6 +199,12 @@ int main(int argc, char** argv)
                 statout = true;
                 break;
             }
+            case 'M': {
+                std::string why;
+                if (!pcs_plane::parse(optarg, plane_params, why)) { std::cerr << "-M " << optarg << ": " << why << std::endl; return 2; }
+                plane = true;
+                break;
+            }
             case 'E': {
                 std::string why;
                 if (!pcs_cluster::parse(optarg, cluster_params, why)) { std::cerr << "-E " << optarg << ": " << why << std::endl; return 2; }
@@ -203,6 +221,7 @@ int main(int argc, char** argv)
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
     if (outlier && n_gpus > 0) { std::cerr << "-O is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
     if (statout && n_gpus > 0) { std::cerr << "-K is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
+    if (plane && n_gpus > 0) { std::cerr << "-M is not available with -G: the node library has no plane segmentation" << std::endl; return 2; }
     if (cluster && n_gpus > 0) { std::cerr << "-E is not available with -G: the node library has no cluster filter" << std::endl; return 2; }
     if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
@@ -343,7 +362,7 @@ int main(int argc, char** argv)
     }
     // -B with -i -V: the cropped payload and its counts stay on the device between the two calls
     void *d_pay = nullptr, *d_pay_counts = nullptr;
-    if (source && ((crop && voxel_leaf) || outlier || statout || cluster)) {
+    if (source && ((crop && voxel_leaf) || outlier || statout || plane || cluster)) {
         if (pcs_device_malloc(ctx, &d_pay, pcs_max_payload_shorts(ctx) * sizeof(int16_t) + 64) != PCS_OK ||
             pcs_device_malloc(ctx, &d_pay_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
@@ -372,6 +391,31 @@ int main(int argc, char** argv)
         if (pcs_memcpy_d2h(ctx, &st, d_stat_block, sizeof st) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
         std::cout << "Statistical outlier removal: " << st.considered << " -> " << st.kept << " points (dense " << st.dense << ", threshold "
                   << st.threshold << "/256 per k)" << std::endl;
+        return true;
+    };
+
+    // -M: the same, and the model blocks
+    void *d_pl = nullptr, *d_npl = nullptr, *d_pl_block = nullptr, *d_pl_models = nullptr;
+    if (plane) {
+        const size_t bytes = source ? pcs_max_payload_shorts(ctx) * sizeof(int16_t) : (size_t)n_streams * cam_cap_bytes;
+        if (pcs_device_malloc(ctx, &d_pl, bytes + 64) != PCS_OK || pcs_device_malloc(ctx, &d_npl, 64) != PCS_OK ||
+            pcs_device_malloc(ctx, &d_pl_block, sizeof(pcs_plane_stats)) != PCS_OK ||
+            pcs_device_malloc(ctx, &d_pl_models, sizeof(pcs_plane_model) * PCS_PLANE_MAX_PLANES) != PCS_OK) {
+            std::cerr << pcs_last_error(ctx) << std::endl; return 1;
+        }
+    }
+    // what -t prints for -M: the block's numbers and the accepted planes, after the frame-set's last launch
+    auto print_plane = [&]() {
+        pcs_plane_stats st{};
+        pcs_plane_model models[PCS_PLANE_MAX_PLANES] = {};
+        if (pcs_memcpy_d2h(ctx, &st, d_pl_block, sizeof st) != PCS_OK ||
+            pcs_memcpy_d2h(ctx, models, d_pl_models, sizeof(pcs_plane_model) * (size_t)plane_params.max_planes) != PCS_OK ||
+            pcs_synchronize(ctx) != PCS_OK) return false;
+        std::cout << "Plane segmentation: " << st.considered << " -> " << st.kept << " points (" << st.planes << " planes, " << st.inliers_total
+                  << " inliers)" << std::endl;
+        for (int r = 0; r < (int)st.planes && r < PCS_PLANE_MAX_PLANES; r++)
+            std::cout << "Plane " << r << ": " << models[r].inliers << " inliers, normal (" << models[r].nx << ", " << models[r].ny << ", "
+                      << models[r].nz << "), offset " << models[r].off << ", hypothesis " << models[r].hypothesis << std::endl;
         return true;
     };
 
@@ -407,7 +451,7 @@ int main(int argc, char** argv)
                       pcs_device_malloc(ctx, &d_nvox, 64) != PCS_OK)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
         if (!stitched.resize(PCS_HEADER_SHORTS + vox_cap_points * PCS_POINT_SHORTS)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
-    if ((voxel_leaf || outlier || statout || cluster) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
+    if ((voxel_leaf || outlier || statout || plane || cluster) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
         d_depth.resize(n_streams, nullptr); d_color.resize(n_streams, nullptr);
         for (int s = 0; s < n_streams; s++) {
             const size_t db = (size_t)cfgs[s].depth.width * cfgs[s].depth.height * 2;
@@ -585,7 +629,7 @@ int main(int argc, char** argv)
                     std::cout << "Voxel grid over " << n_gpus << " GPU(s): kernels " << vstats.kernels_ms << " ms, exchange " << vstats.exchange_ms
                               << " ms (" << vstats.exchanged_bytes << " B), root " << vstats.root_voxel_ms << " ms, " << vstats.partials
                               << (voxel_route == PCS_NODE_VOXEL_PARTIALS ? " partials -> " : " points -> ") << vstats.voxels << " voxels" << std::endl;
-            } else if (outlier || statout || cluster) {
+            } else if (outlier || statout || plane || cluster) {
                 // the payload on the device (under -Z / -B / -d as ever), the filter on its device count, then the voxel grid on the
                 // filter's device count or the kept records out: no count leaves the device in between
                 for (int s = 0; s < n_streams; s++) {
@@ -610,6 +654,12 @@ int main(int argc, char** argv)
                     rc = pcs_stat_outlier_device_counted(ctx, d_last, d_nlast, max_points, &statout_params, static_cast<int16_t*>(d_stat), max_shorts,
                                                          static_cast<int32_t*>(d_nstat), static_cast<pcs_stat_outlier_stats*>(d_stat_block));
                     d_last = static_cast<const int16_t*>(d_stat); d_nlast = static_cast<const int32_t*>(d_nstat);
+                }
+                if (rc == PCS_OK && plane) {
+                    rc = pcs_plane_segment_device_counted(ctx, d_last, d_nlast, max_points, &plane_params, static_cast<int16_t*>(d_pl), max_shorts,
+                                                          static_cast<int32_t*>(d_npl), static_cast<pcs_plane_model*>(d_pl_models),
+                                                          static_cast<pcs_plane_stats*>(d_pl_block));
+                    d_last = static_cast<const int16_t*>(d_pl); d_nlast = static_cast<const int32_t*>(d_npl);
                 }
                 if (rc == PCS_OK && cluster) {
                     rc = pcs_cluster_filter_device_counted(ctx, d_last, d_nlast, max_points, &cluster_params, static_cast<int16_t*>(d_clu), max_shorts,
@@ -639,6 +689,7 @@ int main(int argc, char** argv)
                 }
                 if (timer && outlier) std::cout << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl;
                 if (timer && statout && !print_statout()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                if (timer && plane && !print_plane()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
                 if (timer && cluster && !print_cluster()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
             } else if (voxel_leaf) {
                 for (int s = 0; s < n_streams; s++) {
@@ -758,11 +809,33 @@ int main(int argc, char** argv)
                 }
                 if (timer && !print_statout()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
             }
-            if (cluster) {
+            if (plane) {
                 // behind -O or -K: that filter's output and device count, through the counted form; else the stitched payload and
                 // its host count
                 const size_t out_shorts = (size_t)n_streams * cam_cap_bytes / 2;
                 const int32_t* d_nprev = static_cast<const int32_t*>(statout ? d_nstat : outlier ? d_nfiltered : nullptr);
+                rc = d_nprev ? pcs_plane_segment_device_counted(ctx, d_result, d_nprev, outlier_in, &plane_params, static_cast<int16_t*>(d_pl),
+                                                                out_shorts, static_cast<int32_t*>(d_npl), static_cast<pcs_plane_model*>(d_pl_models),
+                                                                static_cast<pcs_plane_stats*>(d_pl_block))
+                             : pcs_plane_segment_device(ctx, d_result, total_pts, &plane_params, static_cast<int16_t*>(d_pl), out_shorts,
+                                                        static_cast<int32_t*>(d_npl), static_cast<pcs_plane_model*>(d_pl_models),
+                                                        static_cast<pcs_plane_stats*>(d_pl_block));
+                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                d_result = static_cast<const int16_t*>(d_pl);
+                if (!voxel_leaf && !cluster) {      // (behind it -E and -V read the count where it is)
+                    int32_t kept = 0;
+                    if (pcs_memcpy_d2h(ctx, &kept, d_npl, sizeof kept) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) {
+                        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
+                    }
+                    total_pts = kept;
+                }
+                if (timer && !print_plane()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+            }
+            if (cluster) {
+                // behind -O, -K or -M: that filter's output and device count, through the counted form; else the stitched payload and
+                // its host count
+                const size_t out_shorts = (size_t)n_streams * cam_cap_bytes / 2;
+                const int32_t* d_nprev = static_cast<const int32_t*>(plane ? d_npl : statout ? d_nstat : outlier ? d_nfiltered : nullptr);
                 rc = d_nprev ? pcs_cluster_filter_device_counted(ctx, d_result, d_nprev, outlier_in, &cluster_params, static_cast<int16_t*>(d_clu),
                                                                  out_shorts, static_cast<int32_t*>(d_nclu), static_cast<pcs_cluster_stats*>(d_clu_block))
                              : pcs_cluster_filter_device(ctx, d_result, total_pts, &cluster_params, static_cast<int16_t*>(d_clu), out_shorts,
@@ -782,6 +855,9 @@ int main(int argc, char** argv)
                 auto run_voxel = [&]() {
                     if (cluster)
                         return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nclu), outlier_in, voxel_leaf,
+                                                             static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
+                    if (plane)
+                        return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_npl), outlier_in, voxel_leaf,
                                                              static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
                     if (statout)
                         return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nstat), outlier_in, voxel_leaf,
@@ -828,7 +904,7 @@ int main(int argc, char** argv)
     if (d_vox) pcs_device_free(ctx, d_vox);
     if (d_nvox) pcs_device_free(ctx, d_nvox);
     if (d_stitched) pcs_device_free(ctx, d_stitched);
-    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts, d_filtered, d_nfiltered, d_stat, d_nstat, d_stat_block, d_clu, d_nclu, d_clu_block}) if (p) pcs_device_free(ctx, p);
+    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts, d_filtered, d_nfiltered, d_stat, d_nstat, d_stat_block, d_clu, d_nclu, d_clu_block, d_pl, d_npl, d_pl_block, d_pl_models}) if (p) pcs_device_free(ctx, p);
     if (node) pcs_node_destroy(node);
     stitched.release();
     pcs_destroy(ctx);

@@ -386,10 +386,12 @@ struct OutlierIndexView {
 };
 hipError_t  outlier_index_view(uint32_t capacity, void* d_ws, size_t ws_bytes, OutlierIndexView* view);
 // What stage 0 leaves and launch_outlier_compact_stage reads, for a flag kernel other than the radius filter's (pcs_kernels_stat.hip):
-// the control block (the record count) and keep_bits[w] = the keep bits of records 64 w .. 64 w + 63, a bit at or beyond the count 0.
+// the control block (the record count) and keep_bits[w] = the keep bits of records 64 w .. 64 w + 63, a bit at or beyond the count 0;
+// tile_prefix[t] = what the tile scan leaves: the kept records in front of tile t (pcs_kernels_plane.hip moves its origin indices by it).
 struct OutlierKeepView {
     const OutlierCtl*   ctl;
     unsigned long long* keep_bits;
+    const uint32_t*     tile_prefix;
 };
 hipError_t  outlier_keep_view(uint32_t capacity, void* d_ws, size_t ws_bytes, OutlierKeepView* view);
 
@@ -422,6 +424,49 @@ hipError_t  launch_cluster_stage(int stage, const int16_t* d_in, uint32_t n_poin
                                  int tolerance_mm, int min_size, int max_size, void* d_ws, size_t ws_bytes, int16_t* d_out,
                                  int32_t* d_out_points, long long* d_stats, int32_t* d_labels, int32_t* d_sizes, int32_t* d_n_clusters,
                                  hipStream_t st);
+
+// Plane segmentation (pcs_plane_segment_device, pcs_plane_labels_device, pcs_plane_count_inliers_device, pcs_kernels_plane.hip; the
+// definition: DESIGN.md section 3 "Plane segmentation"): each launch its own call, so that the host layer can bracket them one by one.
+// A call is kPlaneInit, then per round r = 0 .. max_planes - 1 kPlaneHypotheses, kPlaneScore, kPlaneSelect, kPlaneMark and — in front
+// of another round — kPlaneTileCount, kPlaneTileScan, kPlaneEmit (launch_outlier_compact_stage from the round's cloud into the next
+// round's) and kPlaneOrigins; then kPlaneFinish and, in the filter form, kPlaneOutCount, kPlaneOutScan, kPlaneOutEmit (the same
+// compaction from the input into d_out / d_out_points). The record count is n_points, or *d_n_points clamped to 0..capacity when that
+// pointer is given, read by kPlaneInit on the device. d_ws: plane_workspace_bytes(capacity) bytes, 256-byte aligned. d_labels NULL
+// (the filter form): the workspace's own. d_models (max_planes blocks of 64 bytes), d_stats (eight int64), d_n_planes: optional,
+// written by kPlaneFinish. launch_plane_count: the score launch alone over n_models planes of five int64 (PlaneEq) at
+// plane_count_planes(d_ws) — the front of the workspace, plane_count_workspace_bytes() bytes of it — into d_counts (zeroed by the
+// caller). plane_host_staging: 1024 bytes of the workspace for a host form's models (at 0), statistics (at 512) and n_planes (at 576).
+constexpr int kPlaneMaxHypotheses = 4096;
+constexpr int kPlaneMaxPlanes     = 8;
+enum PlaneStep : int {
+    kPlaneInit, kPlaneHypotheses, kPlaneScore, kPlaneSelect, kPlaneMark, kPlaneTileCount, kPlaneTileScan, kPlaneEmit, kPlaneOrigins,
+    kPlaneFinish, kPlaneOutCount, kPlaneOutScan, kPlaneOutEmit, kPlaneSteps
+};
+struct PlaneJob {
+    const int16_t* d_in;
+    uint32_t       n_points;
+    const int32_t* d_n_points;
+    uint32_t       capacity;
+    int32_t        distance_mm, iterations, min_inliers, max_planes;
+    uint32_t       seed;
+    int32_t        mode;
+    void*          d_ws;
+    size_t         ws_bytes;
+    int16_t*       d_out;
+    int32_t*       d_out_points;
+    int32_t*       d_labels;
+    int32_t*       d_n_planes;
+    void*          d_models;
+    long long*     d_stats;
+};
+size_t      plane_workspace_bytes(uint32_t capacity);
+size_t      plane_count_workspace_bytes();
+long long*  plane_count_planes(void* d_ws);
+void*       plane_host_staging(uint32_t capacity, void* d_ws);
+const char* plane_step_name(int step);
+hipError_t  launch_plane_step(const PlaneJob& job, int step, int round, hipStream_t st);
+hipError_t  launch_plane_count(const int16_t* d_in, uint32_t n_points, void* d_ws, size_t ws_bytes, uint32_t n_models,
+                               unsigned long long* d_counts, hipStream_t st);
 
 // Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
 // index is the outlier filter's, cell edge max_dist_mm (launch_cell_index_stage over the target; `index` is its view, or nullptr for

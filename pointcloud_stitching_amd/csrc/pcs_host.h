@@ -1,7 +1,7 @@
 // pcs_host.h — what the translation units of the C ABI share: the context itself and the helpers more than one of them calls.
 // pcs_capi.cpp: contexts, the a1 / a2 twins, the fused path, host forms, plumbing; pcs_capi_voxel.cpp: the voxel grid, partials, sinks;
 // pcs_capi_codec.cpp: the payload codec; and the payload-cloud family over the cell index — pcs_capi_outlier.cpp, pcs_capi_stat.cpp,
-// pcs_capi_normals.cpp, pcs_capi_align.cpp — whose common checks, slab policy, index build and staging live in pcs_capi_cloud.cpp.
+// pcs_capi_normals.cpp, pcs_capi_align.cpp, pcs_capi_cluster.cpp, and pcs_capi_plane.cpp, which uses the family's compaction alone — whose common checks, slab policy, index build and staging live in pcs_capi_cloud.cpp.
 // Internal to libpcs_hip.so; nothing here is exported.
 #ifndef PCS_HOST_H
 #define PCS_HOST_H
@@ -137,8 +137,9 @@ struct pcs_ctx {
     // radius outlier removal (pcs_capi_outlier.cpp): the cell index, keep bits and tile words of one call, sized from the call's
     // n_points / max_points alone (outlier_workspace_bytes), grown on demand by ensure_ws as the voxel workspace is
     // (statistical outlier removal, pcs_capi_stat.cpp, asks the same slab for stat_workspace_bytes: the index in front, its own words behind;
-    // Euclidean clusters, pcs_capi_cluster.cpp, for cluster_workspace_bytes, carved the same way. Every call builds its index anew:
-    // nothing of one tenant's is read by the next)
+    // Euclidean clusters, pcs_capi_cluster.cpp, for cluster_workspace_bytes, carved the same way; plane segmentation,
+    // pcs_capi_plane.cpp, for plane_workspace_bytes: its own words in front, the filter's carve behind them for the control block, keep
+    // bits and tile words. Every call builds what it reads anew: nothing of one tenant's is read by the next)
     void*                           s_outlier_ws = nullptr; size_t s_outlier_ws_cap = 0;
 
     // alignment sums and the ICP loop (pcs_capi_align.cpp): the target's cell index (the outlier filter's layout), the match

@@ -483,7 +483,7 @@ hipError_t outlier_keep_view(uint32_t capacity, void* d_ws, size_t ws_bytes, Out
 {
     if (!capacity || !view || ws_bytes < outlier_workspace_bytes(capacity) || ((uintptr_t)d_ws & 255u)) return hipErrorInvalidValue;
     const OutlierCarve cv(capacity, d_ws);
-    *view = OutlierKeepView{cv.ctl, cv.keep_bits};
+    *view = OutlierKeepView{cv.ctl, cv.keep_bits, cv.tile_prefix};
     return hipSuccess;
 }
 

@@ -1,8 +1,8 @@
 // pcs_outlier_index.h — the uniform-grid neighbour index's device-side vocabulary: what a kernel needs to find a cell's run in the
 // index that the kIndexStages launches of launch_cell_index_stage build (pcs_kernels_outlier.hip has the build and its description).
 // Included by pcs_kernels_outlier.hip (radius outlier removal), pcs_kernels_stat.hip (statistical outlier removal),
-// pcs_kernels_align.hip (alignment sums), pcs_kernels_normals.hip (surface normals) and pcs_kernels_cluster.hip (Euclidean clusters),
-// never compiled alone.
+// pcs_kernels_align.hip (alignment sums), pcs_kernels_normals.hip (surface normals), pcs_kernels_cluster.hip (Euclidean clusters)
+// and pcs_kernels_plane.hip (plane segmentation: load_xyz alone), never compiled alone.
 #pragma once
 
 #include "pcs_kernels_common.h"

@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig
+from .types import AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -92,6 +92,13 @@ SYMBOLS = [
     ("pcs_cluster_filter", C.c_int, [_VP, _VP, C.c_int, _P(ClusterParams), _VP, C.c_size_t, _P(C.c_int), _P(ClusterStatsC)]),
     ("pcs_cluster_labels_device", C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     ("pcs_cluster_labels", C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _P(C.c_int)]),
+    ("pcs_plane_segment_device", C.c_int, [_VP, _VP, C.c_int, _P(PlaneParams), _VP, C.c_size_t, _VP, _VP, _VP]),
+    ("pcs_plane_segment_device_counted", C.c_int, [_VP, _VP, _VP, C.c_int, _P(PlaneParams), _VP, C.c_size_t, _VP, _VP, _VP]),
+    ("pcs_plane_segment", C.c_int, [_VP, _VP, C.c_int, _P(PlaneParams), _VP, C.c_size_t, _P(C.c_int), _P(PlaneModel), _P(PlaneStats)]),
+    ("pcs_plane_labels_device", C.c_int, [_VP, _VP, C.c_int, _P(PlaneParams), _VP, _VP, _VP, _VP]),
+    ("pcs_plane_labels", C.c_int, [_VP, _VP, C.c_int, _P(PlaneParams), _VP, _P(C.c_int), _P(PlaneModel), _P(PlaneStats)]),
+    ("pcs_plane_count_inliers_device", C.c_int, [_VP, _VP, C.c_int, _P(PlaneModel), C.c_int, _VP]),
+    ("pcs_plane_from_points", C.c_int, [_VP, _VP, _VP, C.c_int, _P(PlaneModel)]),
     ("pcs_align_sums_device", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]),
     ("pcs_align_sums", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _P(AlignSumsC), _VP]),
     ("pcs_align_solve", C.c_int, [_P(AlignSumsC), _P(C.c_double), _P(C.c_double)]),

@@ -44,6 +44,24 @@ CLUSTER_LABEL_LAUNCHES = 11                               # ... of one cluster_l
 CLUSTER_LABEL_STAGES = CLUSTER_STAGES[:9] + ("label roots", "labels")
 CLUSTER_STATS_FIELDS = ("considered", "clusters", "kept_clusters", "largest", "kept")      # three reserved words behind them
 
+PLANE_DISTANCE_MIN, PLANE_DISTANCE_MAX = 1, 1000          # pcs_plane_*: distance_mm
+PLANE_ITERATIONS_MAX, PLANE_MAX_PLANES = 4096, 8
+PLANE_MODE_REMOVE, PLANE_MODE_KEEP = 0, 1
+PLANE_STATS_FIELDS = ("considered", "planes", "inliers_total", "kept", "largest_plane", "degenerate_hypotheses")    # two reserved words behind them
+PLANE_MODEL_FIELDS = ("nx", "ny", "nz", "off", "threshold", "inliers")
+
+
+def plane_stages(max_planes: int, labels: bool = False) -> tuple:
+    """The launches of one plane_segment (8 max_planes + 1) or plane_labels (8 max_planes - 2) call, in kernel_times_ms order."""
+    out = ["init"]
+    for r in range(max_planes):
+        out += ["hypotheses", "score", "select", "mark"]
+        if r + 1 < max_planes:
+            out += ["tile count", "tile scan", "emit", "origins"]
+    out.append("finish")
+    return tuple(out if labels else out + ["out tile count", "out tile scan", "out emit"])
+
+
 ALIGN_DIST_MIN, ALIGN_DIST_MAX = 1, 1000                  # pcs_align_*: max_dist_mm
 ALIGN_ITERATIONS_MAX = 100
 ALIGN_STOP_ITERATIONS, ALIGN_STOP_CONVERGED, ALIGN_STOP_REFUSED = 0, 1, 2
@@ -176,6 +194,37 @@ class ClusterStatsC(C.Structure):
 
     def as_dict(self) -> dict:
         return {name: int(getattr(self, name)) for name in CLUSTER_STATS_FIELDS}
+
+
+class PlaneParams(C.Structure):
+    """pcs_plane_params: eight 32-bit words."""
+    _fields_ = [("distance_mm", C.c_int32), ("iterations", C.c_int32), ("min_inliers", C.c_int32), ("max_planes", C.c_int32),
+                ("seed", C.c_uint32), ("mode", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    @classmethod
+    def make(cls, distance_mm: int, iterations: int, min_inliers: int = 3, max_planes: int = 1, seed: int = 1, mode: int = 0,
+             reserved=(0, 0)) -> "PlaneParams":
+        return cls(int(distance_mm), int(iterations), int(min_inliers), int(max_planes), int(seed) & 0xFFFFFFFF, int(mode),
+                   (C.c_int32 * 2)(int(reserved[0]), int(reserved[1])))
+
+
+class PlaneModel(C.Structure):
+    """pcs_plane_model: 64 bytes."""
+    _fields_ = [(name, C.c_int64) for name in PLANE_MODEL_FIELDS] + [("sample", C.c_int32 * 3), ("hypothesis", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        d = {name: int(getattr(self, name)) for name in PLANE_MODEL_FIELDS}
+        d["sample"] = tuple(int(v) for v in self.sample)
+        d["hypothesis"] = int(self.hypothesis)
+        return d
+
+
+class PlaneStats(C.Structure):
+    """struct pcs_plane_stats: eight int64."""
+    _fields_ = [(name, C.c_int64) for name in PLANE_STATS_FIELDS] + [("reserved", C.c_int64 * 2)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in PLANE_STATS_FIELDS}
 
 
 class AlignSumsC(C.Structure):

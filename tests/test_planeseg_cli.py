@@ -1,0 +1,190 @@
+"""-M (plane segmentation) of pcs-multicamera-optimized, end to end on the GPU: two edge servers on loopback into the centre with -M
+(alone, behind -O and -K, in front of -E and -V), the cameras of the node itself with -i -Z -M, each against the brute-force
+restatement (tests/np_planes.py) of what the stage in front of it produced — that stage restated by the existing numpy restatements
+— the -t lines against the restatement's statistics and models, and without -M the dump of today. (The flag surface needs no GPU:
+tests/test_planeseg_cpu.py.)"""
+import subprocess
+
+import numpy as np
+import pytest
+
+import np_clusters as NC
+import np_planes as N
+import np_radius_outlier as NR
+import np_stat_outlier as NS
+from test_wire import CENTRAL, CLI_DIR, EDGE, frame_inputs, free_port, retry_server_start, wait_listening
+from pointcloud_stitching_amd import synthetic as S
+from pointcloud_stitching_amd.api import PcsContext
+from pointcloud_stitching_amd.types import FLAG_DROP_INVALID, HEADER_SHORTS
+
+pytestmark = pytest.mark.gpu
+
+STAR = (30, 256, 300, 3, 7)        # distance_mm, iterations, min_inliers, max_planes, seed for two 64x48 edge payloads
+RADIUS = (100, 5)                  # the -O in front of it
+STAT = (8, 2000, 200)              # ... and the -K
+CLUSTER = (100, 50, 3000)          # the -E behind it
+LOCAL = (50, 128, 100, 2, 3)       # ... for three 64x48 cameras of the node with invalid depth dropped
+LOCAL_BEHIND_STAT = (30, 256, 200, 3, 7)
+LOCAL_CLUSTER = (150, 30, 0)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    subprocess.run(["make", "-C", CLI_DIR], check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+
+
+@pytest.fixture(scope="module")
+def edge_payload(oracle):
+    cfgs, depth, color = frame_inputs(1, 64, 48, 0, single=True)
+    cam, _ = oracle.process_frames(cfgs, depth, color)
+    return cam
+
+
+def dump(path):
+    raw = np.fromfile(path, dtype=np.uint8)
+    assert int.from_bytes(raw[:4].tobytes(), "little") == raw.size - 4
+    return raw[4:].view(np.int16).reshape(-1, 5)
+
+
+def star_dump(tmp_path, extra):
+    """Two pull-mode edges (the same camera twice) into a centre that dumps its one frame-set; returns (records, stdout)."""
+    out = str(tmp_path / "dump.bin")
+    p1, p2 = free_port(), free_port()
+    edges = [subprocess.Popen([EDGE, "-f", "synth:64x48", "-m", "-r", "2", "-p", str(p), "-P"],
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for p in (p1, p2)]
+    central = None
+    try:
+        wait_listening([p1, p2], procs=edges)
+        central = subprocess.Popen([CENTRAL, "-c", f"127.0.0.1:{p1},127.0.0.1:{p2}", "-q", "-r", "1", "-o", out] + extra,
+                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        stdout, err = central.communicate(timeout=150)
+        assert central.returncode == 0, err
+        return dump(out), stdout
+    finally:
+        for p in edges + ([central] if central else []):
+            if p.poll() is None:
+                p.kill()
+
+
+def segmented(rec, params):
+    """The restatement of -M over rec: (kept records, the lines -t prints)."""
+    distance, iterations, min_inliers, max_planes, seed = params
+    labels, n_planes, models, stats, kept = N.segment(rec, distance, iterations, min_inliers, max_planes, seed, 0)
+    assert n_planes >= 1 and 0 < kept.shape[0] < rec.shape[0], "the fixture must have kept and dropped records"
+    lines = [f"Plane segmentation: {stats['considered']} -> {stats['kept']} points ({stats['planes']} planes, {stats['inliers_total']} inliers)"]
+    lines += [f"Plane {r}: {m['inliers']} inliers, normal ({m['nx']}, {m['ny']}, {m['nz']}), offset {m['off']}, hypothesis {m['hypothesis']}"
+              for r, m in enumerate(models[:n_planes])]
+    return kept, lines
+
+
+def option(params):
+    return ",".join(str(v) for v in params)
+
+
+def has_lines(stdout, lines):
+    out = stdout.splitlines()
+    return all(line in out for line in lines)
+
+
+@retry_server_start
+def test_star_with_plane_segmentation(edge_payload, tmp_path):
+    stitched = np.concatenate([edge_payload, edge_payload])
+    want, lines = segmented(stitched, STAR)
+    got, stdout = star_dump(tmp_path, ["-M", option(STAR), "-t"])
+    assert got.shape == want.shape and (got == want).all()
+    assert has_lines(stdout, lines), stdout
+
+
+@retry_server_start
+def test_star_with_the_defaults(edge_payload, tmp_path):
+    """-M distance_mm,iterations alone: min_inliers 3, max_planes 1, seed 1."""
+    stitched = np.concatenate([edge_payload, edge_payload])
+    want, lines = segmented(stitched, (60, 128, 3, 1, 1))
+    got, stdout = star_dump(tmp_path, ["-M", "60,128", "-t"])
+    assert got.shape == want.shape and (got == want).all()
+    assert has_lines(stdout, lines), stdout
+
+
+@retry_server_start
+def test_star_without_the_option_is_unchanged(edge_payload, tmp_path):
+    stitched = np.concatenate([edge_payload, edge_payload])
+    got, stdout = star_dump(tmp_path, ["-t"])
+    assert got.shape == stitched.shape and (got == stitched).all() and "Plane" not in stdout
+
+
+@pytest.mark.parametrize("timer", [False, True])
+@retry_server_start
+def test_star_between_the_outlier_filters_and_the_cluster_filter_then_voxel_grid(edge_payload, oracle, tmp_path, timer):
+    stitched = np.concatenate([edge_payload, edge_payload])
+    first = NR.radius_outlier(stitched, *RADIUS)
+    second, _, _ = NS.stat_outlier(first, *STAT)
+    third, lines = segmented(second, STAR)
+    kept, _, stats = NC.cluster_filter(third, *CLUSTER)
+    want = oracle.voxel_grid(kept, 100)
+    assert 0 < want.shape[0] < kept.shape[0] < third.shape[0] < second.shape[0] < first.shape[0] < stitched.shape[0]
+    got, stdout = star_dump(tmp_path, ["-O", option(RADIUS), "-K", option(STAT), "-M", option(STAR), "-E", option(CLUSTER), "-V", "100"]
+                            + (["-t"] if timer else []))
+    assert got.shape == want.shape and (got == want).all()
+    assert has_lines(stdout, lines) == timer
+    assert (f"Cluster filter: {stats['considered']} -> {stats['kept']} points" in stdout) == timer
+
+
+@retry_server_start
+def test_star_behind_the_radius_filter_in_front_of_the_cluster_filter(edge_payload, tmp_path):
+    stitched = np.concatenate([edge_payload, edge_payload])
+    first = NR.radius_outlier(stitched, *RADIUS)
+    second, lines = segmented(first, STAR)
+    want, _, stats = NC.cluster_filter(second, *CLUSTER)
+    assert 0 < want.shape[0] < second.shape[0]
+    got, stdout = star_dump(tmp_path, ["-O", option(RADIUS), "-M", option(STAR), "-E", option(CLUSTER), "-t"])
+    assert got.shape == want.shape and (got == want).all()
+    assert has_lines(stdout, lines), stdout
+
+
+@retry_server_start
+def test_star_in_front_of_the_voxel_grid_alone(edge_payload, oracle, tmp_path):
+    stitched = np.concatenate([edge_payload, edge_payload])
+    kept, lines = segmented(stitched, STAR)
+    want = oracle.voxel_grid(kept, 100)
+    got, stdout = star_dump(tmp_path, ["-M", option(STAR), "-V", "100", "-t"])
+    assert 0 < want.shape[0] < kept.shape[0] and got.shape == want.shape and (got == want).all()
+    assert has_lines(stdout, lines), stdout
+
+
+def local_payload():
+    cfgs, depth, color = S.synth_frame_set(3, 64, 48)
+    with PcsContext(cfgs, flags=FLAG_DROP_INVALID) as ctx:
+        buf, counts, size = ctx.process_frames(depth, color)
+    payload = buf[HEADER_SHORTS:HEADER_SHORTS + size // 2].reshape(-1, 5).copy()
+    assert 0 < payload.shape[0] < 3 * 64 * 48
+    return payload
+
+
+@pytest.mark.parametrize("leaf", [0, 100])
+def test_local_cameras_with_plane_segmentation(oracle, tmp_path, leaf):
+    """-i synth: -Z -M [-V]: the restatement applied to what pcs_process_frames_device writes for the same frames."""
+    kept, lines = segmented(local_payload(), LOCAL)
+    want = oracle.voxel_grid(kept, leaf) if leaf else kept
+    out = str(tmp_path / "dump.bin")
+    r = subprocess.run([CENTRAL, "-i", "synth:64x48", "-N", "3", "-Z", "-M", option(LOCAL), "-q", "-r", "1", "-t", "-o", out]
+                       + (["-V", str(leaf)] if leaf else []), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=150)
+    assert r.returncode == 0, r.stderr
+    got = dump(out)
+    assert got.shape == want.shape and (got == want).all()
+    assert has_lines(r.stdout, lines), r.stdout
+
+
+def test_local_cameras_between_the_statistical_filter_and_the_cluster_filter(oracle, tmp_path):
+    """-i synth: -Z -K -M -E: each stage takes the one in front of it by its device count."""
+    first, _, _ = NS.stat_outlier(local_payload(), 8, 1000, 300)
+    second, lines = segmented(first, LOCAL_BEHIND_STAT)
+    want, _, stats = NC.cluster_filter(second, *LOCAL_CLUSTER)
+    assert 0 < want.shape[0] < second.shape[0]
+    out = str(tmp_path / "dump.bin")
+    r = subprocess.run([CENTRAL, "-i", "synth:64x48", "-N", "3", "-Z", "-K", "8,1000,300", "-M", option(LOCAL_BEHIND_STAT), "-E", option(LOCAL_CLUSTER), "-q",
+                        "-r", "1", "-t", "-o", out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=150)
+    assert r.returncode == 0, r.stderr
+    got = dump(out)
+    assert got.shape == want.shape and (got == want).all()
+    assert has_lines(r.stdout, lines), r.stdout
+    assert f"Cluster filter: {stats['considered']} -> {stats['kept']} points" in r.stdout
