@@ -270,10 +270,14 @@ __device__ __forceinline__ void color_stretch(const StreamParams& P, const int32
 // bookkeeping, and waits for them itself: vmcnt(kWinPieces) before deprojection (everything but the window, naming the five
 // destinations so that nothing reads them earlier) and vmcnt(0) before the first read of the window.
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+// ONCE: bytes this lane alone reads, once per launch (its Z16 quad) are asked for nontemporal — they do not push the LUT and the colour
+// rows, which neighbouring waves read again, out of the caches' way.
+template <bool ONCE = false>
 __device__ __forceinline__ u32x4v load16_asm(const void* base, uint32_t off)
 {
     u32x4v v;
-    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(off), "s"(base));
+    if constexpr (ONCE) asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(v) : "v"(off), "s"(base));
+    else                asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v) : "v"(off), "s"(base));
     return v;
 }
 __device__ __forceinline__ uint32_t load4_asm(const void* base, uint32_t off)
@@ -324,7 +328,7 @@ __device__ __forceinline__ void dense_tile_rowc(const StreamParams& P, const uin
     const uint32_t ic = min(i0, n - kPointsPerLane);        // a lane past the stream's end reads its last quad; its records are not stored
     const uint32_t r = P.w_magic ? (__umulhi(ic, P.w_magic) >> P.w_shift) : ic / (uint32_t)P.W;
     const uint32_t c0 = ic - r * (uint32_t)P.W;
-    u32x4v dv = load16_asm(depth, ic * 2u);                 // what src.fetch() requests, in its order, then the colour row
+    u32x4v dv = load16_asm<true>(depth, ic * 2u);           // what src.fetch() requests, in its order, then the colour row
     u32x4v ma = load16_asm(P.mx, c0 * 4u);
     u32x4v mb = load16_asm(P.mx, c0 * 4u + 16u);
     uint32_t myb = load4_asm(P.my, r * 4u);
@@ -711,6 +715,7 @@ void pcs_fused_compact_kernel(const StreamParams* __restrict__ params, int strea
 
 template <bool DDIST, bool CDIST, class Mth, uint32_t THREADS = kBlockThreads>
 __global__ __launch_bounds__(THREADS, 7)     // <= 72 VGPRs for every instantiation (one landed on 73 -> 6 waves/SIMD); A/B on one box: no measurable change, 8 spills and is slower
+                                             // (the row-constant tile, 56 VGPRs, fits 8 once its constants take <= 80 SGPRs: measured slower too)
 void pcs_fused_dense_kernel(const StreamParams* __restrict__ params, int stream0, FramePtrs fp,
                             uint8_t* __restrict__ payload_bytes)
 {
