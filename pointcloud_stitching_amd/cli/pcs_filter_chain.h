@@ -1,0 +1,198 @@
+// pcs_filter_chain.h — the post-stitch filters of pcs-multicamera-optimized, -O -K -M -E in that order, as one chain ahead of -V.
+// Plain C++17 over include/pcs_hip.h. The rule every stage follows, stated once:
+//
+//   A stage reads the output of the stage in front of it. If that stage left its record count on the device, the counted form is
+//   called with that count word and max_points = the number of records that entered the chain; otherwise the plain form with the
+//   host's count. The stage writes its own output and its own count word. Nothing is copied to the host in between: whoever needs
+//   the last count fetches it once.
+//
+// Two output buffers alternate between the stages (stage k reads what stage k-1 wrote and writes the other one, so no call sees
+// overlapping input and output; the first stage's input belongs to the caller). Every enabled stage keeps a 64-byte count word and
+// its own statistics / model block, which report() reads after the frame-set's last launch.
+#pragma once
+
+#include <cstring>
+#include <ostream>
+#include <string>
+#include <vector>
+
+#include "pcs_cluster.h"
+#include "pcs_outlier.h"
+#include "pcs_plane.h"
+#include "pcs_statoutlier.h"
+
+namespace pcs_filter_chain {
+
+struct Cloud {
+    const int16_t* d;       // device: the records
+    const int32_t* d_n;     // device: their count, or nullptr when only the host knows it
+    int n;                  // the host's count (read only when d_n is nullptr)
+    int capacity;           // the records that entered the chain: max_points of every counted call
+};
+
+struct Params {
+    int radius_mm = 0, min_neighbors = 0;
+    pcs_stat_outlier_params stat{};
+    pcs_plane_params plane{};
+    pcs_cluster_params cluster{};
+};
+
+// -M's block: the statistics, then the models
+struct PlaneBlock {
+    pcs_plane_stats stats;
+    pcs_plane_model models[PCS_PLANE_MAX_PLANES];
+};
+
+struct Stage {
+    char letter;
+    const char* refusal;       // "-G: the node library has no <refusal>"
+    const char* (*help)();
+    bool (*parse)(const char* arg, Params& p, std::string& why);
+    size_t block_bytes;        // the statistics / model block on the device (0: none)
+    // the plain or the counted library entry, by whether `in` has a device count
+    int (*call)(pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void* d_block);
+    // the -t line(s): `block` is the host's copy, n_in / n_kept the counts in front of and behind the stage
+    void (*print)(std::ostream& os, const void* block, int n_in, int n_kept);
+};
+
+inline const Stage kStages[] = {
+    {'O', "outlier filter", pcs_outlier::help,
+     [](const char* arg, Params& p, std::string& why) { return pcs_outlier::parse(arg, p.radius_mm, p.min_neighbors, why); }, 0,
+     [](pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void*) {
+         return in.d_n ? pcs_radius_outlier_device_counted(ctx, in.d, in.d_n, in.capacity, p.radius_mm, p.min_neighbors, d_out, out_shorts, d_n_out)
+                       : pcs_radius_outlier_device(ctx, in.d, in.n, p.radius_mm, p.min_neighbors, d_out, out_shorts, d_n_out);
+     },
+     [](std::ostream& os, const void*, int n_in, int n_kept) { os << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl; }},
+    {'K', "outlier filter", pcs_statoutlier::help,
+     [](const char* arg, Params& p, std::string& why) { return pcs_statoutlier::parse(arg, p.stat, why); }, sizeof(pcs_stat_outlier_stats),
+     [](pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void* d_block) {
+         pcs_stat_outlier_stats* d_stats = static_cast<pcs_stat_outlier_stats*>(d_block);
+         return in.d_n ? pcs_stat_outlier_device_counted(ctx, in.d, in.d_n, in.capacity, &p.stat, d_out, out_shorts, d_n_out, d_stats)
+                       : pcs_stat_outlier_device(ctx, in.d, in.n, &p.stat, d_out, out_shorts, d_n_out, d_stats);
+     },
+     [](std::ostream& os, const void* block, int, int) {
+         pcs_stat_outlier_stats st;
+         memcpy(&st, block, sizeof st);
+         os << "Statistical outlier removal: " << st.considered << " -> " << st.kept << " points (dense " << st.dense << ", threshold "
+            << st.threshold << "/256 per k)" << std::endl;
+     }},
+    {'M', "plane segmentation", pcs_plane::help,
+     [](const char* arg, Params& p, std::string& why) { return pcs_plane::parse(arg, p.plane, why); }, sizeof(PlaneBlock),
+     [](pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void* d_block) {
+         PlaneBlock* b = static_cast<PlaneBlock*>(d_block);
+         return in.d_n ? pcs_plane_segment_device_counted(ctx, in.d, in.d_n, in.capacity, &p.plane, d_out, out_shorts, d_n_out, b->models, &b->stats)
+                       : pcs_plane_segment_device(ctx, in.d, in.n, &p.plane, d_out, out_shorts, d_n_out, b->models, &b->stats);
+     },
+     [](std::ostream& os, const void* block, int, int) {
+         PlaneBlock b;
+         memcpy(&b, block, sizeof b);
+         const pcs_plane_stats& st = b.stats;
+         os << "Plane segmentation: " << st.considered << " -> " << st.kept << " points (" << st.planes << " planes, " << st.inliers_total
+            << " inliers)" << std::endl;
+         for (int r = 0; r < (int)st.planes && r < PCS_PLANE_MAX_PLANES; r++)
+             os << "Plane " << r << ": " << b.models[r].inliers << " inliers, normal (" << b.models[r].nx << ", " << b.models[r].ny << ", "
+                << b.models[r].nz << "), offset " << b.models[r].off << ", hypothesis " << b.models[r].hypothesis << std::endl;
+     }},
+    {'E', "cluster filter", pcs_cluster::help,
+     [](const char* arg, Params& p, std::string& why) { return pcs_cluster::parse(arg, p.cluster, why); }, sizeof(pcs_cluster_stats),
+     [](pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void* d_block) {
+         pcs_cluster_stats* d_stats = static_cast<pcs_cluster_stats*>(d_block);
+         return in.d_n ? pcs_cluster_filter_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, d_out, out_shorts, d_n_out, d_stats)
+                       : pcs_cluster_filter_device(ctx, in.d, in.n, &p.cluster, d_out, out_shorts, d_n_out, d_stats);
+     },
+     [](std::ostream& os, const void* block, int, int) {
+         pcs_cluster_stats st;
+         memcpy(&st, block, sizeof st);
+         os << "Cluster filter: " << st.considered << " -> " << st.kept << " points (" << st.clusters << " clusters, " << st.kept_clusters
+            << " kept, largest " << st.largest << ")" << std::endl;
+     }},
+};
+constexpr int kStageCount = sizeof kStages / sizeof kStages[0];
+
+struct Chain {
+    Params params;
+    bool enabled[kStageCount] = {};
+    pcs_ctx* ctx = nullptr;
+    size_t out_shorts = 0;                 // what each of d_buf holds
+    void* d_buf[2] = {};
+    void* d_count[kStageCount] = {};
+    void* d_block[kStageCount] = {};
+    Cloud entered{};                       // what the last run() was given
+    int status = PCS_OK;                   // of the last run(): the first stage that failed ends it
+
+    bool any() const
+    {
+        for (bool e : enabled) if (e) return true;
+        return false;
+    }
+
+    // An option of the table's: its argument into the parameters, the stage switched on. false: `why` says what is wrong with it.
+    bool parse(int letter, const char* arg, std::string& why)
+    {
+        for (int s = 0; s < kStageCount; s++)
+            if (kStages[s].letter == letter) return enabled[s] = kStages[s].parse(arg, params, why);
+        return false;
+    }
+
+    // Buffers for clouds of up to out_shorts shorts: one per enabled stage, two at the most.
+    int allocate(pcs_ctx* c, size_t shorts)
+    {
+        ctx = c; out_shorts = shorts;
+        int n = 0, rc = PCS_OK;
+        for (int s = 0; s < kStageCount && rc == PCS_OK; s++) {
+            if (!enabled[s]) continue;
+            if (n < 2) rc = pcs_device_malloc(ctx, &d_buf[n++], out_shorts * sizeof(int16_t) + 64);
+            if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_count[s], 64);
+            if (rc == PCS_OK && kStages[s].block_bytes) rc = pcs_device_malloc(ctx, &d_block[s], kStages[s].block_bytes);
+        }
+        return rc;
+    }
+
+    // The enabled stages over `in`, launched in order; returns the last one's output (or `in`). Copies nothing to the host.
+    Cloud run(pcs_ctx* c, Cloud in)
+    {
+        entered = in; status = PCS_OK;
+        int k = 0;
+        for (int s = 0; s < kStageCount && status == PCS_OK; s++) {
+            if (!enabled[s]) continue;
+            int16_t* d_out = static_cast<int16_t*>(d_buf[k++ & 1]);
+            int32_t* d_n_out = static_cast<int32_t*>(d_count[s]);
+            status = kStages[s].call(c, params, in, d_out, out_shorts, d_n_out, d_block[s]);
+            in = Cloud{d_out, d_n_out, 0, in.capacity};
+        }
+        return in;
+    }
+
+    // The -t lines of the last run(), in stage order. false: a copy failed (pcs_last_error has it).
+    bool report(std::ostream& os) const
+    {
+        if (!any()) return true;
+        int32_t n[kStageCount + 1] = {entered.n};
+        std::vector<char> block[kStageCount];
+        bool ok = !entered.d_n || pcs_memcpy_d2h(ctx, &n[0], entered.d_n, sizeof n[0]) == PCS_OK;
+        for (int s = 0; s < kStageCount && ok; s++) {
+            if (!enabled[s]) continue;
+            block[s].resize(kStages[s].block_bytes);
+            ok = pcs_memcpy_d2h(ctx, &n[s + 1], d_count[s], sizeof n[0]) == PCS_OK &&
+                 (block[s].empty() || pcs_memcpy_d2h(ctx, block[s].data(), d_block[s], block[s].size()) == PCS_OK);
+        }
+        if (!ok || pcs_synchronize(ctx) != PCS_OK) return false;
+        int n_in = n[0];
+        for (int s = 0; s < kStageCount; s++) {
+            if (!enabled[s]) continue;
+            kStages[s].print(os, block[s].data(), n_in, n[s + 1]);
+            n_in = n[s + 1];
+        }
+        return true;
+    }
+
+    void release()
+    {
+        auto drop = [this](void*& p) { if (p) pcs_device_free(ctx, p); p = nullptr; };
+        for (void*& p : d_buf) drop(p);
+        for (void*& p : d_count) drop(p);
+        for (void*& p : d_block) drop(p);
+    }
+};
+
+}  // namespace pcs_filter_chain

@@ -40,35 +40,31 @@
 //                      on the host and decoded on the GPU into the camera's device payload (pcs_decompress_payload) ahead of the
 //                      stitch / -T / -B / -V paths, which see what they always saw; a frame that fails validation ends the run with
 //                      the validator's message. What is served on -p stays raw.
+//              -O -K -M -E  the post-stitch filters, one chain (pcs_filter_chain.h) in that fixed order, after -T and -B / -d, before -V. A
+//                      stage reads the output of the stage in front of it: through the counted form, with that stage's count word,
+//                      wherever the count is on the device (every -i payload, every stage behind another), else through the plain
+//                      form with the host's count. No count leaves the device in between; the last one is fetched only when no -V
+//                      reads it there (pcs_voxel_grid_device_counted). With -c the chain runs on the stitched device payload; with -i
+//                      the payload is built on the device (pcs_process_frames_device). -t prints each stage's line(s) per frame-set,
+//                      in stage order. None with -G: the node library has no such filters.
 //              -O <radius_mm,min_neighbors>  radius outlier removal on the stitched cloud (pcs_radius_outlier_device: a record stays iff
-//                      at least min_neighbors others lie within radius_mm of it): after -T and -B / -d, before -V. With -c it runs on
-//                      the stitched device payload (with -V its output and device count feed pcs_voxel_grid_device_counted); with -i
-//                      the payload is built on the device (pcs_process_frames_device), filtered by the counted form, then voxelised
-//                      or copied out. -t prints `Outlier removal: <in> -> <kept> points` per frame-set. Not with -G: the node library
-//                      has no such filter. The filter knows nothing of invalid depth: with -i give -Z (or -B).
+//                      at least min_neighbors others lie within radius_mm of it). -t prints `Outlier removal: <in> -> <kept> points`.
+//                      The filter knows nothing of invalid depth: with -i give -Z (or -B).
 //              -K <mean_k,std_mul_milli,max_dist_mm>  statistical outlier removal on the stitched cloud (pcs_stat_outlier_device: a
 //                      record stays iff it has mean_k others within max_dist_mm and the summed distance to the nearest mean_k is at
-//                      most the cloud's mean + std_mul_milli / 1000 deviations): after -T, -B / -d and -O, before -V. With -c it
-//                      runs on the stitched device payload, or on -O's output and device count through the counted form; with -i
-//                      on the device payload's count, or -O's; with -V its output and device count feed
-//                      pcs_voxel_grid_device_counted. -t prints `Statistical outlier removal: <in> -> <kept> points (dense <M>,
-//                      threshold <T>/256 per k)` per frame-set. Not with -G: the node library has no such filter. Zero-depth pixels
-//                      sit on one point and drag the mean down: with -i give -Z (or -B).
+//                      most the cloud's mean + std_mul_milli / 1000 deviations). -t prints `Statistical outlier removal: <in> ->
+//                      <kept> points (dense <M>, threshold <T>/256 per k)`. Zero-depth pixels sit on one point and drag the mean
+//                      down: with -i give -Z (or -B).
 //              -M <distance_mm,iterations[,min_inliers[,max_planes[,seed]]]>  plane segmentation on the stitched cloud
 //                      (pcs_plane_segment_device, mode 0: up to max_planes rounds, each takes the plane through three drawn records that
 //                      has the most records within distance_mm, out of `iterations` such planes, out of the cloud while it has
-//                      min_inliers records; defaults 3, 1 and seed 1): after -T, -B / -d, -O and -K, before -E and -V. It takes the
-//                      stage in front of it through the counted form wherever that stage left a device count, and its output and
-//                      device count feed -E or -V the same way. -t prints `Plane segmentation: <in> -> <kept> points (<planes>
+//                      min_inliers records; defaults 3, 1 and seed 1). -t prints `Plane segmentation: <in> -> <kept> points (<planes>
 //                      planes, <inliers> inliers)` and one line `Plane <r>: <inliers> inliers, normal (<nx>, <ny>, <nz>), offset <off>,
-//                      hypothesis <h>` per accepted plane and frame-set. Not with -G: the node library has no such filter.
+//                      hypothesis <h>` per accepted plane.
 //              -E <tolerance_mm,min_size[,max_size]>  Euclidean cluster filter on the stitched cloud (pcs_cluster_filter_device: records
 //                      within tolerance_mm of each other are connected; a record stays iff its connected component holds min_size to
-//                      max_size records, max_size 0 or absent: no upper bound): after -T, -B / -d, -O and -K, before -V. It takes
-//                      the stage in front of it through the counted form wherever that stage left a device count (-O, -K, and
-//                      every -i payload); with -V its output and device count feed pcs_voxel_grid_device_counted. -t prints
-//                      `Cluster filter: <in> -> <kept> points (<clusters> clusters, <kept_clusters> kept, largest <largest>)` per
-//                      frame-set. Not with -G: the node library has no such filter. Zero-depth pixels form one huge cluster on
+//                      max_size records, max_size 0 or absent: no upper bound). -t prints `Cluster filter: <in> -> <kept> points
+//                      (<clusters> clusters, <kept_clusters> kept, largest <largest>)`. Zero-depth pixels form one huge cluster on
 //                      their camera's origin: with -i give -Z (or -B).
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
@@ -84,11 +80,8 @@
 #include <getopt.h>
 #include <signal.h>
 
-#include "pcs_cluster.h"
 #include "pcs_cropbox.h"
-#include "pcs_outlier.h"
-#include "pcs_plane.h"
-#include "pcs_statoutlier.h"
+#include "pcs_filter_chain.h"
 #include "pcs_synth.h"
 #include "pcs_wire.h"
 #include "../../include/pcs_node.h"
@@ -107,17 +100,13 @@ static const char* dump_path = nullptr;
 static const char* transform_path = nullptr;
 static bool crop = false;
 static int16_t crop_lo[3], crop_hi[3];
-static bool outlier = false;
-static int outlier_radius = 0, outlier_neighbors = 0;
-static bool statout = false;
-static pcs_stat_outlier_params statout_params{};
-static bool plane = false;
-static pcs_plane_params plane_params{};
-static bool cluster = false;
-static pcs_cluster_params cluster_params{};
+static pcs_filter_chain::Chain chain;      // -O -K -M -E
+using pcs_filter_chain::Cloud;
 
 static void usage()
 {
+    std::string filters;
+    for (const auto& stage : pcs_filter_chain::kStages) filters += stage.help();
     std::cout << "\nMulticamera pointcloud stitching (MI355X)\nUsage: pcs-multicamera-optimized [options]\n\nOptions:\n"
               << " -h (help)        Display command line options\n"
               << " -f (fast)        Accepted for compatibility (it thinned the reference's PCL viewer); no effect\n"
@@ -135,13 +124,7 @@ static void usage()
               << "                  as the reference's pcs-multicamera-optimized does (decode, pcl::transformPointCloud, re-encode)\n"
               << " -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box, millimetres in the world frame, inclusive: -i crops in the fused path, -c crops the\n"
               << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
-              << " -O <radius_mm,min_neighbors>  radius outlier removal on the stitched cloud: a record stays iff at least min_neighbors\n"
-              << "                  others lie within radius_mm (1..1000, 1..255); after -T and -B / -d, before -V; not with -G\n"
-              << " -K <mean_k,std_mul_milli,max_dist_mm>  statistical outlier removal on the stitched cloud: a record stays iff it has mean_k\n"
-              << "                  others within max_dist_mm (1..64, 1..1000) and its summed distance to the nearest mean_k is at most the\n"
-              << "                  cloud's mean + std_mul_milli / 1000 (0..10000) deviations; after -T, -B / -d and -O, before -V; not with -G\n"
-              << pcs_plane::help()
-              << pcs_cluster::help()
+              << filters
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
@@ -187,28 +170,9 @@ int main(int argc, char** argv)
                 crop = true;
                 break;
             }
-            case 'O': {
+            case 'O': case 'K': case 'M': case 'E': {
                 std::string why;
-                if (!pcs_outlier::parse(optarg, outlier_radius, outlier_neighbors, why)) { std::cerr << "-O " << optarg << ": " << why << std::endl; return 2; }
-                outlier = true;
-                break;
-            }
-            case 'K': {
-                std::string why;
-                if (!pcs_statoutlier::parse(optarg, statout_params, why)) { std::cerr << "-K " << optarg << ": " << why << std::endl; return 2; }
-                statout = true;
-                break;
-            }
-            case 'M': {
-                std::string why;
-                if (!pcs_plane::parse(optarg, plane_params, why)) { std::cerr << "-M " << optarg << ": " << why << std::endl; return 2; }
-                plane = true;
-                break;
-            }
-            case 'E': {
-                std::string why;
-                if (!pcs_cluster::parse(optarg, cluster_params, why)) { std::cerr << "-E " << optarg << ": " << why << std::endl; return 2; }
-                cluster = true;
+                if (!chain.parse(c, optarg, why)) { std::cerr << "-" << (char)c << " " << optarg << ": " << why << std::endl; return 2; }
                 break;
             }
             case 's': case 'v': case 'n':
@@ -219,10 +183,11 @@ int main(int argc, char** argv)
     }
     if (downsample < 1) { std::cerr << "downsample must be >= 1" << std::endl; return 2; }
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
-    if (outlier && n_gpus > 0) { std::cerr << "-O is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
-    if (statout && n_gpus > 0) { std::cerr << "-K is not available with -G: the node library has no outlier filter" << std::endl; return 2; }
-    if (plane && n_gpus > 0) { std::cerr << "-M is not available with -G: the node library has no plane segmentation" << std::endl; return 2; }
-    if (cluster && n_gpus > 0) { std::cerr << "-E is not available with -G: the node library has no cluster filter" << std::endl; return 2; }
+    for (int k = 0; k < pcs_filter_chain::kStageCount; k++)
+        if (chain.enabled[k] && n_gpus > 0) {
+            const auto& stage = pcs_filter_chain::kStages[k];
+            std::cerr << "-" << stage.letter << " is not available with -G: the node library has no " << stage.refusal << std::endl; return 2;
+        }
     if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
     if (!source && !cameras) source = "synth:1280x720";      // no live cameras on this node: the synthetic generator
@@ -360,82 +325,17 @@ int main(int argc, char** argv)
         if (pcs_device_malloc(ctx, &d_cropped, (size_t)n_streams * cam_cap_bytes + 64) != PCS_OK ||
             pcs_device_malloc(ctx, &d_crop_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
-    // -B with -i -V: the cropped payload and its counts stay on the device between the two calls
+    // -B with -i -V, and the chain with -i: the payload and its counts stay on the device between the calls
     void *d_pay = nullptr, *d_pay_counts = nullptr;
-    if (source && ((crop && voxel_leaf) || outlier || statout || plane || cluster)) {
+    if (source && ((crop && voxel_leaf) || chain.any())) {
         if (pcs_device_malloc(ctx, &d_pay, pcs_max_payload_shorts(ctx) * sizeof(int16_t) + 64) != PCS_OK ||
             pcs_device_malloc(ctx, &d_pay_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
 
-    // -O: the filtered payload and its count stay on the device (-V reads both there)
-    void *d_filtered = nullptr, *d_nfiltered = nullptr;
-    if (outlier) {
-        const size_t bytes = source ? pcs_max_payload_shorts(ctx) * sizeof(int16_t) : (size_t)n_streams * cam_cap_bytes;
-        if (pcs_device_malloc(ctx, &d_filtered, bytes + 64) != PCS_OK || pcs_device_malloc(ctx, &d_nfiltered, 64) != PCS_OK) {
-            std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-        }
+    // -O -K -M -E: the chain's buffers hold the largest cloud that can enter it
+    if (chain.any() && chain.allocate(ctx, source ? pcs_max_payload_shorts(ctx) : (size_t)n_streams * cam_cap_bytes / 2) != PCS_OK) {
+        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
     }
-
-    // -K: the same, and the statistics block for -t
-    void *d_stat = nullptr, *d_nstat = nullptr, *d_stat_block = nullptr;
-    if (statout) {
-        const size_t bytes = source ? pcs_max_payload_shorts(ctx) * sizeof(int16_t) : (size_t)n_streams * cam_cap_bytes;
-        if (pcs_device_malloc(ctx, &d_stat, bytes + 64) != PCS_OK || pcs_device_malloc(ctx, &d_nstat, 64) != PCS_OK ||
-            pcs_device_malloc(ctx, &d_stat_block, sizeof(pcs_stat_outlier_stats)) != PCS_OK) {
-            std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-        }
-    }
-    // what -t prints for -K: the block's numbers, after the frame-set's last launch
-    auto print_statout = [&]() {
-        pcs_stat_outlier_stats st{};
-        if (pcs_memcpy_d2h(ctx, &st, d_stat_block, sizeof st) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
-        std::cout << "Statistical outlier removal: " << st.considered << " -> " << st.kept << " points (dense " << st.dense << ", threshold "
-                  << st.threshold << "/256 per k)" << std::endl;
-        return true;
-    };
-
-    // -M: the same, and the model blocks
-    void *d_pl = nullptr, *d_npl = nullptr, *d_pl_block = nullptr, *d_pl_models = nullptr;
-    if (plane) {
-        const size_t bytes = source ? pcs_max_payload_shorts(ctx) * sizeof(int16_t) : (size_t)n_streams * cam_cap_bytes;
-        if (pcs_device_malloc(ctx, &d_pl, bytes + 64) != PCS_OK || pcs_device_malloc(ctx, &d_npl, 64) != PCS_OK ||
-            pcs_device_malloc(ctx, &d_pl_block, sizeof(pcs_plane_stats)) != PCS_OK ||
-            pcs_device_malloc(ctx, &d_pl_models, sizeof(pcs_plane_model) * PCS_PLANE_MAX_PLANES) != PCS_OK) {
-            std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-        }
-    }
-    // what -t prints for -M: the block's numbers and the accepted planes, after the frame-set's last launch
-    auto print_plane = [&]() {
-        pcs_plane_stats st{};
-        pcs_plane_model models[PCS_PLANE_MAX_PLANES] = {};
-        if (pcs_memcpy_d2h(ctx, &st, d_pl_block, sizeof st) != PCS_OK ||
-            pcs_memcpy_d2h(ctx, models, d_pl_models, sizeof(pcs_plane_model) * (size_t)plane_params.max_planes) != PCS_OK ||
-            pcs_synchronize(ctx) != PCS_OK) return false;
-        std::cout << "Plane segmentation: " << st.considered << " -> " << st.kept << " points (" << st.planes << " planes, " << st.inliers_total
-                  << " inliers)" << std::endl;
-        for (int r = 0; r < (int)st.planes && r < PCS_PLANE_MAX_PLANES; r++)
-            std::cout << "Plane " << r << ": " << models[r].inliers << " inliers, normal (" << models[r].nx << ", " << models[r].ny << ", "
-                      << models[r].nz << "), offset " << models[r].off << ", hypothesis " << models[r].hypothesis << std::endl;
-        return true;
-    };
-
-    // -E: the same
-    void *d_clu = nullptr, *d_nclu = nullptr, *d_clu_block = nullptr;
-    if (cluster) {
-        const size_t bytes = source ? pcs_max_payload_shorts(ctx) * sizeof(int16_t) : (size_t)n_streams * cam_cap_bytes;
-        if (pcs_device_malloc(ctx, &d_clu, bytes + 64) != PCS_OK || pcs_device_malloc(ctx, &d_nclu, 64) != PCS_OK ||
-            pcs_device_malloc(ctx, &d_clu_block, sizeof(pcs_cluster_stats)) != PCS_OK) {
-            std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-        }
-    }
-    // what -t prints for -E: the block's numbers, after the frame-set's last launch
-    auto print_cluster = [&]() {
-        pcs_cluster_stats st{};
-        if (pcs_memcpy_d2h(ctx, &st, d_clu_block, sizeof st) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
-        std::cout << "Cluster filter: " << st.considered << " -> " << st.kept << " points (" << st.clusters << " clusters, " << st.kept_clusters
-                  << " kept, largest " << st.largest << ")" << std::endl;
-        return true;
-    };
 
     // -V: device-resident rasters (with -i) and the voxel cloud
     std::vector<void*> d_depth, d_color;
@@ -451,7 +351,7 @@ int main(int argc, char** argv)
                       pcs_device_malloc(ctx, &d_nvox, 64) != PCS_OK)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
         if (!stitched.resize(PCS_HEADER_SHORTS + vox_cap_points * PCS_POINT_SHORTS)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
-    if ((voxel_leaf || outlier || statout || plane || cluster) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
+    if ((voxel_leaf || chain.any()) && source && !node) {      // (with -G the node library stages the rasters on their owning GPUs itself)
         d_depth.resize(n_streams, nullptr); d_color.resize(n_streams, nullptr);
         for (int s = 0; s < n_streams; s++) {
             const size_t db = (size_t)cfgs[s].depth.width * cfgs[s].depth.height * 2;
@@ -477,6 +377,34 @@ int main(int argc, char** argv)
         if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, d_vox, (size_t)size_bytes) != PCS_OK) return false;
         if (pcs_synchronize(ctx) != PCS_OK) return false;
         memcpy(stitched.data(), &size_bytes, sizeof(int));
+        return true;
+    };
+
+    // -O -K -M -E over `in`, then what is served -> stitched: with -V the voxel grid of the chain's output, on its device count where
+    // it has one; else the records themselves, their count fetched once. Then the chain's -t lines, after the frame-set's last launch.
+    // (`again` of fetch_voxels repeats the voxel call alone.)
+    auto filter_to_stitched = [&](const Cloud& in) -> bool {
+        const Cloud c = chain.run(ctx, in);
+        if (chain.status != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return false; }
+        if (voxel_leaf) {
+            auto run_voxel = [&]() {
+                int16_t* out = static_cast<int16_t*>(d_vox);
+                const size_t out_shorts = vox_cap_points * PCS_POINT_SHORTS;
+                return c.d_n ? pcs_voxel_grid_device_counted(ctx, c.d, c.d_n, c.capacity, voxel_leaf, out, out_shorts, static_cast<int32_t*>(d_nvox))
+                             : pcs_voxel_grid_device(ctx, c.d, c.n, voxel_leaf, out, out_shorts, static_cast<int32_t*>(d_nvox));
+            };
+            if (run_voxel() != PCS_OK || !fetch_voxels(run_voxel)) { std::cerr << pcs_last_error(ctx) << std::endl; return false; }
+        } else {
+            int32_t n = c.n;
+            if (c.d_n && (pcs_memcpy_d2h(ctx, &n, c.d_n, sizeof n) != PCS_OK || pcs_synchronize(ctx) != PCS_OK)) {
+                std::cerr << pcs_last_error(ctx) << std::endl; return false;
+            }
+            size_bytes = n * PCS_POINT_BYTES;
+            if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, c.d, (size_t)size_bytes) != PCS_OK) return false;
+            pcs_synchronize(ctx);
+            memcpy(stitched.data(), &size_bytes, sizeof(int));                                             // :394-395
+        }
+        if (timer && !chain.report(std::cout)) { std::cerr << pcs_last_error(ctx) << std::endl; return false; }
         return true;
     };
 
@@ -629,68 +557,20 @@ int main(int argc, char** argv)
                     std::cout << "Voxel grid over " << n_gpus << " GPU(s): kernels " << vstats.kernels_ms << " ms, exchange " << vstats.exchange_ms
                               << " ms (" << vstats.exchanged_bytes << " B), root " << vstats.root_voxel_ms << " ms, " << vstats.partials
                               << (voxel_route == PCS_NODE_VOXEL_PARTIALS ? " partials -> " : " points -> ") << vstats.voxels << " voxels" << std::endl;
-            } else if (outlier || statout || plane || cluster) {
-                // the payload on the device (under -Z / -B / -d as ever), the filter on its device count, then the voxel grid on the
-                // filter's device count or the kept records out: no count leaves the device in between
+            } else if (chain.any()) {
+                // the payload on the device (under -Z / -B / -d as ever), the chain on its device count, then the voxel grid on the
+                // chain's device count or the kept records out: no count leaves the device in between
                 for (int s = 0; s < n_streams; s++) {
                     if (pcs_memcpy_h2d(ctx, d_depth[s], depth[s].data(), depth[s].size() * 2) != PCS_OK ||
                         pcs_memcpy_h2d(ctx, d_color[s], color[s].data(), color[s].size()) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
                 }
                 const size_t max_shorts = pcs_max_payload_shorts(ctx);
-                const int max_points = (int)(max_shorts / PCS_POINT_SHORTS);
-                const int32_t* d_total = static_cast<const int32_t*>(d_pay_counts) + n_streams;
                 rc = pcs_process_frames_device(ctx, reinterpret_cast<const uint16_t* const*>(d_depth.data()),
                                                reinterpret_cast<const uint8_t* const*>(d_color.data()), static_cast<int16_t*>(d_pay), max_shorts,
                                                static_cast<int32_t*>(d_pay_counts));
-                // (the last filter's output and device count: what the next stage reads)
-                const int16_t* d_last = static_cast<const int16_t*>(d_pay);
-                const int32_t* d_nlast = d_total;
-                if (rc == PCS_OK && outlier) {
-                    rc = pcs_radius_outlier_device_counted(ctx, d_last, d_nlast, max_points, outlier_radius, outlier_neighbors,
-                                                           static_cast<int16_t*>(d_filtered), max_shorts, static_cast<int32_t*>(d_nfiltered));
-                    d_last = static_cast<const int16_t*>(d_filtered); d_nlast = static_cast<const int32_t*>(d_nfiltered);
-                }
-                if (rc == PCS_OK && statout) {
-                    rc = pcs_stat_outlier_device_counted(ctx, d_last, d_nlast, max_points, &statout_params, static_cast<int16_t*>(d_stat), max_shorts,
-                                                         static_cast<int32_t*>(d_nstat), static_cast<pcs_stat_outlier_stats*>(d_stat_block));
-                    d_last = static_cast<const int16_t*>(d_stat); d_nlast = static_cast<const int32_t*>(d_nstat);
-                }
-                if (rc == PCS_OK && plane) {
-                    rc = pcs_plane_segment_device_counted(ctx, d_last, d_nlast, max_points, &plane_params, static_cast<int16_t*>(d_pl), max_shorts,
-                                                          static_cast<int32_t*>(d_npl), static_cast<pcs_plane_model*>(d_pl_models),
-                                                          static_cast<pcs_plane_stats*>(d_pl_block));
-                    d_last = static_cast<const int16_t*>(d_pl); d_nlast = static_cast<const int32_t*>(d_npl);
-                }
-                if (rc == PCS_OK && cluster) {
-                    rc = pcs_cluster_filter_device_counted(ctx, d_last, d_nlast, max_points, &cluster_params, static_cast<int16_t*>(d_clu), max_shorts,
-                                                           static_cast<int32_t*>(d_nclu), static_cast<pcs_cluster_stats*>(d_clu_block));
-                    d_last = static_cast<const int16_t*>(d_clu); d_nlast = static_cast<const int32_t*>(d_nclu);
-                }
                 if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                if (voxel_leaf) {
-                    auto run_voxel = [&]() {
-                        return pcs_voxel_grid_device_counted(ctx, d_last, d_nlast,
-                                                             max_points, voxel_leaf, static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS,
-                                                             static_cast<int32_t*>(d_nvox));
-                    };
-                    rc = run_voxel();
-                    if (rc != PCS_OK || !fetch_voxels(run_voxel)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                }
-                int32_t n_in = 0, n_kept = 0, n_last = 0;
-                if (pcs_memcpy_d2h(ctx, &n_in, d_total, sizeof n_in) != PCS_OK ||
-                    (outlier && pcs_memcpy_d2h(ctx, &n_kept, d_nfiltered, sizeof n_kept) != PCS_OK) ||
-                    pcs_memcpy_d2h(ctx, &n_last, d_nlast, sizeof n_last) != PCS_OK ||
-                    pcs_synchronize(ctx) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                if (!voxel_leaf) {
-                    size_bytes = n_last * PCS_POINT_BYTES;
-                    if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, d_last, (size_t)size_bytes) != PCS_OK) return 1;
-                    pcs_synchronize(ctx);
-                    memcpy(stitched.data(), &size_bytes, sizeof(int));
-                }
-                if (timer && outlier) std::cout << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl;
-                if (timer && statout && !print_statout()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                if (timer && plane && !print_plane()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                if (timer && cluster && !print_cluster()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
+                if (!filter_to_stitched({static_cast<const int16_t*>(d_pay), static_cast<const int32_t*>(d_pay_counts) + n_streams, 0,
+                                         (int)(max_shorts / PCS_POINT_SHORTS)})) return 1;
             } else if (voxel_leaf) {
                 for (int s = 0; s < n_streams; s++) {
                     if (pcs_memcpy_h2d(ctx, d_depth[s], depth[s].data(), depth[s].size() * 2) != PCS_OK ||
@@ -775,107 +655,7 @@ int main(int argc, char** argv)
             rc = pcs_stitch_device(ctx, dptr.data(), pts.data(), n_streams, downsample, static_cast<int16_t*>(d_stitched),
                                    (size_t)n_streams * cam_cap_bytes / 2, &total_pts);
             if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-            const int outlier_in = total_pts;
-            if (outlier) {
-                rc = pcs_radius_outlier_device(ctx, d_result, total_pts, outlier_radius, outlier_neighbors, static_cast<int16_t*>(d_filtered),
-                                               (size_t)n_streams * cam_cap_bytes / 2, static_cast<int32_t*>(d_nfiltered));
-                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                d_result = static_cast<const int16_t*>(d_filtered);
-                if (!voxel_leaf || timer) {      // (with -V the voxel grid reads the count where it is)
-                    int32_t kept = 0;
-                    if (pcs_memcpy_d2h(ctx, &kept, d_nfiltered, sizeof kept) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) {
-                        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-                    }
-                    if (timer) std::cout << "Outlier removal: " << outlier_in << " -> " << kept << " points" << std::endl;
-                    if (!voxel_leaf) total_pts = kept;
-                }
-            }
-            if (statout) {
-                // behind -O: its output and its device count, through the counted form; else the stitched payload and its host count
-                const size_t out_shorts = (size_t)n_streams * cam_cap_bytes / 2;
-                rc = outlier ? pcs_stat_outlier_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nfiltered), outlier_in, &statout_params,
-                                                               static_cast<int16_t*>(d_stat), out_shorts, static_cast<int32_t*>(d_nstat),
-                                                               static_cast<pcs_stat_outlier_stats*>(d_stat_block))
-                             : pcs_stat_outlier_device(ctx, d_result, total_pts, &statout_params, static_cast<int16_t*>(d_stat), out_shorts,
-                                                       static_cast<int32_t*>(d_nstat), static_cast<pcs_stat_outlier_stats*>(d_stat_block));
-                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                d_result = static_cast<const int16_t*>(d_stat);
-                if (!voxel_leaf) {      // (with -V the voxel grid reads the count where it is)
-                    int32_t kept = 0;
-                    if (pcs_memcpy_d2h(ctx, &kept, d_nstat, sizeof kept) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) {
-                        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-                    }
-                    total_pts = kept;
-                }
-                if (timer && !print_statout()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-            }
-            if (plane) {
-                // behind -O or -K: that filter's output and device count, through the counted form; else the stitched payload and
-                // its host count
-                const size_t out_shorts = (size_t)n_streams * cam_cap_bytes / 2;
-                const int32_t* d_nprev = static_cast<const int32_t*>(statout ? d_nstat : outlier ? d_nfiltered : nullptr);
-                rc = d_nprev ? pcs_plane_segment_device_counted(ctx, d_result, d_nprev, outlier_in, &plane_params, static_cast<int16_t*>(d_pl),
-                                                                out_shorts, static_cast<int32_t*>(d_npl), static_cast<pcs_plane_model*>(d_pl_models),
-                                                                static_cast<pcs_plane_stats*>(d_pl_block))
-                             : pcs_plane_segment_device(ctx, d_result, total_pts, &plane_params, static_cast<int16_t*>(d_pl), out_shorts,
-                                                        static_cast<int32_t*>(d_npl), static_cast<pcs_plane_model*>(d_pl_models),
-                                                        static_cast<pcs_plane_stats*>(d_pl_block));
-                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                d_result = static_cast<const int16_t*>(d_pl);
-                if (!voxel_leaf && !cluster) {      // (behind it -E and -V read the count where it is)
-                    int32_t kept = 0;
-                    if (pcs_memcpy_d2h(ctx, &kept, d_npl, sizeof kept) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) {
-                        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-                    }
-                    total_pts = kept;
-                }
-                if (timer && !print_plane()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-            }
-            if (cluster) {
-                // behind -O, -K or -M: that filter's output and device count, through the counted form; else the stitched payload and
-                // its host count
-                const size_t out_shorts = (size_t)n_streams * cam_cap_bytes / 2;
-                const int32_t* d_nprev = static_cast<const int32_t*>(plane ? d_npl : statout ? d_nstat : outlier ? d_nfiltered : nullptr);
-                rc = d_nprev ? pcs_cluster_filter_device_counted(ctx, d_result, d_nprev, outlier_in, &cluster_params, static_cast<int16_t*>(d_clu),
-                                                                 out_shorts, static_cast<int32_t*>(d_nclu), static_cast<pcs_cluster_stats*>(d_clu_block))
-                             : pcs_cluster_filter_device(ctx, d_result, total_pts, &cluster_params, static_cast<int16_t*>(d_clu), out_shorts,
-                                                         static_cast<int32_t*>(d_nclu), static_cast<pcs_cluster_stats*>(d_clu_block));
-                if (rc != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-                d_result = static_cast<const int16_t*>(d_clu);
-                if (!voxel_leaf) {      // (with -V the voxel grid reads the count where it is)
-                    int32_t kept = 0;
-                    if (pcs_memcpy_d2h(ctx, &kept, d_nclu, sizeof kept) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) {
-                        std::cerr << pcs_last_error(ctx) << std::endl; return 1;
-                    }
-                    total_pts = kept;
-                }
-                if (timer && !print_cluster()) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-            }
-            if (voxel_leaf) {
-                auto run_voxel = [&]() {
-                    if (cluster)
-                        return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nclu), outlier_in, voxel_leaf,
-                                                             static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
-                    if (plane)
-                        return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_npl), outlier_in, voxel_leaf,
-                                                             static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
-                    if (statout)
-                        return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nstat), outlier_in, voxel_leaf,
-                                                             static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
-                    if (outlier)
-                        return pcs_voxel_grid_device_counted(ctx, d_result, static_cast<const int32_t*>(d_nfiltered), outlier_in, voxel_leaf,
-                                                             static_cast<int16_t*>(d_vox), vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
-                    return pcs_voxel_grid_device(ctx, d_result, total_pts, voxel_leaf, static_cast<int16_t*>(d_vox),
-                                                 vox_cap_points * PCS_POINT_SHORTS, static_cast<int32_t*>(d_nvox));
-                };
-                rc = run_voxel();
-                if (rc != PCS_OK || !fetch_voxels(run_voxel)) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
-            } else {
-                size_bytes = total_pts * PCS_POINT_BYTES;
-                if (size_bytes && pcs_memcpy_d2h(ctx, stitched.data() + PCS_HEADER_SHORTS, d_result, (size_t)size_bytes) != PCS_OK) return 1;
-                pcs_synchronize(ctx);
-                memcpy(stitched.data(), &size_bytes, sizeof(int));                                         // :394-395
-            }
+            if (!filter_to_stitched({d_result, nullptr, total_pts, total_pts})) return 1;
         }
         if (serve) {
             int req = pcs_wire::recv_pull(client_fd);                                                      // :398
@@ -904,7 +684,8 @@ int main(int argc, char** argv)
     if (d_vox) pcs_device_free(ctx, d_vox);
     if (d_nvox) pcs_device_free(ctx, d_nvox);
     if (d_stitched) pcs_device_free(ctx, d_stitched);
-    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts, d_filtered, d_nfiltered, d_stat, d_nstat, d_stat_block, d_clu, d_nclu, d_clu_block, d_pl, d_npl, d_pl_block, d_pl_models}) if (p) pcs_device_free(ctx, p);
+    for (void* p : {d_cropped, d_crop_counts, d_pay, d_pay_counts}) if (p) pcs_device_free(ctx, p);
+    chain.release();
     if (node) pcs_node_destroy(node);
     stitched.release();
     pcs_destroy(ctx);

@@ -10,6 +10,12 @@
 
 namespace pcs_outlier {
 
+inline const char* help()
+{
+    return " -O <radius_mm,min_neighbors>  radius outlier removal on the stitched cloud: a record stays iff at least min_neighbors\n"
+           "                  others lie within radius_mm (1..1000, 1..255); after -T and -B / -d, before -V; not with -G\n";
+}
+
 // Exactly two integers separated by a comma, each inside the library's range. On failure `why` says what is wrong.
 inline bool parse(const char* arg, int& radius_mm, int& min_neighbors, std::string& why)
 {

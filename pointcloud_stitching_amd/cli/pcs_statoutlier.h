@@ -10,6 +10,13 @@
 
 namespace pcs_statoutlier {
 
+inline const char* help()
+{
+    return " -K <mean_k,std_mul_milli,max_dist_mm>  statistical outlier removal on the stitched cloud: a record stays iff it has mean_k\n"
+           "                  others within max_dist_mm (1..64, 1..1000) and its summed distance to the nearest mean_k is at most the\n"
+           "                  cloud's mean + std_mul_milli / 1000 (0..10000) deviations; after -T, -B / -d and -O, before -V; not with -G\n";
+}
+
 // Exactly three integers separated by commas, each inside the library's range. On failure `why` says what is wrong.
 inline bool parse(const char* arg, pcs_stat_outlier_params& params, std::string& why)
 {

@@ -1,7 +1,8 @@
 """-M (plane segmentation) of pcs-multicamera-optimized, end to end on the GPU: two edge servers on loopback into the centre with -M
 (alone, behind -O and -K, in front of -E and -V), the cameras of the node itself with -i -Z -M, each against the brute-force
 restatement (tests/np_planes.py) of what the stage in front of it produced — that stage restated by the existing numpy restatements
-— the -t lines against the restatement's statistics and models, and without -M the dump of today. (The flag surface needs no GPU:
+— the -t lines against the restatement's statistics and models, and without -M the dump of today; and the node's cameras through
+all four filters in front of -V, against the library's host forms stage by stage. (The flag surface needs no GPU:
 tests/test_planeseg_cpu.py.)"""
 import subprocess
 
@@ -15,7 +16,7 @@ import np_stat_outlier as NS
 from test_wire import CENTRAL, CLI_DIR, EDGE, frame_inputs, free_port, retry_server_start, wait_listening
 from pointcloud_stitching_amd import synthetic as S
 from pointcloud_stitching_amd.api import PcsContext
-from pointcloud_stitching_amd.types import FLAG_DROP_INVALID, HEADER_SHORTS
+from pointcloud_stitching_amd.types import FLAG_DROP_INVALID, HEADER_SHORTS, PlaneParams
 
 pytestmark = pytest.mark.gpu
 
@@ -26,6 +27,8 @@ CLUSTER = (100, 50, 3000)          # the -E behind it
 LOCAL = (50, 128, 100, 2, 3)       # ... for three 64x48 cameras of the node with invalid depth dropped
 LOCAL_BEHIND_STAT = (30, 256, 200, 3, 7)
 LOCAL_CLUSTER = (150, 30, 0)
+LOCAL_RADIUS = (200, 5)            # the four-stage chain of the node's cameras: the LOCAL constants of the four CLI test files
+LOCAL_STAT = (8, 1000, 300)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -188,3 +191,48 @@ def test_local_cameras_between_the_statistical_filter_and_the_cluster_filter(ora
     assert got.shape == want.shape and (got == want).all()
     assert has_lines(r.stdout, lines), r.stdout
     assert f"Cluster filter: {stats['considered']} -> {stats['kept']} points" in r.stdout
+
+
+@pytest.fixture(scope="module")
+def local_chain(oracle):
+    """-O -K -M -E stage by stage through the library's host forms, over the oracle's payload of the node's three cameras: the clouds
+    behind each stage and the lines -t prints."""
+    cfgs, depth, color = S.synth_frame_set(3, 64, 48)
+    payload, _ = oracle.process_frames(cfgs, depth, color, flags=FLAG_DROP_INVALID)
+    with PcsContext(cfgs, flags=FLAG_DROP_INVALID) as ctx:
+        first = ctx.radius_outlier(payload, *LOCAL_RADIUS)
+        second, st = ctx.stat_outlier(first, *LOCAL_STAT)
+        third, models, pl = ctx.plane_segment(second, PlaneParams.make(*LOCAL))
+        fourth, cl = ctx.cluster_filter(third, *LOCAL_CLUSTER)
+    lines = [f"Outlier removal: {payload.shape[0]} -> {first.shape[0]} points",
+             f"Statistical outlier removal: {st['considered']} -> {st['kept']} points (dense {st['dense']}, threshold {st['threshold']}/256 per k)",
+             f"Plane segmentation: {pl['considered']} -> {pl['kept']} points ({pl['planes']} planes, {pl['inliers_total']} inliers)"]
+    lines += [f"Plane {r}: {m['inliers']} inliers, normal ({m['nx']}, {m['ny']}, {m['nz']}), offset {m['off']}, hypothesis {m['hypothesis']}"
+              for r, m in enumerate(models[:pl['planes']])]
+    lines += [f"Cluster filter: {cl['considered']} -> {cl['kept']} points ({cl['clusters']} clusters, {cl['kept_clusters']} kept, largest {cl['largest']})"]
+    # every stage drops a record and keeps one, and a plane is accepted: a chain that keeps everything or nothing would pass whatever
+    # the plumbing does (3642 -> 1776 -> 1277 -> 807 (2 planes) -> 487 by the numpy restatements)
+    assert 0 < fourth.shape[0] < third.shape[0] < second.shape[0] < first.shape[0] < payload.shape[0] < 3 * 64 * 48
+    assert pl['planes'] >= 1 and (st['kept'], pl['kept'], cl['kept']) == (second.shape[0], third.shape[0], fourth.shape[0])
+    return fourth, lines
+
+
+@pytest.mark.parametrize("leaf", [0, 100])
+def test_local_cameras_through_all_four_filters(local_chain, oracle, tmp_path, leaf):
+    """-i synth: -Z -O -K -M -E [-V]: four stages over two alternating buffers, each written twice, then the voxel grid on the last
+    stage's device count (or the kept records out), against the same chain through the library's host forms."""
+    kept, lines = local_chain
+    want = kept
+    if leaf:
+        want = oracle.voxel_grid(kept, leaf)
+        assert 0 < want.shape[0] < kept.shape[0]
+    out = str(tmp_path / "dump.bin")
+    r = subprocess.run([CENTRAL, "-i", "synth:64x48", "-N", "3", "-Z", "-O", option(LOCAL_RADIUS), "-K", option(LOCAL_STAT), "-M", option(LOCAL),
+                        "-E", option(LOCAL_CLUSTER), "-q", "-r", "1", "-t", "-o", out] + (["-V", str(leaf)] if leaf else []),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=150)
+    assert r.returncode == 0, r.stderr
+    got = dump(out)
+    assert got.shape == want.shape and (got == want).all()
+    assert has_lines(r.stdout, lines), r.stdout
+    chain_lines = [line for line in r.stdout.splitlines() if line in lines]
+    assert chain_lines == lines, r.stdout      # each once, in stage order
