@@ -823,6 +823,65 @@ int pcs_cluster_labels_device(pcs_ctx* ctx, const int16_t* d_payload, int n_poin
 int pcs_cluster_labels(pcs_ctx* ctx, const int16_t* payload, int n_points, int tolerance_mm, int32_t* labels, int32_t* sizes,
                        int* n_clusters);   /* host pointers, staged, synchronous */
 
+/* ---- Cluster objects: per-cluster box and sums (not in the reference) -------------------------------------------------------------- *
+ * What the clusters that pass the size filter ARE, from the call that filters: one index build and one union. Adjacency, clusters,
+ * size(i), label(i) and KEPT are those above with the same pcs_cluster_params. Integer only; no float anywhere.
+ *   OBJECT        a cluster with min_size <= size and (max_size == 0 or size <= max_size). Objects are numbered k = 0 .. n_objects-1
+ *                   by ascending label (the input index of their first record); n_objects equals the filter's kept_clusters.
+ *   object_of(i)  the k of record i's cluster, -1 where it is no object: the true k, also where k >= max_objects.
+ *   object k      over its member records, coordinates sign-extended from the shorts: label, size; lo[a] / hi[a] the minimum /
+ *                   maximum of coordinate a (an inclusive box); sum_xyz[a] the sum of coordinate a (|sum| < 2^47);
+ *                   sum_rgb = (sum R, sum G, sum B) with R = short3 & 0xFF, G = (short3 >> 8) & 0xFF, B = short4 & 0xFF (the high
+ *                   byte of short 4 is not read). Sums, not means: they are exact and add across shards; the consumer divides.
+ * The table holds the first min(n_objects, max_objects) objects, each entry written whole (80 bytes, reserved words 0);
+ * *n_objects always receives the full count. Nothing at or beyond entry min(n_objects, max_objects), and nothing at or beyond word
+ * n of object_of, is written. Exact and deterministic: the same bytes on every run, whatever order the atomics arrive in; under a
+ * permutation of the records the table is the same multiset of (size, lo, hi, sum_xyz, sum_rgb), only label, the order and object_of
+ * follow the permutation. tests/np_cluster_objects.py restates it.
+ * pcs_cluster_objects_device: asynchronous on the context's stream, no host round trip. `out` is a HOST struct of device pointers,
+ *   read at call time: objects (8-byte aligned, max_objects entries; NULL iff max_objects == 0), max_objects 0..PCS_CLUSTER_OBJECTS_MAX,
+ *   reserved 0, n_objects (required, 4-byte aligned), object_of (optional, n int32, 4-byte aligned), out / out_shorts / out_points
+ *   (optional, both pointers or neither: the filtered payload, whose bytes, count and rule out_shorts >= 5 n are exactly
+ *   pcs_cluster_filter_device's for the same arguments), stats (optional, that filter's block, unchanged meaning; without `out`
+ *   its `kept` is still the kept record count). Launches: the filter's index, init, union and roots (9), then record roots, firsts,
+ *   first scan, slots, accumulate, finish (6): 15; with `out` the filter's flag, tile count, tile scan and emit in between: 19;
+ *   with stats one more (and, without `out`, flag, tile count and tile scan for its kept count: 19). n_points 0 launches nothing and
+ *   writes n_objects = 0, a zero out_points and a zeroed block.
+ * pcs_cluster_objects_device_counted: the count is read from *d_n_points (device, 4-byte aligned) when the kernels run, clamped to
+ *   0..max_points; max_points sizes the workspace, the grids and the output checks; records at or beyond the count are never read
+ *   as records, object_of is written below the device count only.
+ * pcs_cluster_objects: host pointers, staged through the context, synchronous; object_of optional.
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the function and the argument), nothing launched, nothing written: every
+ *   refusal of pcs_cluster_filter_device*; a NULL out struct; max_objects outside 0..PCS_CLUSTER_OBJECTS_MAX; objects NULL with
+ *   max_objects > 0 or not 8-byte aligned; reserved != 0; out without out_points or the reverse; n_objects NULL or misaligned; a
+ *   misaligned object_of; any overlap among the input and all output ranges.
+ * Works on every context: flags, crop box and downsample are not read. The workspace is the cluster filter's plus 8.13 bytes per
+ *   record of n_points / max_points (the record's root, its root's object, the firsts' bitmap and tile words) and 80 bytes per object
+ *   of max_objects, in the same slab of the context, grown on demand. With pcs_kernel_timing enabled a call yields one interval per
+ *   launch. Measured: DESIGN.md section 10 (f15), profiles/objects_probe.txt.                                                      */
+#define PCS_CLUSTER_OBJECTS_MAX 65536
+typedef struct pcs_cluster_object {          /* 80 bytes, 8-byte aligned */
+    int32_t label, size;
+    int16_t lo[3], hi[3];
+    int32_t reserved0;                       /* 0 */
+    int64_t sum_xyz[3];
+    int64_t sum_rgb[3];
+    int64_t reserved1;                       /* 0 */
+} pcs_cluster_object;
+typedef struct pcs_cluster_objects_out {     /* host struct of device pointers, read at call time */
+    pcs_cluster_object* objects; int32_t max_objects; int32_t reserved;   /* objects may be NULL iff max_objects == 0 */
+    int32_t* n_objects;                      /* required, 4-byte aligned */
+    int32_t* object_of;                      /* optional, n int32 */
+    int16_t* out; size_t out_shorts; int32_t* out_points;   /* optional filtered payload: out and out_points both or neither */
+    struct pcs_cluster_stats* stats;         /* optional, the filter's block, unchanged meaning */
+} pcs_cluster_objects_out;
+int pcs_cluster_objects_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const pcs_cluster_params* params,
+                               const pcs_cluster_objects_out* out);
+int pcs_cluster_objects_device_counted(pcs_ctx* ctx, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                       const pcs_cluster_params* params, const pcs_cluster_objects_out* out);
+int pcs_cluster_objects(pcs_ctx* ctx, const int16_t* payload, int n_points, const pcs_cluster_params* params,
+                        pcs_cluster_object* objects, int max_objects, int* n_objects, int32_t* object_of);   /* host pointers, staged, synchronous */
+
 /* ---- RANSAC plane segmentation on a packed payload (not in the reference) --------------------------------------------------------- *
  * Connectivity is transitive: everything that stands on a floor is one cluster through the floor. This call takes the dominant planes
  * (floor, walls, a table) out of the cloud, or hands them out, between the outlier filters and the cluster filter. n records of 5

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -692,6 +692,37 @@ class PcsContext:
         *d_n_clusters (int32, required) the number of clusters. See pcs_cluster_labels_device."""
         self._check(self._lib.pcs_cluster_labels_device(self._h, d_payload or None, int(n_points), int(tolerance_mm), d_labels or None,
                                                         d_sizes or None, d_n_clusters or None))
+
+    def cluster_objects(self, payload: np.ndarray, tolerance_mm: int, min_size: int, max_size: int = 0, max_objects: int = 1024):
+        """Packed records (int16 [n,5]) -> (the object table: a structured array (types.CLUSTER_OBJECT_DTYPE) of the first
+        min(n_objects, max_objects) clusters that hold min_size..max_size records, by ascending label, with their box and integer
+        sums; n_objects, the full count; object_of int32 [n]: every record's object, -1 for none)
+        (pcs_cluster_objects: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        n = p.shape[0]
+        table = np.zeros(max(int(max_objects), 1), CLUSTER_OBJECT_DTYPE)
+        object_of = np.zeros(max(n, 1), np.int32)
+        cnt = C.c_int(-1)
+        params = ClusterParams.make(tolerance_mm, min_size, max_size)
+        self._check(self._lib.pcs_cluster_objects(self._h, _ptr(p) if n else None, n, C.byref(params),
+                                                  C.cast(table.ctypes.data, C.POINTER(ClusterObject)) if max_objects else None,
+                                                  int(max_objects), C.byref(cnt), _ptr(object_of)))
+        return table[:min(int(cnt.value), int(max_objects))].copy(), int(cnt.value), object_of[:n].copy()
+
+    def cluster_objects_device(self, d_payload: int, n_points: int, params: ClusterParams, out: ClusterObjectsOut) -> None:
+        """Asynchronous; `out` (types.ClusterObjectsOut) holds the device pointers: the table and *n_objects, optionally object_of,
+        the filtered payload with its count, and the statistics block. params and out may be None (refused). See
+        pcs_cluster_objects_device."""
+        self._check(self._lib.pcs_cluster_objects_device(self._h, d_payload or None, int(n_points), C.byref(params) if params is not None else None,
+                                                         C.byref(out) if out is not None else None))
+
+    def cluster_objects_device_counted(self, d_payload: int, d_n_points: int, max_points: int, params: ClusterParams,
+                                       out: ClusterObjectsOut) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run. See
+        pcs_cluster_objects_device_counted."""
+        self._check(self._lib.pcs_cluster_objects_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
+                                                                 C.byref(params) if params is not None else None,
+                                                                 C.byref(out) if out is not None else None))
 
     # -- plane segmentation (defined by this build; see include/pcs_hip.h) --------------------------
     def plane_segment(self, payload: np.ndarray, params: PlaneParams):

@@ -9,6 +9,10 @@
 // Two output buffers alternate between the stages (stage k reads what stage k-1 wrote and writes the other one, so no call sees
 // overlapping input and output; the first stage's input belongs to the caller). Every enabled stage keeps a 64-byte count word and
 // its own statistics / model block, which report() reads after the frame-set's last launch.
+//
+// -L (pcs_objects.h) adds nothing to the order: with it the E stage calls the objects form of the cluster filter — plain or counted by
+// the same rule, the stage's usual output buffer, count word and statistics block in its `out` struct — so the cloud that leaves the
+// stage is what -E alone gives, and the object table and its count land in two device blocks of the chain's own.
 #pragma once
 
 #include <cstring>
@@ -17,6 +21,7 @@
 #include <vector>
 
 #include "pcs_cluster.h"
+#include "pcs_objects.h"
 #include "pcs_outlier.h"
 #include "pcs_plane.h"
 #include "pcs_statoutlier.h"
@@ -35,6 +40,8 @@ struct Params {
     pcs_stat_outlier_params stat{};
     pcs_plane_params plane{};
     pcs_cluster_params cluster{};
+    // -L: max_objects 0 = not given; the table and its count word on the device (Chain::allocate)
+    struct { int max_objects = 0; pcs_cluster_object* d_table = nullptr; int32_t* d_n = nullptr; } objects;
 };
 
 // -M's block: the statistics, then the models
@@ -97,6 +104,13 @@ inline const Stage kStages[] = {
      [](const char* arg, Params& p, std::string& why) { return pcs_cluster::parse(arg, p.cluster, why); }, sizeof(pcs_cluster_stats),
      [](pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void* d_block) {
          pcs_cluster_stats* d_stats = static_cast<pcs_cluster_stats*>(d_block);
+         if (p.objects.max_objects) {      // -L: the same filter, and the object table beside it
+             pcs_cluster_objects_out o{};
+             o.objects = p.objects.d_table; o.max_objects = p.objects.max_objects; o.n_objects = p.objects.d_n;
+             o.out = d_out; o.out_shorts = out_shorts; o.out_points = d_n_out; o.stats = d_stats;
+             return in.d_n ? pcs_cluster_objects_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, &o)
+                           : pcs_cluster_objects_device(ctx, in.d, in.n, &p.cluster, &o);
+         }
          return in.d_n ? pcs_cluster_filter_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, d_out, out_shorts, d_n_out, d_stats)
                        : pcs_cluster_filter_device(ctx, in.d, in.n, &p.cluster, d_out, out_shorts, d_n_out, d_stats);
      },
@@ -108,6 +122,7 @@ inline const Stage kStages[] = {
      }},
 };
 constexpr int kStageCount = sizeof kStages / sizeof kStages[0];
+constexpr int kClusterStage = kStageCount - 1;      // 'E': the stage -L rides on
 
 struct Chain {
     Params params;
@@ -119,6 +134,9 @@ struct Chain {
     void* d_block[kStageCount] = {};
     Cloud entered{};                       // what the last run() was given
     int status = PCS_OK;                   // of the last run(): the first stage that failed ends it
+    std::string objects_file;              // -L: where the table goes ("-": stdout); empty: no -L
+    void* d_objects = nullptr;             // ... the table (params.objects.max_objects entries) and its count word
+    void* d_n_objects = nullptr;
 
     bool any() const
     {
@@ -134,6 +152,13 @@ struct Chain {
         return false;
     }
 
+    // -L's argument: the file and the table's size. false: `why` says what is wrong with it.
+    bool parse_objects(const char* arg, std::string& why)
+    {
+        return pcs_objects::parse(arg, objects_file, params.objects.max_objects, why);
+    }
+    bool objects() const { return params.objects.max_objects != 0; }
+
     // Buffers for clouds of up to out_shorts shorts: one per enabled stage, two at the most.
     int allocate(pcs_ctx* c, size_t shorts)
     {
@@ -144,6 +169,12 @@ struct Chain {
             if (n < 2) rc = pcs_device_malloc(ctx, &d_buf[n++], out_shorts * sizeof(int16_t) + 64);
             if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_count[s], 64);
             if (rc == PCS_OK && kStages[s].block_bytes) rc = pcs_device_malloc(ctx, &d_block[s], kStages[s].block_bytes);
+        }
+        if (rc == PCS_OK && objects()) {
+            rc = pcs_device_malloc(ctx, &d_objects, (size_t)params.objects.max_objects * sizeof(pcs_cluster_object));
+            if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_n_objects, 64);
+            params.objects.d_table = static_cast<pcs_cluster_object*>(d_objects);
+            params.objects.d_n = static_cast<int32_t*>(d_n_objects);
         }
         return rc;
     }
@@ -176,13 +207,32 @@ struct Chain {
             ok = pcs_memcpy_d2h(ctx, &n[s + 1], d_count[s], sizeof n[0]) == PCS_OK &&
                  (block[s].empty() || pcs_memcpy_d2h(ctx, block[s].data(), d_block[s], block[s].size()) == PCS_OK);
         }
+        int32_t n_objects = 0;
+        if (ok && objects()) ok = pcs_memcpy_d2h(ctx, &n_objects, d_n_objects, sizeof n_objects) == PCS_OK;
         if (!ok || pcs_synchronize(ctx) != PCS_OK) return false;
         int n_in = n[0];
         for (int s = 0; s < kStageCount; s++) {
             if (!enabled[s]) continue;
             kStages[s].print(os, block[s].data(), n_in, n[s + 1]);
+            if (s == kClusterStage && objects())
+                os << "Objects: " << n_objects << " (" << (n_objects < params.objects.max_objects ? n_objects : params.objects.max_objects)
+                   << " written)" << std::endl;
             n_in = n[s + 1];
         }
+        return true;
+    }
+
+    // -L's lines of the last run(): the header and one line per written object. false: a copy failed (pcs_last_error has it).
+    bool write_objects(std::ostream& os) const
+    {
+        int32_t n_objects = 0;
+        if (!entered.d) { pcs_objects::write(os, nullptr, 0); return true; }      // no frame-set went through: the header alone
+        if (pcs_memcpy_d2h(ctx, &n_objects, d_n_objects, sizeof n_objects) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
+        const int written = n_objects < 0 ? 0 : n_objects < params.objects.max_objects ? n_objects : params.objects.max_objects;
+        std::vector<pcs_cluster_object> table((size_t)written);
+        if (written && (pcs_memcpy_d2h(ctx, table.data(), d_objects, table.size() * sizeof table[0]) != PCS_OK || pcs_synchronize(ctx) != PCS_OK))
+            return false;
+        pcs_objects::write(os, table.data(), written);
         return true;
     }
 
@@ -192,6 +242,8 @@ struct Chain {
         for (void*& p : d_buf) drop(p);
         for (void*& p : d_count) drop(p);
         for (void*& p : d_block) drop(p);
+        drop(d_objects);
+        drop(d_n_objects);
     }
 };
 

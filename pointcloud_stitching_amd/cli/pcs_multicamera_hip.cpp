@@ -66,11 +66,20 @@
 //                      max_size records, max_size 0 or absent: no upper bound). -t prints `Cluster filter: <in> -> <kept> points
 //                      (<clusters> clusters, <kept_clusters> kept, largest <largest>)`. Zero-depth pixels form one huge cluster on
 //                      their camera's origin: with -i give -Z (or -B).
+//              -L <file>[,<max_objects>]  (with -E) what the clusters that stay ARE: the E stage calls pcs_cluster_objects_device (plain or
+//                      counted by the chain's rule) with its usual output buffer, count word and statistics block, so the cloud that
+//                      leaves the stage, and everything behind it, is byte for byte what -E alone gives; the object table (objects by
+//                      ascending first record: label, size, inclusive box, integer sums of coordinates and colours) stays on the
+//                      device. -t prints `Objects: <n_objects> (<written> written)` behind the `Cluster filter:` line. After the last
+//                      frame-set <file> (`-`: stdout) gets one header line `# k label size lo_x lo_y lo_z hi_x hi_y hi_z sum_x sum_y
+//                      sum_z sum_r sum_g sum_b` and one line of raw integers per written object of that frame-set, at most max_objects
+//                      (1..65536, default 1024). Refused without -E and with -G (the node library has no object table).
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <string>
 #include <thread>
@@ -124,7 +133,7 @@ static void usage()
               << "                  as the reference's pcs-multicamera-optimized does (decode, pcl::transformPointCloud, re-encode)\n"
               << " -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box, millimetres in the world frame, inclusive: -i crops in the fused path, -c crops the\n"
               << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
-              << filters
+              << filters << pcs_objects::help()
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
@@ -135,7 +144,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -175,6 +184,11 @@ int main(int argc, char** argv)
                 if (!chain.parse(c, optarg, why)) { std::cerr << "-" << (char)c << " " << optarg << ": " << why << std::endl; return 2; }
                 break;
             }
+            case 'L': {
+                std::string why;
+                if (!chain.parse_objects(optarg, why)) { std::cerr << "-L " << optarg << ": " << why << std::endl; return 2; }
+                break;
+            }
             case 's': case 'v': case 'n':
                 std::cerr << "-" << (char)c << " drives the reference's PCL viewer / PLY writer, which this build does not include" << std::endl;
                 return 2;
@@ -183,11 +197,15 @@ int main(int argc, char** argv)
     }
     if (downsample < 1) { std::cerr << "downsample must be >= 1" << std::endl; return 2; }
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
+    if (chain.objects() && n_gpus > 0) { std::cerr << "-L is not available with -G: the node library has no object table" << std::endl; return 2; }
     for (int k = 0; k < pcs_filter_chain::kStageCount; k++)
         if (chain.enabled[k] && n_gpus > 0) {
             const auto& stage = pcs_filter_chain::kStages[k];
             std::cerr << "-" << stage.letter << " is not available with -G: the node library has no " << stage.refusal << std::endl; return 2;
         }
+    if (chain.objects() && !chain.enabled[pcs_filter_chain::kClusterStage]) {
+        std::cerr << "-L writes the objects of the cluster filter: it needs -E <tolerance_mm,min_size[,max_size]>" << std::endl; return 2;
+    }
     if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
     if (!source && !cameras) source = "synth:1280x720";      // no live cameras on this node: the synthetic generator
@@ -672,6 +690,17 @@ int main(int argc, char** argv)
     if (dump_path) {
         FILE* f = fopen(dump_path, "wb");
         if (f) { fwrite(stitched.data(), 1, (size_t)size_bytes + 4, f); fclose(f); }
+    }
+    if (chain.objects()) {      // -L: the last frame-set's object table
+        bool ok;
+        if (chain.objects_file == "-") {
+            ok = chain.write_objects(std::cout);
+        } else {
+            std::ofstream f(chain.objects_file);
+            ok = f.good() && chain.write_objects(f);
+            if (!f.good()) std::cerr << "-L: cannot write " << chain.objects_file << std::endl;
+        }
+        if (!ok) std::cerr << "-L: " << pcs_last_error(ctx) << std::endl;
     }
     for (int fd : cam_fd) ::close(fd);
     if (client_fd >= 0) ::close(client_fd);

@@ -101,6 +101,87 @@ int run_labels(pcs_ctx* c, const int16_t* d_payload, int n_points, int tolerance
     return PCS_OK;
 }
 
+// ---- the object table ---------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(pcs_cluster_object) == 80 && alignof(pcs_cluster_object) == 8, "pcs_cluster_object is 80 bytes, 8-byte aligned");
+
+// What both device forms of the objects call check: the filter's checks over the filtered payload where one is asked for (without
+// one, the filter's checks of the parameters, the count and the input), then the table's own arguments and every overlap.
+// n_points is the counted form's max_points; count / count_name its count word (an input: nothing may be written over it).
+int check_objects(pcs_ctx* c, const char* who, const void* in, int n_points, const char* n_name, const pcs_cluster_params* params,
+                  const pcs_cluster_objects_out* out, const void* count = nullptr, const char* count_name = nullptr)
+{
+    if (!out) return fail(c, PCS_ERR_INVALID_ARG, "%s: out is NULL", who);
+    if ((out->out != nullptr) != (out->out_points != nullptr))
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: out->out and out->out_points go together: %s is NULL", who, out->out ? "out->out_points" : "out->out");
+    if (out->out) {
+        if (int rc = check_args(c, who, in, "d_payload", n_points, n_name, params, out->out, "out->out", out->out_shorts, out->out_points,
+                                "out->out_points", 4, out->stats, "out->stats"))
+            return rc;
+    } else {
+        // the same checks with the count word standing in for the filter's: no payload output, so no worst case to hold
+        if (int rc = check_args(c, who, in, "d_payload", 0, n_name, params, nullptr, "out->out", 0, out->n_objects, "out->n_objects", 4,
+                                out->stats, "out->stats"))
+            return rc;
+        if (n_points < 0 || n_points > kMaxPoints) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s %d is outside 0..%d", who, n_name, n_points, kMaxPoints);
+        if (n_points && !in) return fail(c, PCS_ERR_INVALID_ARG, "%s: d_payload is NULL", who);
+    }
+    if (out->max_objects < 0 || out->max_objects > PCS_CLUSTER_OBJECTS_MAX)
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: out->max_objects %d is outside 0..%d", who, out->max_objects, PCS_CLUSTER_OBJECTS_MAX);
+    if (out->max_objects && !out->objects) return fail(c, PCS_ERR_INVALID_ARG, "%s: out->objects is NULL with out->max_objects %d", who, out->max_objects);
+    if ((uintptr_t)out->objects & 7u) return fail(c, PCS_ERR_INVALID_ARG, "%s: out->objects is not 8-byte aligned", who);
+    if (out->reserved != 0) return fail(c, PCS_ERR_INVALID_ARG, "%s: out->reserved %d is not 0", who, out->reserved);
+    if (!out->n_objects) return fail(c, PCS_ERR_INVALID_ARG, "%s: out->n_objects is NULL", who);
+    if ((uintptr_t)out->n_objects & 3u) return fail(c, PCS_ERR_INVALID_ARG, "%s: out->n_objects is not 4-byte aligned", who);
+    if ((uintptr_t)out->object_of & 3u) return fail(c, PCS_ERR_INVALID_ARG, "%s: out->object_of is not 4-byte aligned", who);
+    if (count_name) {
+        if (!count) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is NULL", who, count_name);
+        if ((uintptr_t)count & 3u) return fail(c, PCS_ERR_INVALID_ARG, "%s: %s is not 4-byte aligned", who, count_name);
+    }
+    const size_t bytes = (size_t)n_points * PCS_POINT_BYTES;
+    const NamedRange ins[] = {{in, bytes, "d_payload"}, {count, sizeof(int32_t), count_name}};
+    const NamedRange outs[] = {{out->objects, (size_t)out->max_objects * sizeof(pcs_cluster_object), "out->objects"},
+                               {out->n_objects, sizeof(int32_t), "out->n_objects"},
+                               {out->object_of, (size_t)n_points * sizeof(int32_t), "out->object_of"},
+                               {out->out, bytes, "out->out"},
+                               {out->out_points, sizeof(int32_t), "out->out_points"},
+                               {out->stats, kStatsBytes, "out->stats"}};
+    const NamedRange* with = nullptr;
+    if (const NamedRange* bad = first_overlap(outs, 6, ins, 2, &with)) {
+        if (!with) with = ranges_overlap(bad->p, bad->n, ins[0].p, ins[0].n) ? &ins[0] : &ins[1];
+        return fail(c, PCS_ERR_INVALID_ARG, "%s: %s overlaps %s", who, bad->name, with->name);
+    }
+    return PCS_OK;
+}
+
+// The objects call's launches, behind the checks. capacity: n_points, or the counted form's max_points.
+int run_objects(pcs_ctx* c, const int16_t* d_payload, int capacity, const int32_t* d_n_points, const pcs_cluster_params& P,
+                const pcs_cluster_objects_out& O)
+{
+    DeviceGuard guard(c->device);
+    if (capacity == 0) {         // nothing to launch: no objects, a zero count, a zeroed block
+        HIPCHK(c, hipMemsetAsync(O.n_objects, 0, sizeof(int32_t), c->stream));
+        if (O.out_points) HIPCHK(c, hipMemsetAsync(O.out_points, 0, sizeof(int32_t), c->stream));
+        if (O.stats) HIPCHK(c, hipMemsetAsync(O.stats, 0, kStatsBytes, c->stream));
+        return PCS_OK;
+    }
+    const uint32_t cap = (uint32_t)capacity, max_objects = (uint32_t)O.max_objects;
+    const size_t need = cluster_objects_workspace_bytes(cap, max_objects);
+    if (int rc = ensure_ws(c, c->s_outlier_ws, c->s_outlier_ws_cap, need)) return rc;
+    // the filter's stages: 0 to 8 always; flag, tile count and tile scan where somebody reads the kept count; emit with `out`; stats
+    int32_t* const d_kept = O.out_points ? O.out_points : cluster_objects_scratch_word(cap, max_objects, c->s_outlier_ws);
+    const int filter_end = O.out ? 13 : O.stats ? 12 : 9;
+    for (int stage = 0; stage < kClusterStages; stage++) {
+        if (stage >= filter_end && !(stage == 13 && O.stats)) continue;
+        PCS_TIMED(c, launch_cluster_stage(stage, d_payload, cap, d_n_points, cap, P.tolerance_mm, P.min_size, P.max_size, c->s_outlier_ws,
+                                          c->s_outlier_ws_cap, O.out, d_kept, reinterpret_cast<long long*>(O.stats), nullptr, nullptr, nullptr,
+                                          c->stream));
+    }
+    for (int k = 0; k < kClusterObjectStages; k++)
+        PCS_TIMED(c, launch_cluster_object_stage(kClusterObjectStage0 + k, d_payload, cap, P.tolerance_mm, P.min_size, P.max_size, max_objects,
+                                                 c->s_outlier_ws, c->s_outlier_ws_cap, O.objects, O.n_objects, O.object_of, c->stream));
+    return PCS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -194,6 +275,57 @@ try {
     return PCS_OK;
 } catch (const std::exception& ex) {
     return fail(c, PCS_ERR_NOMEM, "pcs_cluster_labels: host allocation failed (%s)", ex.what());
+}
+
+int pcs_cluster_objects_device(pcs_ctx* c, const int16_t* d_payload, int n_points, const pcs_cluster_params* params,
+                               const pcs_cluster_objects_out* out)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (int rc = check_objects(c, "pcs_cluster_objects_device", d_payload, n_points, "n_points", params, out)) return rc;
+    return run_objects(c, d_payload, n_points, nullptr, *params, *out);
+}
+
+int pcs_cluster_objects_device_counted(pcs_ctx* c, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                       const pcs_cluster_params* params, const pcs_cluster_objects_out* out)
+{
+    if (!c) return PCS_ERR_INVALID_ARG;
+    if (int rc = check_objects(c, "pcs_cluster_objects_device_counted", d_payload, max_points, "max_points", params, out, d_n_points, "d_n_points"))
+        return rc;
+    return run_objects(c, d_payload, max_points, d_n_points, *params, *out);
+}
+
+int pcs_cluster_objects(pcs_ctx* c, const int16_t* payload, int n_points, const pcs_cluster_params* params, pcs_cluster_object* objects,
+                        int max_objects, int* n_objects, int32_t* object_of)
+try {
+    static const char who[] = "pcs_cluster_objects";
+    if (!c) return PCS_ERR_INVALID_ARG;
+    // the device form's checks over the host ranges (its names for them: the struct's), the count word's alignment the host's
+    pcs_cluster_objects_out host{};
+    host.objects = objects;
+    host.max_objects = max_objects;
+    host.n_objects = reinterpret_cast<int32_t*>(n_objects);
+    host.object_of = object_of;
+    if (int rc = check_objects(c, who, payload, n_points, "n_points", params, &host)) return rc;
+    if (n_points == 0) { *n_objects = 0; return PCS_OK; }
+    DeviceGuard guard(c->device);
+    // the table, then object_of, in the staged output (8-byte aligned: the slab is 256-byte aligned, an entry 80 bytes)
+    const size_t table = (size_t)max_objects * sizeof(pcs_cluster_object), words = (size_t)n_points * sizeof(int32_t);
+    if (int rc = stage_payload(c, payload, (size_t)n_points * PCS_POINT_BYTES, table + words)) return rc;
+    pcs_cluster_objects_out dev{};
+    dev.objects = max_objects ? reinterpret_cast<pcs_cluster_object*>(c->s_voxel_out) : nullptr;
+    dev.max_objects = max_objects;
+    dev.n_objects = c->d_counts;
+    dev.object_of = object_of ? reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(c->s_voxel_out) + table) : nullptr;
+    if (int rc = run_objects(c, c->s_voxel_in, n_points, nullptr, *params, dev)) return rc;
+    int32_t count = 0;
+    if (int rc = fetch_count(c, who, n_points, "their object's first", &count)) return rc;
+    const size_t written = (size_t)std::min(count, max_objects);
+    if (written) HIPCHK(c, hipMemcpy(objects, dev.objects, written * sizeof(pcs_cluster_object), hipMemcpyDeviceToHost));
+    if (object_of) HIPCHK(c, hipMemcpy(object_of, dev.object_of, words, hipMemcpyDeviceToHost));
+    *n_objects = count;
+    return PCS_OK;
+} catch (const std::exception& ex) {
+    return fail(c, PCS_ERR_NOMEM, "pcs_cluster_objects: host allocation failed (%s)", ex.what());
 }
 
 }  // extern "C"

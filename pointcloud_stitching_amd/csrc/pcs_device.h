@@ -414,7 +414,7 @@ hipError_t  launch_stat_stage(int stage, const int16_t* d_in, uint32_t n_points,
 // given to stage 6, which zeroes it) the statistics block. The labels form runs kClusterLabelStages launches, cluster_label_stage(k)
 // of them: 0 to 8, then 14 (label roots) and 15 (labels) with d_labels (n_points int32), d_sizes (optional) and d_n_clusters; it has
 // no counted variant (d_n_points NULL). d_ws: cluster_workspace_bytes(capacity) bytes, 256-byte aligned; count and capacity as
-// launch_outlier_stage's. cluster_stage_name names all sixteen.
+// launch_outlier_stage's. cluster_stage_name names all sixteen, and the object table's six behind them.
 constexpr int kClusterStages      = 14;
 constexpr int kClusterLabelStages = 11;
 inline int  cluster_label_stage(int k) { return k < 9 ? k : k + 5; }
@@ -424,6 +424,19 @@ hipError_t  launch_cluster_stage(int stage, const int16_t* d_in, uint32_t n_poin
                                  int tolerance_mm, int min_size, int max_size, void* d_ws, size_t ws_bytes, int16_t* d_out,
                                  int32_t* d_out_points, long long* d_stats, int32_t* d_labels, int32_t* d_sizes, int32_t* d_n_clusters,
                                  hipStream_t st);
+// The object table (pcs_cluster_objects_device; DESIGN.md section 3 "Cluster objects"): stages 16 to 21 — record roots, firsts, first
+// scan, slots, accumulate, finish — behind stages 0 to 8 of launch_cluster_stage (and, for the filtered payload, its 9 to 13) over the
+// same workspace, which must hold cluster_objects_workspace_bytes(capacity, max_objects). The record count is the one stage 0 left
+// in the control block. d_objects: max_objects entries (NULL with 0); d_n_objects required; d_object_of optional, `capacity` int32.
+// cluster_objects_scratch_word: an int32 of the workspace for a caller that needs the compaction's count and has no word of its own.
+constexpr int kClusterAllStages    = 22;     // what cluster_stage_name names
+constexpr int kClusterObjectStage0 = 16;
+constexpr int kClusterObjectStages = 6;
+size_t      cluster_objects_workspace_bytes(uint32_t capacity, uint32_t max_objects);
+int32_t*    cluster_objects_scratch_word(uint32_t capacity, uint32_t max_objects, void* d_ws);
+hipError_t  launch_cluster_object_stage(int stage, const int16_t* d_in, uint32_t capacity, int tolerance_mm, int min_size, int max_size,
+                                        uint32_t max_objects, void* d_ws, size_t ws_bytes, pcs_cluster_object* d_objects,
+                                        int32_t* d_n_objects, int32_t* d_object_of, hipStream_t st);
 
 // Plane segmentation (pcs_plane_segment_device, pcs_plane_labels_device, pcs_plane_count_inliers_device, pcs_kernels_plane.hip; the
 // definition: DESIGN.md section 3 "Plane segmentation"): each launch its own call, so that the host layer can bracket them one by one.

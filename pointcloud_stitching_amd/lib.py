@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig
+from .types import AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -92,6 +92,9 @@ SYMBOLS = [
     ("pcs_cluster_filter", C.c_int, [_VP, _VP, C.c_int, _P(ClusterParams), _VP, C.c_size_t, _P(C.c_int), _P(ClusterStatsC)]),
     ("pcs_cluster_labels_device", C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP]),
     ("pcs_cluster_labels", C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _P(C.c_int)]),
+    ("pcs_cluster_objects_device", C.c_int, [_VP, _VP, C.c_int, _P(ClusterParams), _P(ClusterObjectsOut)]),
+    ("pcs_cluster_objects_device_counted", C.c_int, [_VP, _VP, _VP, C.c_int, _P(ClusterParams), _P(ClusterObjectsOut)]),
+    ("pcs_cluster_objects", C.c_int, [_VP, _VP, C.c_int, _P(ClusterParams), _P(ClusterObject), C.c_int, _P(C.c_int), _VP]),
     ("pcs_plane_segment_device", C.c_int, [_VP, _VP, C.c_int, _P(PlaneParams), _VP, C.c_size_t, _VP, _VP, _VP]),
     ("pcs_plane_segment_device_counted", C.c_int, [_VP, _VP, _VP, C.c_int, _P(PlaneParams), _VP, C.c_size_t, _VP, _VP, _VP]),
     ("pcs_plane_segment", C.c_int, [_VP, _VP, C.c_int, _P(PlaneParams), _VP, C.c_size_t, _P(C.c_int), _P(PlaneModel), _P(PlaneStats)]),

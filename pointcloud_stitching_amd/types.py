@@ -43,6 +43,12 @@ CLUSTER_STAGES = ("clear", "insert", "cell sums", "cell scan", "cell starts", "s
 CLUSTER_LABEL_LAUNCHES = 11                               # ... of one cluster_labels call
 CLUSTER_LABEL_STAGES = CLUSTER_STAGES[:9] + ("label roots", "labels")
 CLUSTER_STATS_FIELDS = ("considered", "clusters", "kept_clusters", "largest", "kept")      # three reserved words behind them
+CLUSTER_OBJECTS_MAX = 65536                               # pcs_cluster_objects_*: max_objects
+CLUSTER_OBJECT_STAGES = CLUSTER_STAGES[:9] + ("record roots", "firsts", "first scan", "slots", "accumulate", "finish")
+CLUSTER_OBJECT_LAUNCHES = 15                              # kernel_times_ms intervals of one cluster_objects call without the filtered output
+CLUSTER_OBJECT_OUT_STAGES = CLUSTER_STAGES[:13] + CLUSTER_OBJECT_STAGES[9:]
+CLUSTER_OBJECT_OUT_LAUNCHES = 19                          # ... with the filtered output (20 with a statistics block, behind "emit")
+CLUSTER_OBJECT_FIELDS = ("label", "size", "lo", "hi", "sum_xyz", "sum_rgb")
 
 PLANE_DISTANCE_MIN, PLANE_DISTANCE_MAX = 1, 1000          # pcs_plane_*: distance_mm
 PLANE_ITERATIONS_MAX, PLANE_MAX_PLANES = 4096, 8
@@ -194,6 +200,31 @@ class ClusterStatsC(C.Structure):
 
     def as_dict(self) -> dict:
         return {name: int(getattr(self, name)) for name in CLUSTER_STATS_FIELDS}
+
+
+class ClusterObject(C.Structure):
+    """pcs_cluster_object: 80 bytes, 8-byte aligned."""
+    _fields_ = [("label", C.c_int32), ("size", C.c_int32), ("lo", C.c_int16 * 3), ("hi", C.c_int16 * 3), ("reserved0", C.c_int32),
+                ("sum_xyz", C.c_int64 * 3), ("sum_rgb", C.c_int64 * 3), ("reserved1", C.c_int64)]
+
+
+# the same layout for numpy: a table is np.ndarray of this dtype
+CLUSTER_OBJECT_DTYPE = np.dtype({"names": ["label", "size", "lo", "hi", "reserved0", "sum_xyz", "sum_rgb", "reserved1"],
+                                 "formats": ["<i4", "<i4", ("<i2", 3), ("<i2", 3), "<i4", ("<i8", 3), ("<i8", 3), "<i8"],
+                                 "offsets": [0, 4, 8, 14, 20, 24, 48, 72], "itemsize": 80})
+
+
+class ClusterObjectsOut(C.Structure):
+    """pcs_cluster_objects_out: a host struct of device pointers."""
+    _fields_ = [("objects", C.c_void_p), ("max_objects", C.c_int32), ("reserved", C.c_int32), ("n_objects", C.c_void_p),
+                ("object_of", C.c_void_p), ("out", C.c_void_p), ("out_shorts", C.c_size_t), ("out_points", C.c_void_p),
+                ("stats", C.c_void_p)]
+
+    @classmethod
+    def make(cls, objects: int = 0, max_objects: int = 0, n_objects: int = 0, object_of: int = 0, out: int = 0, out_shorts: int = 0,
+             out_points: int = 0, stats: int = 0, reserved: int = 0) -> "ClusterObjectsOut":
+        return cls(objects or None, int(max_objects), int(reserved), n_objects or None, object_of or None, out or None, int(out_shorts),
+                   out_points or None, stats or None)
 
 
 class PlaneParams(C.Structure):

@@ -1,0 +1,396 @@
+"""The object table on the GPU (pcs_cluster_objects_device, its counted sibling and the host form), word for word against the
+restatement of DESIGN.md section 3 "Cluster objects" (tests/np_cluster_objects.py) over the clouds of tests/cluster_cases.py: the
+table, n_objects, object_of and the filtered payload with its count and statistics block, at the reference's `buffer + 2` shorts and
+at 16-byte alignment, with 0xA5 guards around the table, behind object_of and around the payload output; one lattice of 131 072
+records against its own arithmetic (sums beyond 32 bits in either sign); a table smaller than the object count; every combination of
+the optional outputs; the counted form; twice for determinism; between the other filters on one context; the host form; the launch
+counts; every refusal. There is no tolerance anywhere."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import cluster_cases as K
+import np_cluster_objects as NO
+import np_clusters as N
+import np_radius_outlier as NR
+import np_stat_outlier as NS
+import radius_outlier_cases as RC
+from pointcloud_stitching_amd import synthetic as S
+from pointcloud_stitching_amd.api import PcsContext, PcsError
+from pointcloud_stitching_amd.types import (CLUSTER_OBJECT_DTYPE, CLUSTER_OBJECT_LAUNCHES, CLUSTER_OBJECT_OUT_LAUNCHES, CLUSTER_OBJECTS_MAX,
+                                            CLUSTER_STATS_FIELDS, POINT_SHORTS, ClusterObject, ClusterObjectsOut, ClusterParams)
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 64
+N_MAX = 131072
+TABLE_MAX = 4200                # lattice_apart has 4096 objects
+CASES = {c[0]: c for c in K.cases()}
+SENTINEL = 0x5A5A5A5A
+STATS_SENTINEL = 0x5A5A5A5A5A5A5A5A
+
+
+def table_equal(a, b):
+    return a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+class Arena:
+    """Device buffers shared by the tests of this module."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.inp = ctx.device_malloc(64 + 10 * N_MAX + 64)
+        self.out = ctx.device_malloc(GUARD + 64 + 10 * N_MAX + GUARD + 64)
+        self.table = ctx.device_malloc(GUARD + 80 * TABLE_MAX + GUARD)
+        self.object_of = ctx.device_malloc(4 * N_MAX + GUARD)
+        self.words = ctx.device_malloc(64)          # [0] n_objects, [4] the kept count, [8] the counted form's input count
+        self.stats = ctx.device_malloc(64 + 64)
+        assert self.inp % 16 == 0 and self.out % 16 == 0 and self.stats % 8 == 0 and self.table % 8 == 0
+
+    def free(self):
+        for p in (self.inp, self.out, self.table, self.object_of, self.words, self.stats):
+            self.ctx.device_free(p)
+
+    def run(self, rec, params, phase=4, max_objects=TABLE_MAX, with_out=True, with_stats=True, with_object_of=True, d_count=None,
+            max_points=None, null_table=False):
+        """-> dict(table, n_objects, object_of, out, kept, stats); every guard and everything behind what the call may write must
+        stay as it was filled. d_count: the counted form with that count on the device and max_points as its capacity."""
+        ctx = self.ctx
+        cap = rec.shape[0] if d_count is None else max_points
+        used = cap if d_count is None else max(0, min(d_count, cap))
+        d_in, d_out, d_table = self.inp + phase, self.out + GUARD + phase, self.table + GUARD
+        if rec.shape[0]:
+            ctx.memcpy_h2d(d_in, np.ascontiguousarray(rec))
+        span = GUARD + phase + 10 * cap + GUARD
+        ctx.memcpy_h2d(self.out, np.full(span, 0xA5, np.uint8))
+        ctx.memcpy_h2d(self.table, np.full(GUARD + 80 * max_objects + GUARD, 0xA5, np.uint8))
+        ctx.memcpy_h2d(self.object_of, np.full(cap + GUARD // 4, SENTINEL, np.int32))
+        ctx.memcpy_h2d(self.words, np.array([SENTINEL, SENTINEL, 0 if d_count is None else d_count, SENTINEL], np.int32))
+        ctx.memcpy_h2d(self.stats, np.full(16, STATS_SENTINEL, np.int64))
+        O = ClusterObjectsOut.make(objects=0 if null_table else d_table, max_objects=max_objects, n_objects=self.words,
+                                   object_of=self.object_of if with_object_of else 0, out=d_out if with_out else 0,
+                                   out_shorts=POINT_SHORTS * cap if with_out else 0, out_points=self.words + 4 if with_out else 0,
+                                   stats=self.stats if with_stats else 0)
+        P = ClusterParams.make(*params)
+        if d_count is None:
+            ctx.cluster_objects_device(d_in, cap, P, O)
+        else:
+            ctx.cluster_objects_device_counted(d_in, self.words + 8, cap, P, O)
+        ctx.synchronize()
+        got = np.empty(span, np.uint8)
+        ctx.memcpy_d2h(got, self.out)
+        raw = np.empty(GUARD + 80 * max_objects + GUARD, np.uint8)
+        ctx.memcpy_d2h(raw, self.table)
+        oo = np.empty(cap + GUARD // 4, np.int32)
+        ctx.memcpy_d2h(oo, self.object_of)
+        words = np.empty(4, np.int32)
+        ctx.memcpy_d2h(words, self.words)
+        block = np.empty(16, np.int64)
+        ctx.memcpy_d2h(block, self.stats)
+        n_objects = int(words[0])
+        assert 0 <= n_objects <= used, n_objects
+        assert words[2] == (0 if d_count is None else d_count) and words[3] == SENTINEL
+        written = min(n_objects, max_objects)
+        assert (raw[:GUARD] == 0xA5).all(), "bytes in front of the table were written"
+        assert (raw[GUARD + 80 * written:] == 0xA5).all(), "bytes at or behind entry min(n_objects, max_objects) were written"
+        table = raw[GUARD:GUARD + 80 * written].copy().view(CLUSTER_OBJECT_DTYPE)
+        assert (table["reserved0"] == 0).all() and (table["reserved1"] == 0).all()
+        if with_object_of:
+            assert (oo[used:] == SENTINEL).all(), "object_of was written at or beyond the count"
+        else:
+            assert (oo == SENTINEL).all()
+        lo = GUARD + phase
+        kept = int(words[1]) if with_out else 0
+        if with_out:
+            assert 0 <= kept <= used
+        else:
+            assert words[1] == SENTINEL
+        assert (got[:lo] == 0xA5).all() and (got[lo + 10 * kept:] == 0xA5).all(), "bytes around the kept records were written"
+        assert (block[8:] == STATS_SENTINEL).all()
+        if with_stats:
+            assert (block[5:8] == 0).all()
+        else:
+            assert (block == STATS_SENTINEL).all()
+        return {"table": table, "n_objects": n_objects, "object_of": oo[:used].copy() if with_object_of else None,
+                "out": got[lo:lo + 10 * kept].copy().view(np.int16).reshape(kept, 5) if with_out else None, "kept": kept,
+                "stats": dict(zip(CLUSTER_STATS_FIELDS, (int(v) for v in block[:5]))) if with_stats else None}
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    cfgs, _, _ = S.synth_frame_set(1, 64, 48, single=True)
+    with PcsContext(cfgs) as c:
+        yield c
+
+
+@pytest.fixture(scope="module")
+def arena(ctx):
+    a = Arena(ctx)
+    yield a
+    a.free()
+
+
+def want_of(name):
+    """(records, params, table, object_of, kept records, stats) of a case, from the shared brute-force reference."""
+    _, rec, params, _ = CASES[name]
+    out, _, stats, lab, sizes = K.reference(name)
+    table, object_of = NO.objects_from_labels(rec, lab, sizes, params[1], params[2])
+    assert table.shape[0] == stats["kept_clusters"]
+    return rec, params, table, object_of, out, stats
+
+
+def check(got, table, object_of, out=None, stats=None, max_objects=TABLE_MAX):
+    assert got["n_objects"] == table.shape[0], (got["n_objects"], table.shape[0])
+    assert table_equal(got["table"], table[:max_objects]), (got["table"], table[:max_objects])
+    if got["object_of"] is not None:
+        assert (got["object_of"] == object_of).all()
+    if out is not None:
+        assert got["kept"] == out.shape[0] and (got["out"] == out).all()
+    if stats is not None:
+        assert got["stats"] == stats, (got["stats"], stats)
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_device_form_matches_the_restatement(arena, name):
+    rec, params, table, object_of, out, stats = want_of(name)
+    for phase in (4, 0):                                    # buffer + 2 shorts; 16-byte aligned
+        check(arena.run(rec, params, phase), table, object_of, out, stats)
+
+
+def test_the_cases_cover_one_object_many_per_wave_and_the_range_ends():
+    assert want_of("lattice_joined")[2].shape[0] == 1 and want_of("duplicates")[2].shape[0] == 1 and want_of("chain_cut")[2].shape[0] == 1
+    assert want_of("sizes_33_64")[2].shape[0] == 32 and want_of("count2049")[2].shape[0] == 218
+    t = want_of("range_ends_t2")[2]
+    assert t["lo"].min() == -32768 and t["hi"].max() == 32767
+    assert ((CASES["count2049"][1][:, 4].astype(np.int64) & 0xFF00) != 0).all(), "the high byte of short 4 is set on every record"
+
+
+def test_lattice_of_131072_against_its_own_arithmetic(arena):
+    """64 x 64 x 32, pitch 1, tolerance 1, x in 32704..32767, y in -32768..-32705, shuffled: one object whose x and y sums leave
+    an int32 in either sign (65 536 such records would stay just inside it)."""
+    g = np.indices((64, 64, 32)).reshape(3, -1).T + np.array([32704, -32768, -16])
+    rec = RC.with_colour(K.shuffled(g, 31))
+    n = rec.shape[0]
+    assert n == N_MAX
+    got = arena.run(rec, (1, n, n))
+    xyz = rec[:, :3].astype(np.int64)
+    want = np.zeros(1, CLUSTER_OBJECT_DTYPE)
+    want[0]["label"], want[0]["size"] = 0, n
+    want[0]["lo"], want[0]["hi"] = (32704, -32768, -16), (32767, -32705, 15)
+    want[0]["sum_xyz"] = xyz.sum(axis=0)
+    want[0]["sum_rgb"] = NO.rgb(rec).sum(axis=0)
+    # 4.29e9 and -4.29e9: twice what an int32 holds, in either sign
+    assert int(want[0]["sum_xyz"][0]) == n * (32704 + 32767) // 2 > 2 ** 31 and int(want[0]["sum_xyz"][1]) == -n * (32768 + 32705) // 2 < -2 ** 31
+    assert got["n_objects"] == 1 and table_equal(got["table"], want), (got["table"], want)
+    assert (got["object_of"] == 0).all() and got["kept"] == n and (got["out"] == rec).all()
+    assert got["stats"] == {"considered": n, "clusters": 1, "kept_clusters": 1, "largest": n, "kept": n}
+    # nobody passes: no object, every record -1
+    got = arena.run(rec, (1, 1, n - 1))
+    assert got["n_objects"] == 0 and got["table"].shape[0] == 0 and (got["object_of"] == -1).all() and got["kept"] == 0
+
+
+def test_a_table_smaller_than_the_object_count(arena):
+    rec, _ = K.sizes_cloud()
+    params = (2, 33, 0)
+    _, _, _, lab, sizes = K.reference("sizes_33_64")         # the same cloud and tolerance: the same labels
+    table, object_of = NO.objects_from_labels(rec, lab, sizes, params[1], params[2])
+    assert table.shape[0] == 38 and object_of.max() == 37
+    got = arena.run(rec, params, max_objects=16)
+    check(got, table, object_of, max_objects=16)
+    assert got["n_objects"] == 38 and got["table"].shape[0] == 16 and got["object_of"].max() == 37
+    for null_table in (False, True):
+        got = arena.run(rec, params, max_objects=0, null_table=null_table)
+        check(got, table, object_of, max_objects=0)
+        assert got["n_objects"] == 38 and got["table"].shape[0] == 0
+
+
+def test_every_combination_of_the_optional_outputs(arena):
+    for name in ("count2049", "sizes_33_64"):
+        rec, params, table, object_of, out, stats = want_of(name)
+        for with_out, with_stats, with_object_of in ((True, False, True), (False, False, True), (False, True, True), (True, True, False),
+                                                     (False, False, False)):
+            got = arena.run(rec, params, with_out=with_out, with_stats=with_stats, with_object_of=with_object_of)
+            check(got, table, object_of, out if with_out else None, stats if with_stats else None)
+
+
+def test_counted_form_reads_its_count_on_the_device(arena):
+    name = "count2049"
+    rec, params, table, object_of, out, stats = want_of(name)
+    n, used = rec.shape[0], 1000
+    # behind the count: copies of members, which would grow the clusters they belong to and join none
+    padded = np.concatenate([rec[:used], rec[:n - used]])
+    lab, sizes, _ = N.labels(rec[:used], params[0])
+    t_want, o_want = NO.objects_from_labels(rec[:used], lab, sizes, params[1], params[2])
+    f_want, _, s_want = N.filter_from_labels(rec[:used], lab, sizes, params[1], params[2])
+    assert 0 < t_want.shape[0] < table.shape[0]
+    check(arena.run(padded, params, d_count=used, max_points=n), t_want, o_want, f_want, s_want)
+    check(arena.run(padded, params, d_count=used, max_points=n, with_out=False, with_stats=False), t_want, o_want)
+    got = arena.run(rec, params, d_count=0, max_points=n)
+    assert got["n_objects"] == 0 and got["kept"] == 0 and got["stats"] == dict.fromkeys(CLUSTER_STATS_FIELDS, 0)
+    for d_count in (n + 1000, 2 ** 31 - 1):                  # clamped to max_points
+        check(arena.run(rec, params, d_count=d_count, max_points=n), table, object_of, out, stats)
+    check(arena.run(rec, params, d_count=-5, max_points=n), table[:0], object_of[:0])
+
+
+@pytest.mark.parametrize("name", ["count2049", "lattice_joined", "sizes_33_64", "chain"])
+def test_two_runs_give_identical_bytes(arena, name):
+    _, rec, params, _ = CASES[name]
+    a, b = arena.run(rec, params), arena.run(rec, params)
+    assert a["n_objects"] == b["n_objects"] and a["table"].tobytes() == b["table"].tobytes()
+    assert a["object_of"].tobytes() == b["object_of"].tobytes() and a["out"].tobytes() == b["out"].tobytes() and a["stats"] == b["stats"]
+
+
+def test_workspace_is_shared_with_the_other_filters(arena):
+    ctx = arena.ctx
+    rec, params, table, object_of, _, _ = want_of("count2049")
+    cube = RC.cube(400, 1)[:2049]
+    for _ in range(2):
+        assert (ctx.radius_outlier(cube, 20, 3) == NR.radius_outlier(cube, 20, 3)).all()
+        got, n_objects, got_of = ctx.cluster_objects(rec, *params)
+        assert n_objects == table.shape[0] and table_equal(got, table) and (got_of == object_of).all()
+        s_want, _, s_stats = NS.stat_outlier(cube, 3, 1000, 100)
+        s_got, s_block = ctx.stat_outlier(cube, 3, 1000, 100)
+        assert s_got.shape == s_want.shape and (s_got == s_want).all() and s_block == s_stats
+
+
+def test_host_form(arena):
+    ctx = arena.ctx
+    for name in ("count2049", "sizes_33_64", "count0", "count1", "range_ends_t2", "extremes_t1"):
+        rec, params, table, object_of, _, _ = want_of(name)
+        got, n_objects, got_of = ctx.cluster_objects(rec, *params)
+        assert n_objects == table.shape[0] and table_equal(got, table) and (got_of == object_of).all(), name
+    rec, params, table, object_of, _, _ = want_of("sizes_33_64")
+    got, n_objects, got_of = ctx.cluster_objects(rec, *params, max_objects=5)
+    assert n_objects == 32 and table_equal(got, table[:5]) and (got_of == object_of).all()
+    # object_of NULL, no table
+    cnt = C.c_int(-1)
+    P = ClusterParams.make(*params)
+    p = np.ascontiguousarray(rec)
+    assert ctx._lib.pcs_cluster_objects(ctx._h, p.ctypes.data, rec.shape[0], C.byref(P), None, 0, C.byref(cnt), None) == 0
+    assert cnt.value == 32
+
+
+def test_kernel_timing_yields_one_interval_per_launch(arena):
+    ctx = arena.ctx
+    rec, params, table, object_of, out, stats = want_of("count257")
+    ctx.kernel_timing(True)
+    try:
+        for with_out, with_stats, launches in ((False, False, CLUSTER_OBJECT_LAUNCHES), (True, False, CLUSTER_OBJECT_OUT_LAUNCHES),
+                                               (True, True, CLUSTER_OBJECT_OUT_LAUNCHES + 1)):
+            ctx.kernel_times_ms()                # drain
+            got = arena.run(rec, params, with_out=with_out, with_stats=with_stats)
+            times = ctx.kernel_times_ms()
+            assert len(times) == launches and all(t >= 0 for t in times), (len(times), launches)
+            check(got, table, object_of)
+    finally:
+        ctx.kernel_timing(False)
+
+
+def test_zero_records(arena):
+    empty = np.zeros((0, 5), np.int16)
+    got = arena.run(empty, (20, 1, 0))
+    assert got["n_objects"] == 0 and got["kept"] == 0 and got["stats"] == dict.fromkeys(CLUSTER_STATS_FIELDS, 0)
+    got = arena.run(empty, (20, 1, 0), d_count=7, max_points=0)
+    assert got["n_objects"] == 0 and got["kept"] == 0 and got["stats"] == dict.fromkeys(CLUSTER_STATS_FIELDS, 0)
+    got = arena.run(empty, (20, 1, 0), with_out=False, with_stats=False)
+    assert got["n_objects"] == 0
+
+
+def test_refusals_launch_nothing_and_write_nothing(arena):
+    ctx = arena.ctx
+    _, rec, params, _ = CASES["count2049"]
+    n = rec.shape[0]
+    d_in, d_out, d_tab, d_of, d_st = arena.inp + 4, arena.out + 4, arena.table, arena.object_of, arena.stats
+    d_nobj, d_cnt, d_n = arena.words, arena.words + 4, arena.words + 8
+    M = 64
+    ctx.memcpy_h2d(d_in, np.ascontiguousarray(rec))
+    ctx.memcpy_h2d(arena.out, np.full(4 + 10 * n + GUARD, 0xA5, np.uint8))
+    ctx.memcpy_h2d(arena.table, np.full(80 * M + GUARD, 0xA5, np.uint8))
+    ctx.memcpy_h2d(arena.object_of, np.full(n + GUARD // 4, SENTINEL, np.int32))
+    ctx.memcpy_h2d(arena.words, np.array([SENTINEL, SENTINEL, n, SENTINEL], np.int32))
+    ctx.memcpy_h2d(arena.stats, np.full(16, STATS_SENTINEL, np.int64))
+    shorts = POINT_SHORTS * n
+    tol, lo, hi = 20, 5, 9
+    good = ClusterParams.make(tol, lo, hi)
+
+    def out_of(**change):
+        kw = dict(objects=d_tab, max_objects=M, n_objects=d_nobj, object_of=d_of, out=d_out, out_shorts=shorts, out_points=d_cnt, stats=d_st)
+        kw.update(change)
+        return ClusterObjectsOut.make(**kw)
+
+    ok = out_of()
+    bad_params = [(ClusterParams.make(0, lo, hi), "tolerance_mm"), (ClusterParams.make(1001, lo, hi), "tolerance_mm"),
+                  (ClusterParams.make(tol, 0, hi), "min_size"), (ClusterParams.make(tol, lo, -1), "max_size"),
+                  (ClusterParams.make(tol, lo, lo - 1), "max_size"), (ClusterParams.make(tol, lo, hi, reserved=1), "reserved"), (None, "params")]
+    bad_outs = [(None, "out is NULL"),
+                (out_of(max_objects=-1), "max_objects"), (out_of(max_objects=CLUSTER_OBJECTS_MAX + 1), "max_objects"),
+                (out_of(objects=0), "out->objects"), (out_of(objects=d_tab + 4), "out->objects"),
+                (out_of(reserved=1), "out->reserved"),
+                (out_of(out=0), "out->out"), (out_of(out_points=0), "out->out_points"),
+                (out_of(n_objects=0), "out->n_objects"), (out_of(n_objects=d_nobj + 2), "out->n_objects"),
+                (out_of(object_of=d_of + 2), "out->object_of"),
+                (out_of(out=d_out + 1), "out->out"), (out_of(out_points=d_cnt + 2), "out->out_points"),
+                (out_of(stats=d_st + 4), "out->stats"), (out_of(out_shorts=shorts - 1), "out_shorts"),
+                (out_of(out=d_in), "overlap"), (out_of(out=d_in + 10 * n - 2), "overlap"),
+                (out_of(out_points=d_out + 8), "overlap"), (out_of(stats=d_out + 4), "overlap"),
+                (out_of(objects=d_in + 4), "overlap"), (out_of(objects=d_out + 4), "overlap"),
+                (out_of(n_objects=d_in + 8), "overlap"), (out_of(n_objects=d_cnt), "overlap"), (out_of(n_objects=d_tab + 8), "overlap"),
+                (out_of(object_of=d_in + 8), "overlap"), (out_of(object_of=d_out + 8), "overlap"), (out_of(object_of=d_tab + 16), "overlap"),
+                (out_of(object_of=d_st - 4 * n + 8), "overlap"), (out_of(stats=d_tab + 8), "overlap"),
+                (out_of(out=0, out_points=0, out_shorts=0, n_objects=d_st + 8), "overlap"),
+                (out_of(out=0, out_points=0, out_shorts=0, object_of=d_in + 8), "overlap")]
+    plain = [((d_in, n, P, ok), word) for P, word in bad_params] + [((d_in, n, good, O), word) for O, word in bad_outs] + [
+        ((d_in, -1, good, ok), "n_points"), ((0, n, good, ok), "d_payload"), ((d_in + 1, n, good, ok), "d_payload"),
+        ((d_in, -1, good, out_of(out=0, out_points=0, out_shorts=0)), "n_points"),
+        ((0, n, good, out_of(out=0, out_points=0, out_shorts=0)), "d_payload"),
+        ((d_in + 1, n, good, out_of(out=0, out_points=0, out_shorts=0)), "d_payload")]
+    for args, word in plain:
+        with pytest.raises(PcsError) as e:
+            ctx.cluster_objects_device(*args)
+        assert e.value.status == -1 and word in str(e.value) and "pcs_cluster_objects_device:" in str(e.value), (word, str(e.value))
+    counted = [((d_in, d_n, n, P, ok), word) for P, word in bad_params] + [((d_in, d_n, n, good, O), word) for O, word in bad_outs] + [
+        ((d_in, 0, n, good, ok), "d_n_points"), ((d_in, d_n + 2, n, good, ok), "d_n_points"), ((d_in, d_n, -1, good, ok), "max_points"),
+        ((d_in, d_out + 8, n, good, ok), "overlap"), ((d_in, d_cnt, n, good, ok), "overlap"), ((d_in, d_nobj, n, good, ok), "overlap"),
+        ((d_in, d_st + 16, n, good, ok), "overlap"), ((d_in, d_tab + 8, n, good, ok), "overlap"), ((d_in, d_of + 8, n, good, ok), "overlap")]
+    for args, word in counted:
+        with pytest.raises(PcsError) as e:
+            ctx.cluster_objects_device_counted(*args)
+        assert e.value.status == -1 and word in str(e.value) and "pcs_cluster_objects_device_counted:" in str(e.value), (word, str(e.value))
+    # the host form
+    lib, h = ctx._lib, ctx._h
+    p = np.ascontiguousarray(rec)
+    h_tab = np.full(80 * M, 0xA5, np.uint8)
+    h_of = np.full(n, SENTINEL, np.int32)
+    cnt = C.c_int(SENTINEL)
+    g, tp = C.byref(good), C.cast(h_tab.ctypes.data, C.POINTER(ClusterObject))
+    host = [((p.ctypes.data, n, C.byref(P) if P is not None else None, tp, M, C.byref(cnt), h_of.ctypes.data), word) for P, word in bad_params] + [
+        ((p.ctypes.data, -3, g, tp, M, C.byref(cnt), h_of.ctypes.data), "n_points"),
+        ((None, n, g, tp, M, C.byref(cnt), h_of.ctypes.data), "payload"),
+        ((p.ctypes.data, n, g, None, M, C.byref(cnt), h_of.ctypes.data), "objects"),
+        ((p.ctypes.data, n, g, tp, -1, C.byref(cnt), h_of.ctypes.data), "max_objects"),
+        ((p.ctypes.data, n, g, tp, CLUSTER_OBJECTS_MAX + 1, C.byref(cnt), h_of.ctypes.data), "max_objects"),
+        ((p.ctypes.data, n, g, tp, M, None, h_of.ctypes.data), "n_objects"),
+        ((p.ctypes.data, n, g, tp, M, C.byref(cnt), h_of.ctypes.data + 2), "object_of"),
+        ((p.ctypes.data, n, g, tp, M, C.byref(cnt), p.ctypes.data + 8), "overlap"),
+        ((p.ctypes.data, n, g, C.cast(h_of.ctypes.data + 8, C.POINTER(ClusterObject)), M, C.byref(cnt), h_of.ctypes.data), "overlap")]
+    for args, word in host:
+        assert lib.pcs_cluster_objects(h, *args) == -1
+        text = lib.pcs_last_error(h).decode()
+        assert word in text and "pcs_cluster_objects:" in text, text
+    assert cnt.value == SENTINEL and (h_tab == 0xA5).all() and (h_of == SENTINEL).all() and (p == rec).all()
+    ctx.synchronize()
+    out = np.empty(4 + 10 * n + GUARD, np.uint8)
+    tab = np.empty(80 * M + GUARD, np.uint8)
+    oo = np.empty(n + GUARD // 4, np.int32)
+    words = np.empty(4, np.int32)
+    back = np.empty((n, 5), np.int16)
+    block = np.empty(16, np.int64)
+    ctx.memcpy_d2h(out, arena.out)
+    ctx.memcpy_d2h(tab, arena.table)
+    ctx.memcpy_d2h(oo, arena.object_of)
+    ctx.memcpy_d2h(words, arena.words)
+    ctx.memcpy_d2h(back, d_in)
+    ctx.memcpy_d2h(block, arena.stats)
+    assert (out == 0xA5).all() and (tab == 0xA5).all() and (oo == SENTINEL).all() and (back == rec).all() and (block == STATS_SENTINEL).all()
+    assert words.tolist() == [SENTINEL, SENTINEL, n, SENTINEL]

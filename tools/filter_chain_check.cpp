@@ -1,6 +1,7 @@
 // filter_chain_check.cpp — pointcloud_stitching_amd/cli/pcs_filter_chain.h over host-memory fakes of the pcs_* calls it makes: which
 // entry point every stage gets, with which pointers, counts and sizes, what comes out and what -t prints, over all 16 subsets of
-// -O -K -M -E and a host-count or device-count start. A stand-alone program: no GPU, no library, nothing loaded into Python.
+// -O -K -M -E and a host-count or device-count start, and every subset with -E again with -L (the objects form of the cluster call: the same
+// cloud out, the table and its count in blocks of the chain's own, the `Objects:` line and the file's lines). A stand-alone program: no GPU, no library, nothing loaded into Python.
 //
 //   make -C pointcloud_stitching_amd/cli ../../tools/bin/filter_chain_check && tools/bin/filter_chain_check
 //   (.../filter_chain_check_asan: the same under the host sanitizers)
@@ -29,6 +30,7 @@ struct Call {
     int stage; bool counted;
     const int16_t* in; const int32_t* d_n; int n_points, max_points, tag;
     int16_t* out; size_t out_shorts; int32_t* d_n_out; void *block, *models;
+    pcs_cluster_object* objects = nullptr; int max_objects = 0; int32_t* d_n_objects = nullptr;      // the objects form of the cluster call; else nullptr, 0, nullptr
 };
 static std::vector<Call> g_calls;
 
@@ -135,6 +137,34 @@ int pcs_cluster_filter_device_counted(pcs_ctx*, const int16_t* in, const int32_t
     if (rc == PCS_OK) fill(st, a, b);
     return rc;
 }
+// the objects form: the filter's fake over the struct's output, and kFakeObjects objects of which the table takes what it holds
+static const int kFakeObjects = 5;
+static pcs_cluster_object fake_object(int k, int kept)
+{
+    return pcs_cluster_object{10 * k, kept + k, {(int16_t)-k, (int16_t)(k - 7), 3}, {(int16_t)(k + 1), 8, (int16_t)(9 * k)}, 0,
+                              {-1000000000000ll * k, 5ll * k, -6}, {255ll * k, 1, 70000000000ll}, 0};
+}
+static int fake_objects(Call c, const pcs_cluster_objects_out* o)
+{
+    int a, b;
+    c.out = o->out; c.out_shorts = o->out_shorts; c.d_n_out = o->out_points; c.block = o->stats;
+    c.objects = o->objects; c.max_objects = o->max_objects; c.d_n_objects = o->n_objects;
+    const int rc = fake_stage(c, &a, &b);
+    if (rc != PCS_OK) return rc;
+    fill(o->stats, a, b);
+    *o->n_objects = kFakeObjects;
+    for (int k = 0; k < kFakeObjects && k < o->max_objects; k++) o->objects[k] = fake_object(k, b);
+    return rc;
+}
+int pcs_cluster_objects_device(pcs_ctx*, const int16_t* in, int n, const pcs_cluster_params* p, const pcs_cluster_objects_out* o)
+{
+    return fake_objects({3, false, in, nullptr, n, 0, p->tolerance_mm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr}, o);
+}
+int pcs_cluster_objects_device_counted(pcs_ctx*, const int16_t* in, const int32_t* d_n, int max_points, const pcs_cluster_params* p,
+                                       const pcs_cluster_objects_out* o)
+{
+    return fake_objects({3, true, in, d_n, 0, max_points, p->tolerance_mm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr}, o);
+}
 }
 
 // ---- the check ---------------------------------------------------------------------------------------------------------------------
@@ -142,10 +172,11 @@ enum Start { kHost, kDeviceFewer, kDeviceFull };
 static const char* const kStartName[] = {"host count", "device count below capacity", "device count at capacity"};
 static const int kTag[kStageCount] = {11, 22, 33, 44};      // radius_mm, mean_k, distance_mm, tolerance_mm
 
-static void check(int subset, Start start)
+// max_objects: 0 without -L, else the table's size (below and above the fakes' object count)
+static void check(int subset, Start start, int max_objects = 0)
 {
-    snprintf(g_case, sizeof g_case, "%s%s%s%s%s, %s", subset ? "" : "none", subset & 1 ? "O" : "", subset & 2 ? "K" : "", subset & 4 ? "M" : "",
-             subset & 8 ? "E" : "", kStartName[start]);
+    snprintf(g_case, sizeof g_case, "%s%s%s%s%s%s, %s", subset ? "" : "none", subset & 1 ? "O" : "", subset & 2 ? "K" : "", subset & 4 ? "M" : "",
+             subset & 8 ? "E" : "", max_objects ? "L" : "", kStartName[start]);
     pcs_ctx ctx{0};
     const int capacity = 41, n_in = start == kDeviceFewer ? 29 : capacity;
     // the cloud that enters: first shorts 0..5 in turn (every stage drops some and keeps some), the rest tells the records apart
@@ -163,11 +194,19 @@ static void check(int subset, Start start)
     for (int s = 0; s < kStageCount; s++)
         if (subset >> s & 1) { EXPECT(chain.parse(kStages[s].letter, args[s], why)); n_enabled++; }
     EXPECT(!chain.parse('V', "1", why) && chain.any() == (subset != 0));
+    EXPECT(!chain.objects());
+    if (max_objects) {
+        const std::string arg = "some,file.txt," + std::to_string(max_objects);
+        EXPECT(chain.parse_objects(arg.c_str(), why) && chain.objects() && chain.objects_file == "some,file.txt" &&
+               chain.params.objects.max_objects == max_objects);
+    }
     const size_t out_shorts = (size_t)capacity * PCS_POINT_SHORTS;
     g_live.clear();
     if (subset) EXPECT(chain.allocate(&ctx, out_shorts) == PCS_OK);
     const size_t want_blocks = (size_t)(n_enabled < 2 ? n_enabled : 2) + n_enabled + (subset >> 1 & 1) + (subset >> 2 & 1) + (subset >> 3 & 1);
-    EXPECT(g_live.size() == want_blocks);
+    EXPECT(g_live.size() == want_blocks + (max_objects ? 2 : 0));      // -L: the table and its count word
+    if (max_objects) EXPECT(g_live.count(chain.d_objects) && g_live[chain.d_objects] == (size_t)max_objects * sizeof(pcs_cluster_object) &&
+                            g_live.count(chain.d_n_objects) && g_live[chain.d_n_objects] == 64);
 
     // what the fakes' rule predicts, stage by stage
     std::vector<std::vector<int16_t>> want(1, std::vector<int16_t>(cloud, cloud + (size_t)n_in * PCS_POINT_SHORTS));
@@ -188,6 +227,7 @@ static void check(int subset, Start start)
                       << ", hypothesis " << 70 + r << "\n";
         }
         if (s == 3) lines << "Cluster filter: " << a << " -> " << b << " points (" << 80 + a << " clusters, 3 kept, largest " << 12 + b << ")\n";
+        if (s == 3 && max_objects) lines << "Objects: " << kFakeObjects << " (" << (max_objects < kFakeObjects ? max_objects : kFakeObjects) << " written)\n";
         EXPECT(b > 0 && b < a);      // (a stage that keeps everything or nothing would hide a wrong pointer)
         want.push_back(next);
     }
@@ -216,6 +256,9 @@ static void check(int subset, Start start)
                 if (c.block) EXPECT(g_live.count(c.block) && g_live[c.block] == kStages[s].block_bytes);
                 if (c.models) EXPECT((char*)c.models >= (char*)c.block + sizeof(pcs_plane_stats) &&
                                      (char*)(static_cast<pcs_plane_model*>(c.models) + PCS_PLANE_MAX_PLANES) <= (char*)c.block + g_live[c.block]);
+                // the objects form for the cluster stage under -L alone, with the chain's own table and count word
+                EXPECT((c.objects != nullptr) == (s == 3 && max_objects != 0));
+                if (c.objects) EXPECT(c.objects == chain.d_objects && c.d_n_objects == chain.d_n_objects && c.max_objects == max_objects);
                 prev = Cloud{c.out, c.d_n_out, 0, capacity};
             }
             const std::vector<int16_t>& last = want.back();
@@ -227,6 +270,16 @@ static void check(int subset, Start start)
         const int syncs = g_syncs;
         EXPECT(chain.report(got) && got.str() == lines.str());
         EXPECT(g_calls.size() == (size_t)n_enabled && g_syncs - syncs <= (subset ? 1 : 0));      // report launches nothing
+        if (max_objects) {      // the file: the header, then the written objects as raw integers
+            std::ostringstream file, file_want;
+            const int kept = (int)(want.back().size() / PCS_POINT_SHORTS);
+            std::vector<pcs_cluster_object> table;
+            for (int k = 0; k < kFakeObjects && k < max_objects; k++) table.push_back(fake_object(k, kept));
+            pcs_objects::write(file_want, table.data(), (int)table.size());
+            EXPECT(chain.write_objects(file) && file.str() == file_want.str() && g_calls.size() == (size_t)n_enabled);
+            EXPECT(file.str().rfind("# k label size lo_x lo_y lo_z hi_x hi_y hi_z sum_x sum_y sum_z sum_r sum_g sum_b\n", 0) == 0);
+            if (max_objects >= 2) EXPECT(file.str().find("\n1 10 " + std::to_string(kept + 1) + " -1 -6 3 2 8 9 -1000000000000 5 -6 255 1 70000000000\n") != std::string::npos);
+        }
         for (int i = 0; i < capacity; i++)                                                           // the caller's cloud is read only
             for (int k = 0; k < PCS_POINT_SHORTS; k++) EXPECT(cloud[i * PCS_POINT_SHORTS + k] == (int16_t)(k ? 100 * i + k : i % 6));
     }
@@ -241,7 +294,11 @@ static void check(int subset, Start start)
 int main()
 {
     for (int subset = 0; subset < 16; subset++)
-        for (Start start : {kHost, kDeviceFewer, kDeviceFull}) check(subset, start);
+        for (Start start : {kHost, kDeviceFewer, kDeviceFull}) {
+            check(subset, start);
+            if (subset & 8)
+                for (int max_objects : {3, 5, 1024}) check(subset, start, max_objects);
+        }
     printf(g_failed ? "filter_chain_check: %d check(s) FAILED\n" : "filter_chain_check: all checks passed, no report\n", g_failed);
     fflush(stdout);      // (a leak report at exit must not swallow the lines above)
     return g_failed ? 1 : 0;
