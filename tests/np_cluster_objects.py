@@ -47,6 +47,38 @@ def objects_from_labels(records, lab, sizes, min_size, max_size=0):
     return table, object_of
 
 
+def objects_from_labels_grouped(records, lab, sizes, min_size, max_size=0):
+    """objects_from_labels (the definition) without its loop over the objects, for clouds of millions of records: the passing records
+    sorted by label (stable), one reduceat per word over the runs of equal labels, in int64. The same return, byte for byte
+    (tests/test_cluster_scale_cases_cpu.py)."""
+    assert 1 <= min_size <= N.INT_MAX and (max_size == 0 or min_size <= max_size <= N.INT_MAX)
+    rec = np.asarray(records, np.int16).reshape(-1, 5)
+    n = rec.shape[0]
+    lab = np.asarray(lab, np.int64).reshape(n)
+    sizes = np.asarray(sizes, np.int64).reshape(n)
+    passes = sizes >= min_size
+    if max_size:
+        passes &= sizes <= max_size
+    members = np.nonzero(passes)[0]
+    members = members[np.argsort(lab[members], kind="stable")]
+    by_label = lab[members]
+    starts = np.nonzero(np.concatenate([[True], by_label[1:] != by_label[:-1]]))[0] if members.size else np.zeros(0, np.int64)
+    table = np.zeros(starts.shape[0], OBJECT_DTYPE)
+    object_of = np.full(n, -1, np.int32)
+    if starts.size:
+        xyz = rec[members, :3].astype(np.int64)
+        colour = rgb(rec[members])
+        counts = np.diff(np.concatenate([starts, [members.size]]))
+        object_of[members] = np.repeat(np.arange(starts.shape[0], dtype=np.int32), counts)
+        table["label"] = by_label[starts]                                  # ascending: the runs of a sort by label
+        table["size"] = counts
+        table["lo"] = np.minimum.reduceat(xyz, starts, axis=0)
+        table["hi"] = np.maximum.reduceat(xyz, starts, axis=0)
+        table["sum_xyz"] = np.add.reduceat(xyz, starts, axis=0)
+        table["sum_rgb"] = np.add.reduceat(colour, starts, axis=0)
+    return table, object_of
+
+
 def cluster_objects(records, tolerance_mm, min_size, max_size=0):
     """(the full table, n_objects, object_of)."""
     lab, sizes, _ = N.labels(records, tolerance_mm)

@@ -4,7 +4,8 @@ table, n_objects, object_of and the filtered payload with its count and statisti
 at 16-byte alignment, with 0xA5 guards around the table, behind object_of and around the payload output; one lattice of 131 072
 records against its own arithmetic (sums beyond 32 bits in either sign); a table smaller than the object count; every combination of
 the optional outputs; the counted form; twice for determinism; between the other filters on one context; the host form; the launch
-counts; every refusal. There is no tolerance anywhere."""
+counts; every refusal. There is no tolerance anywhere.
+Clouds of one to 2.7 million records, object ranks beyond max_objects, one object held by every workgroup: tests/test_clusters_scale.py."""
 import ctypes as C
 
 import numpy as np

@@ -4,7 +4,8 @@ tests/cluster_cases.py: at the reference's `buffer + 2` shorts and at 16-byte al
 for one cloud, with guard bytes in front of the output, behind the kept records and behind the worst-case output, twice for
 determinism, with and without a statistics block, through the counted form, the host forms, the labels forms, between the other two
 filters on one context, in front of the voxel grid, and through every refusal. Clouds of at most 4 096 records against the brute
-force, one lattice of 65 536 against its own arithmetic, capacities up to 65 536. There is no tolerance anywhere."""
+force, one lattice of 65 536 against its own arithmetic, capacities up to 65 536. There is no tolerance anywhere.
+Clouds of one to 2.7 million records, where the scans take a second chunk and the union-find is contended: tests/test_clusters_scale.py."""
 import ctypes as C
 
 import numpy as np
