@@ -970,6 +970,104 @@ int pcs_plane_count_inliers_device(pcs_ctx* ctx, const int16_t* d_payload, int n
                                    int64_t* d_counts);
 int pcs_plane_from_points(const int16_t* p0, const int16_t* p1, const int16_t* p2, int distance_mm, pcs_plane_model* model);
 
+/* ---- background model and subtraction on packed payloads (not in the reference) --------------------------------------------------- *
+ * The plane filter takes out a floor and a wall; a fixed rig also sees shelves, a truss, tables, a net — in every frame-set. This is a
+ * change detector against a LEARNED background: one persistent table, learned once, probed per record, no index build per call.
+ * Everything is in the payload's integer millimetres (shorts 0..2 = x, y, z signed; colour is not read); no float anywhere.
+ *   CELL      of a record: floor(v / cell_mm) + 32768 per axis, 0..65535; cell_mm 1..1000. Negative coordinates floor.
+ *   MODEL     a map cell -> seen (uint32 >= 1), a counter `frames`, a sticky `overflow` flag, and its constants cell_mm and max_cells.
+ *   LEARN     of a payload: frames += 1; every DISTINCT cell that holds at least one of its records gets seen += 1 (a new cell enters
+ *               with seen = 1). Zero records still count as a frame. The result depends neither on the record order nor on how often
+ *               a cell is hit within one call. frames stops at PCS_BACKGROUND_FRAMES_MAX: a learn call at the cap is refused.
+ *   OVERFLOW  set when a learn call takes the number of distinct cells above max_cells; it stays set until reset. Which of the surplus
+ *               cells got in is unspecified (and `cells` may then exceed max_cells). There is no hang and no write outside the table.
+ *   SUBTRACT  record i in cell c is BACKGROUND iff some cell c' with |c' - c| <= dilate on every axis has seen[c'] >= min_seen; c' stays
+ *               inside 0..65535 per axis, nothing wraps at the ends of the int16 range. min_seen 1..65535, dilate 0 or 1, mode
+ *               PCS_BACKGROUND_MODE_REMOVE (keep what is NOT background) or PCS_BACKGROUND_MODE_KEEP. With overflow set every record is
+ *               kept, in both modes: a filter must never silently eat a scene because a table was sized too small.
+ * The output of subtract is the kept records in input order, all 10 bytes of each unchanged, their count, and (optional) the statistics
+ * block of eight int64: considered, kept, background (0 on an overflowed model), cells, frames, min_seen, overflow, reserved (0).
+ * Exact and deterministic: the same bytes on every run, whatever order the atomics arrive in (tests/np_background.py restates it as
+ * a Python dict and brute force). DESIGN.md section 3 has the definition and what follows from it.
+ * pcs_background_create: a model on the context's device, empty (frames 0, no cell). cell_mm 1..1000, max_cells
+ *   1..PCS_BACKGROUND_MAX_CELLS_MAX. The table is the model's own allocation, not a context slab: 2048 ceil(2 max_cells / 2048) slots of
+ *   16 bytes, about 32 bytes per max_cells (PCS_ERR_NOMEM if the device has no room). One launch (clear). A model belongs to the
+ *   context that created it: pcs_background_destroy it first, or leave it to that context's pcs_destroy, which frees what is left
+ *   (the pointer is dead afterwards). Any context on the same device may learn into it or subtract with it; calls on one model from
+ *   several contexts are ordered by the caller (streams). pcs_background_reset: the freshly created model again, one launch.
+ * pcs_background_learn_device: asynchronous on the context's stream, no host round trip, one launch (none with n_points 0, which
+ *   still counts as a frame). pcs_background_learn_device_counted: the count is read from *d_n_points (device, 4-byte aligned) when
+ *   the kernel runs, clamped to 0..max_points (max_points 0: nothing launched, a frame). pcs_background_learn: host pointers, staged
+ *   through the context, synchronous.
+ * pcs_background_subtract_device: asynchronous, no host round trip: flag (one probe sequence per record for background, up to 27 with
+ *   dilate 1 for foreground), then the radius filter's ordered compaction (three launches) and, with d_stats, the block: 5 launches, 4
+ *   without. d_out needs room for the worst case: out_shorts >= 5 n_points is checked up front; nothing outside the first 10 * kept
+ *   bytes of d_out is written. *d_out_points (device, 4-byte aligned, required) receives kept; d_stats (device, 8-byte aligned,
+ *   optional) the block. n_points 0 launches nothing and writes a zero count and a zeroed block.
+ *   pcs_background_subtract_device_counted: the count from *d_n_points as above; max_points sizes the workspace, the grids and the
+ *   output check. It takes any counted filter's output and count, and its own feed pcs_voxel_grid_device_counted and the other
+ *   counted filters. pcs_background_subtract: host pointers, staged, synchronous; stats optional (with n_points 0 it reads nothing
+ *   from the device: cells, frames and overflow of the block are 0 then).
+ * pcs_background_info: synchronous (waits for the context's stream): what the model holds now.
+ * pcs_background_export: synchronous; the canonical "PCB1" container: a 32-byte header {"PCB1", uint32 version 1,
+ *   int32 cell_mm, uint32 frames, uint32 cells, 12 zero bytes}, then `cells` entries of 12 bytes {uint16 cx, cy, cz, uint16 0, uint32
+ *   seen}, strictly ascending by key (cx | cy << 16 | cz << 32): the same model is the same bytes on every run and every machine.
+ *   capacity < 32 + 12 cells is PCS_ERR_CAPACITY (pcs_background_export_bound(max_cells) always suffices); an overflowed model is
+ *   PCS_ERR_CAPACITY too: what it holds is unspecified. One gather launch (none for a model without cells); the host sorts.
+ * pcs_background_import: validates (below), then a new model with the container's cell_mm, frames and cells; cells > max_cells is
+ *   PCS_ERR_CAPACITY. Two launches (clear, import; one for an empty container). Synchronous.
+ * pcs_background_validate: host only, no context, no GPU: everything an importer relies on. PCS_ERR_INVALID_ARG with the first violation
+ *   in pcs_last_error(NULL) for: bad magic or version, cell_mm outside 1..1000, frames above the cap, non-zero header padding, a length
+ *   that is not 32 + 12 cells, non-zero entry padding, seen outside 1..frames, keys that do not ascend strictly. Fills *info (optional;
+ *   max_cells = cells, overflow = 0).
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the function and the argument), nothing launched, nothing written: a NULL
+ *   model, a model on another device than the context's, a parameter out of range, reserved != 0, NULL params, a negative count, a
+ *   NULL pointer (payload and output may be NULL with a count of 0), an odd payload or output address, a misaligned count or stats
+ *   address, out_shorts below the worst case, any overlap among the input, output, count and stats ranges, a learn call at the
+ *   frames cap.
+ * Works on every context: flags, crop box, downsample and PCS_FLAG_SCALAR_ARITH are not read. subtract's workspace is the radius
+ *   filter's slab in the context. With pcs_kernel_timing enabled a call yields one interval per launch: create 1, reset 1, learn 1
+ *   (0 with no record capacity), subtract 5 or 4 (0 with no capacity), export 1 (0 for a model without cells), import 2 (1 for a
+ *   container without cells). Measured: DESIGN.md section 10 (f16), profiles/background_probe.txt.                                   */
+#define PCS_BACKGROUND_CELL_MIN       1
+#define PCS_BACKGROUND_CELL_MAX       1000
+#define PCS_BACKGROUND_FRAMES_MAX     65535
+#define PCS_BACKGROUND_MAX_CELLS_MAX  (1 << 26)
+#define PCS_BACKGROUND_MODE_REMOVE    0
+#define PCS_BACKGROUND_MODE_KEEP      1
+typedef struct pcs_background pcs_background;               /* opaque; lives on the context's device */
+typedef struct pcs_background_params {
+    int32_t min_seen, dilate, mode, reserved;               /* reserved is 0 */
+} pcs_background_params;
+struct pcs_background_info {     /* (a tag only: pcs_background_info is also the call's name, as pcs_compressed_info) */
+    int32_t  cell_mm, max_cells;
+    uint32_t cells, frames;
+    int32_t  overflow, reserved;
+};
+struct pcs_background_stats {
+    int64_t considered, kept, background, cells, frames, min_seen, overflow, reserved;
+};
+int pcs_background_create(pcs_ctx* ctx, int cell_mm, int max_cells, pcs_background** out);
+int pcs_background_destroy(pcs_ctx* ctx, pcs_background* bg);
+int pcs_background_reset(pcs_ctx* ctx, pcs_background* bg);
+int pcs_background_learn_device(pcs_ctx* ctx, pcs_background* bg, const int16_t* d_payload, int n_points);
+int pcs_background_learn_device_counted(pcs_ctx* ctx, pcs_background* bg, const int16_t* d_payload, const int32_t* d_n_points,
+                                        int max_points);
+int pcs_background_learn(pcs_ctx* ctx, pcs_background* bg, const int16_t* payload, int n_points);   /* host pointer, staged, synchronous */
+int pcs_background_subtract_device(pcs_ctx* ctx, pcs_background* bg, const int16_t* d_payload, int n_points,
+                                   const pcs_background_params* params, int16_t* d_out, size_t out_shorts, int32_t* d_out_points,
+                                   struct pcs_background_stats* d_stats);
+int pcs_background_subtract_device_counted(pcs_ctx* ctx, pcs_background* bg, const int16_t* d_payload, const int32_t* d_n_points,
+                                           int max_points, const pcs_background_params* params, int16_t* d_out, size_t out_shorts,
+                                           int32_t* d_out_points, struct pcs_background_stats* d_stats);
+int pcs_background_subtract(pcs_ctx* ctx, pcs_background* bg, const int16_t* payload, int n_points, const pcs_background_params* params,
+                            int16_t* out, size_t out_shorts, int* out_points, struct pcs_background_stats* stats);   /* host pointers, staged, synchronous */
+int pcs_background_info(pcs_ctx* ctx, pcs_background* bg, struct pcs_background_info* info);
+size_t pcs_background_export_bound(int max_cells);
+int pcs_background_export(pcs_ctx* ctx, pcs_background* bg, void* out, size_t capacity, size_t* out_bytes);
+int pcs_background_import(pcs_ctx* ctx, const void* bytes, size_t n_bytes, int max_cells, pcs_background** out);
+int pcs_background_validate(const void* bytes, size_t n_bytes, struct pcs_background_info* info);
+
 /* ---- extrinsics refinement: nearest-neighbour alignment sums, the rigid fit, the ICP loop (not in the reference) ---------------- *
  * transform[i] comes from four surveyed markers (calibration.py); these calls refine it from the data: move one camera's payload
  * onto another's where they overlap. DESIGN.md section 3 "Alignment sums" has the definition and what follows from it.

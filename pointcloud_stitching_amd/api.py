@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -55,6 +55,108 @@ def compressed_info(container) -> CompressedInfo:
         d = lib.pcs_last_error(None)
         raise PcsError(rc, d.decode() if d else "")
     return info
+
+
+def _as_bytes_array(container) -> np.ndarray:
+    return np.ascontiguousarray(np.frombuffer(container, np.uint8) if isinstance(container, (bytes, bytearray, memoryview)) else container)
+
+
+def background_export_bound(max_cells: int) -> int:
+    """pcs_background_export_bound: the largest "PCB1" container of a model of max_cells cells (32 + 12 max_cells)."""
+    return int(_libmod.load().pcs_background_export_bound(int(max_cells)))
+
+
+def background_validate(container) -> dict:
+    """pcs_background_validate: validate a "PCB1" container (bytes or a uint8 array) on the host — no context, no GPU. Returns
+    cell_mm, cells and frames; raises PcsError (PCS_ERR_INVALID_ARG) whose text names the first violation."""
+    lib = _libmod.load()
+    buf = _as_bytes_array(container)
+    info = BackgroundInfo()
+    rc = lib.pcs_background_validate(buf.ctypes.data if buf.nbytes else None, buf.nbytes, C.byref(info))
+    if rc != 0:
+        d = lib.pcs_last_error(None)
+        raise PcsError(rc, d.decode() if d else "")
+    return info.as_dict()
+
+
+class Background:
+    """A background model on a context's device (pcs_background_*): learn frame-sets into it, subtract it from others. Created by
+    PcsContext.background_create / background_import; close() it (or leave a `with` block) before the context closes, which frees
+    what is left."""
+
+    def __init__(self, ctx: "PcsContext", handle: int):
+        self._ctx = ctx
+        self._h = handle
+
+    @property
+    def handle(self) -> int:
+        return self._h or 0
+
+    def close(self) -> None:
+        if self._h and self._ctx._h:
+            self._ctx._check(self._ctx._lib.pcs_background_destroy(self._ctx._h, self._h))
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _call(self, fn, *args) -> None:
+        self._ctx._check(fn(self._ctx._h, self._h, *args))
+
+    def reset(self) -> None:
+        self._call(self._ctx._lib.pcs_background_reset)
+
+    def info(self) -> dict:
+        """cell_mm, max_cells, cells, frames, overflow — synchronous."""
+        info = BackgroundInfo()
+        self._call(self._ctx._lib.pcs_background_info, C.byref(info))
+        return info.as_dict()
+
+    def learn(self, payload: np.ndarray) -> None:
+        """Packed records (int16 [n,5]) as one frame-set (pcs_background_learn: host array, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        self._call(self._ctx._lib.pcs_background_learn, _ptr(p) if p.shape[0] else None, p.shape[0])
+
+    def learn_device(self, d_payload: int, n_points: int) -> None:
+        self._call(self._ctx._lib.pcs_background_learn_device, d_payload or None, int(n_points))
+
+    def learn_device_counted(self, d_payload: int, d_n_points: int, max_points: int) -> None:
+        self._call(self._ctx._lib.pcs_background_learn_device_counted, d_payload or None, d_n_points or None, int(max_points))
+
+    def subtract(self, payload: np.ndarray, min_seen: int, dilate: int = 1, mode: int = 0):
+        """Packed records (int16 [n,5]) -> (the records that are not background (mode 0) or are (mode 1), input order; the statistics
+        block as a dict) (pcs_background_subtract: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        out = np.zeros((max(p.shape[0], 1), POINT_SHORTS), np.int16)
+        cnt = C.c_int(0)
+        stats = BackgroundStats()
+        params = BackgroundParams.make(min_seen, dilate, mode)
+        self._call(self._ctx._lib.pcs_background_subtract, _ptr(p), p.shape[0], C.byref(params), _ptr(out), p.shape[0] * POINT_SHORTS,
+                   C.byref(cnt), C.byref(stats))
+        return out[:cnt.value].copy(), stats.as_dict()
+
+    def subtract_device(self, d_payload: int, n_points: int, params: BackgroundParams, d_out: int, out_shorts: int, d_out_points: int,
+                        d_stats: int = 0) -> None:
+        """Asynchronous; device pointers as ints; *d_out_points (int32, required) receives the kept count, d_stats (eight int64,
+        optional) the statistics block. params may be None (refused). See pcs_background_subtract_device."""
+        self._call(self._ctx._lib.pcs_background_subtract_device, d_payload or None, int(n_points),
+                   C.byref(params) if params is not None else None, d_out or None, out_shorts, d_out_points or None, d_stats or None)
+
+    def subtract_device_counted(self, d_payload: int, d_n_points: int, max_points: int, params: BackgroundParams, d_out: int,
+                                out_shorts: int, d_out_points: int, d_stats: int = 0) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run."""
+        self._call(self._ctx._lib.pcs_background_subtract_device_counted, d_payload or None, d_n_points or None, int(max_points),
+                   C.byref(params) if params is not None else None, d_out or None, out_shorts, d_out_points or None, d_stats or None)
+
+    def export(self) -> bytes:
+        """The canonical "PCB1" container (pcs_background_export): synchronous. PcsError (PCS_ERR_CAPACITY) for an overflowed model."""
+        buf = np.zeros(background_export_bound(self.info()["max_cells"]), np.uint8)
+        n = C.c_size_t(0)
+        self._call(self._ctx._lib.pcs_background_export, _ptr(buf), buf.nbytes, C.byref(n))
+        return buf[:n.value].tobytes()
 
 
 def plane_from_points(p0, p1, p2, distance_mm: int) -> dict:
@@ -723,6 +825,20 @@ class PcsContext:
         self._check(self._lib.pcs_cluster_objects_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
                                                                  C.byref(params) if params is not None else None,
                                                                  C.byref(out) if out is not None else None))
+
+    # -- background model and subtraction (defined by this build; see include/pcs_hip.h) ------------
+    def background_create(self, cell_mm: int, max_cells: int) -> Background:
+        """An empty background model on this context's device (pcs_background_create)."""
+        h = C.c_void_p()
+        self._check(self._lib.pcs_background_create(self._h, int(cell_mm), int(max_cells), C.byref(h)))
+        return Background(self, h.value)
+
+    def background_import(self, container, max_cells: int) -> Background:
+        """A model from a "PCB1" container (bytes or a uint8 array), validated first (pcs_background_import)."""
+        buf = _as_bytes_array(container)
+        h = C.c_void_p()
+        self._check(self._lib.pcs_background_import(self._h, buf.ctypes.data if buf.nbytes else None, buf.nbytes, int(max_cells), C.byref(h)))
+        return Background(self, h.value)
 
     # -- plane segmentation (defined by this build; see include/pcs_hip.h) --------------------------
     def plane_segment(self, payload: np.ndarray, params: PlaneParams):

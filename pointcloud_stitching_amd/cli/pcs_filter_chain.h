@@ -1,4 +1,4 @@
-// pcs_filter_chain.h — the post-stitch filters of pcs-multicamera-optimized, -O -K -M -E in that order, as one chain ahead of -V.
+// pcs_filter_chain.h — the post-stitch filters of pcs-multicamera-optimized, -X -O -K -M -E in that order, as one chain ahead of -V.
 // Plain C++17 over include/pcs_hip.h. The rule every stage follows, stated once:
 //
 //   A stage reads the output of the stage in front of it. If that stage left its record count on the device, the counted form is
@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "pcs_background.h"
 #include "pcs_cluster.h"
 #include "pcs_objects.h"
 #include "pcs_outlier.h"
@@ -36,6 +37,14 @@ struct Cloud {
 };
 
 struct Params {
+    // -X FILE: the option's words, then what allocate() makes of them and the file (the model on the device, min_seen from its frames)
+    struct {
+        std::string file;
+        int min_percent = 0, dilate = 0;
+        pcs_background* model = nullptr;
+        pcs_background_params params{};
+        uint32_t frames = 0;
+    } background;
     int radius_mm = 0, min_neighbors = 0;
     pcs_stat_outlier_params stat{};
     pcs_plane_params plane{};
@@ -59,17 +68,33 @@ struct Stage {
     // the plain or the counted library entry, by whether `in` has a device count
     int (*call)(pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void* d_block);
     // the -t line(s): `block` is the host's copy, n_in / n_kept the counts in front of and behind the stage
-    void (*print)(std::ostream& os, const void* block, int n_in, int n_kept);
+    void (*print)(std::ostream& os, const Params& p, const void* block, int n_in, int n_kept);
 };
 
 inline const Stage kStages[] = {
+    {'X', "background model", pcs_background_cli::help,
+     [](const char* arg, Params& p, std::string& why) {
+         return pcs_background_cli::parse_subtract(arg, p.background.file, p.background.min_percent, p.background.dilate, why);
+     }, sizeof(pcs_background_stats),
+     [](pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void* d_block) {
+         pcs_background_stats* d_stats = static_cast<pcs_background_stats*>(d_block);
+         const auto& b = p.background;
+         return in.d_n ? pcs_background_subtract_device_counted(ctx, b.model, in.d, in.d_n, in.capacity, &b.params, d_out, out_shorts, d_n_out, d_stats)
+                       : pcs_background_subtract_device(ctx, b.model, in.d, in.n, &b.params, d_out, out_shorts, d_n_out, d_stats);
+     },
+     [](std::ostream& os, const Params& p, const void* block, int, int) {
+         pcs_background_stats st;
+         memcpy(&st, block, sizeof st);
+         os << "Background subtraction: " << st.considered << " -> " << st.kept << " points (" << st.cells << " cells, seen >= " << st.min_seen
+            << " of " << st.frames << ", dilate " << p.background.dilate << ")" << std::endl;
+     }},
     {'O', "outlier filter", pcs_outlier::help,
      [](const char* arg, Params& p, std::string& why) { return pcs_outlier::parse(arg, p.radius_mm, p.min_neighbors, why); }, 0,
      [](pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void*) {
          return in.d_n ? pcs_radius_outlier_device_counted(ctx, in.d, in.d_n, in.capacity, p.radius_mm, p.min_neighbors, d_out, out_shorts, d_n_out)
                        : pcs_radius_outlier_device(ctx, in.d, in.n, p.radius_mm, p.min_neighbors, d_out, out_shorts, d_n_out);
      },
-     [](std::ostream& os, const void*, int n_in, int n_kept) { os << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl; }},
+     [](std::ostream& os, const Params&, const void*, int n_in, int n_kept) { os << "Outlier removal: " << n_in << " -> " << n_kept << " points" << std::endl; }},
     {'K', "outlier filter", pcs_statoutlier::help,
      [](const char* arg, Params& p, std::string& why) { return pcs_statoutlier::parse(arg, p.stat, why); }, sizeof(pcs_stat_outlier_stats),
      [](pcs_ctx* ctx, const Params& p, const Cloud& in, int16_t* d_out, size_t out_shorts, int32_t* d_n_out, void* d_block) {
@@ -77,7 +102,7 @@ inline const Stage kStages[] = {
          return in.d_n ? pcs_stat_outlier_device_counted(ctx, in.d, in.d_n, in.capacity, &p.stat, d_out, out_shorts, d_n_out, d_stats)
                        : pcs_stat_outlier_device(ctx, in.d, in.n, &p.stat, d_out, out_shorts, d_n_out, d_stats);
      },
-     [](std::ostream& os, const void* block, int, int) {
+     [](std::ostream& os, const Params&, const void* block, int, int) {
          pcs_stat_outlier_stats st;
          memcpy(&st, block, sizeof st);
          os << "Statistical outlier removal: " << st.considered << " -> " << st.kept << " points (dense " << st.dense << ", threshold "
@@ -90,7 +115,7 @@ inline const Stage kStages[] = {
          return in.d_n ? pcs_plane_segment_device_counted(ctx, in.d, in.d_n, in.capacity, &p.plane, d_out, out_shorts, d_n_out, b->models, &b->stats)
                        : pcs_plane_segment_device(ctx, in.d, in.n, &p.plane, d_out, out_shorts, d_n_out, b->models, &b->stats);
      },
-     [](std::ostream& os, const void* block, int, int) {
+     [](std::ostream& os, const Params&, const void* block, int, int) {
          PlaneBlock b;
          memcpy(&b, block, sizeof b);
          const pcs_plane_stats& st = b.stats;
@@ -114,7 +139,7 @@ inline const Stage kStages[] = {
          return in.d_n ? pcs_cluster_filter_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, d_out, out_shorts, d_n_out, d_stats)
                        : pcs_cluster_filter_device(ctx, in.d, in.n, &p.cluster, d_out, out_shorts, d_n_out, d_stats);
      },
-     [](std::ostream& os, const void* block, int, int) {
+     [](std::ostream& os, const Params&, const void* block, int, int) {
          pcs_cluster_stats st;
          memcpy(&st, block, sizeof st);
          os << "Cluster filter: " << st.considered << " -> " << st.kept << " points (" << st.clusters << " clusters, " << st.kept_clusters
@@ -122,7 +147,9 @@ inline const Stage kStages[] = {
      }},
 };
 constexpr int kStageCount = sizeof kStages / sizeof kStages[0];
+constexpr int kBackgroundStage = 0;                 // 'X': the stage of -X FILE
 constexpr int kClusterStage = kStageCount - 1;      // 'E': the stage -L rides on
+static_assert(kStageCount == 5, "X O K M E");
 
 struct Chain {
     Params params;
@@ -137,11 +164,38 @@ struct Chain {
     std::string objects_file;              // -L: where the table goes ("-": stdout); empty: no -L
     void* d_objects = nullptr;             // ... the table (params.objects.max_objects entries) and its count word
     void* d_n_objects = nullptr;
+    // -X learn: the option's words and the model allocate() creates; -X FILE: the file's bytes (load_background), imported by allocate()
+    struct { std::string file; int cell_mm = 0, max_cells = 0; pcs_background* model = nullptr; } learn;
+    std::vector<char> background_bytes;
 
+    bool learning() const { return learn.cell_mm != 0; }
     bool any() const
     {
         for (bool e : enabled) if (e) return true;
-        return false;
+        return learning();
+    }
+
+    // -X's argument, either form. false: `why` says what is wrong with it.
+    bool parse_background(const char* arg, std::string& why)
+    {
+        const bool is_learn = strncmp(arg, "learn:", 6) == 0;
+        if (learning() || enabled[kBackgroundStage]) {
+            why = is_learn == learning() ? "the option was given twice" : "one run either learns a model or subtracts one: give one form of -X";
+            return false;
+        }
+        if (is_learn) return pcs_background_cli::parse_learn(arg + 6, learn.file, learn.cell_mm, learn.max_cells, why);
+        return parse('X', arg, why);
+    }
+
+    // -X FILE: the file read and validated on the host, before any context exists. false: `why` names the file and what was found.
+    bool load_background(std::string& why)
+    {
+        struct pcs_background_info info{};
+        if (!pcs_background_cli::load(params.background.file, background_bytes, info, why)) return false;
+        params.background.frames = info.frames;
+        params.background.params = pcs_background_params{pcs_background_cli::min_seen_of(info.frames, params.background.min_percent),
+                                                         params.background.dilate, PCS_BACKGROUND_MODE_REMOVE, 0};
+        return true;
     }
 
     // An option of the table's: its argument into the parameters, the stage switched on. false: `why` says what is wrong with it.
@@ -170,6 +224,11 @@ struct Chain {
             if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_count[s], 64);
             if (rc == PCS_OK && kStages[s].block_bytes) rc = pcs_device_malloc(ctx, &d_block[s], kStages[s].block_bytes);
         }
+        if (rc == PCS_OK && enabled[kBackgroundStage]) {      // a table with room for the file's cells, no more
+            const size_t cells = background_bytes.size() > 32 ? (background_bytes.size() - 32) / 12 : 1;
+            rc = pcs_background_import(ctx, background_bytes.data(), background_bytes.size(), (int)cells, &params.background.model);
+        }
+        if (rc == PCS_OK && learning()) rc = pcs_background_create(ctx, learn.cell_mm, learn.max_cells, &learn.model);
         if (rc == PCS_OK && objects()) {
             rc = pcs_device_malloc(ctx, &d_objects, (size_t)params.objects.max_objects * sizeof(pcs_cluster_object));
             if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_n_objects, 64);
@@ -183,6 +242,9 @@ struct Chain {
     Cloud run(pcs_ctx* c, Cloud in)
     {
         entered = in; status = PCS_OK;
+        if (learning())
+            status = in.d_n ? pcs_background_learn_device_counted(c, learn.model, in.d, in.d_n, in.capacity)
+                            : pcs_background_learn_device(c, learn.model, in.d, in.n);
         int k = 0;
         for (int s = 0; s < kStageCount && status == PCS_OK; s++) {
             if (!enabled[s]) continue;
@@ -213,7 +275,7 @@ struct Chain {
         int n_in = n[0];
         for (int s = 0; s < kStageCount; s++) {
             if (!enabled[s]) continue;
-            kStages[s].print(os, block[s].data(), n_in, n[s + 1]);
+            kStages[s].print(os, params, block[s].data(), n_in, n[s + 1]);
             if (s == kClusterStage && objects())
                 os << "Objects: " << n_objects << " (" << (n_objects < params.objects.max_objects ? n_objects : params.objects.max_objects)
                    << " written)" << std::endl;
@@ -236,8 +298,34 @@ struct Chain {
         return true;
     }
 
+    // -X learn: when the run ends: the model into its file, and with `say` the line. 0, or the status the program ends with (1) after a
+    // message on `err`: an overflowed model, a failed call, a file that cannot be written.
+    int finish_learning(std::ostream& os, std::ostream& err, bool say)
+    {
+        if (!learning() || !learn.model) return 0;
+        struct pcs_background_info info{};
+        if (pcs_background_info(ctx, learn.model, &info) != PCS_OK) { err << "-X learn: " << pcs_last_error(ctx) << std::endl; return 1; }
+        if (info.overflow) {
+            err << "-X learn: the scene has more than max_cells " << learn.max_cells << " cells of " << learn.cell_mm
+                << " mm: no model written (give a larger max_cells or a larger cell_mm)" << std::endl;
+            return 1;
+        }
+        std::vector<char> bytes(pcs_background_export_bound((int)info.cells));
+        size_t n = 0;
+        if (pcs_background_export(ctx, learn.model, bytes.data(), bytes.size(), &n) != PCS_OK) { err << "-X learn: " << pcs_last_error(ctx) << std::endl; return 1; }
+        FILE* f = fopen(learn.file.c_str(), "wb");
+        const bool ok = f && fwrite(bytes.data(), 1, n, f) == n;
+        if (f && fclose(f) != 0) { err << "-X learn: cannot write " << learn.file << std::endl; return 1; }
+        if (!ok) { err << "-X learn: cannot write " << learn.file << std::endl; return 1; }
+        if (say) os << "Background learned: " << info.frames << " frame-sets, " << info.cells << " cells of " << info.cell_mm << " mm" << std::endl;
+        return 0;
+    }
+
     void release()
     {
+        if (params.background.model) pcs_background_destroy(ctx, params.background.model);
+        if (learn.model) pcs_background_destroy(ctx, learn.model);
+        params.background.model = learn.model = nullptr;
         auto drop = [this](void*& p) { if (p) pcs_device_free(ctx, p); p = nullptr; };
         for (void*& p : d_buf) drop(p);
         for (void*& p : d_count) drop(p);

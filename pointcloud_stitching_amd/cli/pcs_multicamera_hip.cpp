@@ -40,6 +40,18 @@
 //                      on the host and decoded on the GPU into the camera's device payload (pcs_decompress_payload) ahead of the
 //                      stitch / -T / -B / -V paths, which see what they always saw; a frame that fails validation ends the run with
 //                      the validator's message. What is served on -p stays raw.
+//              -X learn:<file>,<cell_mm>[,<max_cells>]  learn the background of a fixed rig (pcs_background_learn_device, counted where the
+//                      cloud's count is on the device — the chain's own rule): every frame-set of the run, as it enters the chain (after
+//                      -T and -B / -d), marks the cells of edge cell_mm it touches in a model of at most max_cells cells (default
+//                      4194304); the frame-sets pass on unchanged. When the run ends <file> gets the model as a PCB1 container
+//                       and -t prints `Background learned: <frames> frame-sets, <cells> cells of <cell_mm> mm`. A
+//                      scene with more cells than max_cells ends the run with status 1 and no file.
+//              -X <file>[,<min_percent>[,<dilate>]]  background subtraction (pcs_background_subtract_device): the chain's first stage, in
+//                      front of -O. <file> is validated (pcs_background_validate: a refusal is a usage error that names what it found)
+//                      and imported at start-up; a record goes iff its cell — with dilate 1 (default) one of the 27 around it — was seen
+//                      in min_seen = max(1, ceil(frames x min_percent / 100)) of the learned frame-sets (min_percent 1..100, default 50).
+//                      -t prints `Background subtraction: <in> -> <kept> points (<cells> cells, seen >= <min_seen> of <frames>, dilate
+//                      <d>)`. One run takes one form of -X, once. Not with -G: the node library has no background model.
 //              -O -K -M -E  the post-stitch filters, one chain (pcs_filter_chain.h) in that fixed order, after -T and -B / -d, before -V. A
 //                      stage reads the output of the stage in front of it: through the counted form, with that stage's count word,
 //                      wherever the count is on the device (every -i payload, every stage behind another), else through the plain
@@ -109,7 +121,7 @@ static const char* dump_path = nullptr;
 static const char* transform_path = nullptr;
 static bool crop = false;
 static int16_t crop_lo[3], crop_hi[3];
-static pcs_filter_chain::Chain chain;      // -O -K -M -E
+static pcs_filter_chain::Chain chain;      // -X -O -K -M -E
 using pcs_filter_chain::Cloud;
 
 static void usage()
@@ -144,7 +156,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:X:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -184,6 +196,11 @@ int main(int argc, char** argv)
                 if (!chain.parse(c, optarg, why)) { std::cerr << "-" << (char)c << " " << optarg << ": " << why << std::endl; return 2; }
                 break;
             }
+            case 'X': {
+                std::string why;
+                if (!chain.parse_background(optarg, why)) { std::cerr << "-X " << optarg << ": " << why << std::endl; return 2; }
+                break;
+            }
             case 'L': {
                 std::string why;
                 if (!chain.parse_objects(optarg, why)) { std::cerr << "-L " << optarg << ": " << why << std::endl; return 2; }
@@ -203,6 +220,11 @@ int main(int argc, char** argv)
             const auto& stage = pcs_filter_chain::kStages[k];
             std::cerr << "-" << stage.letter << " is not available with -G: the node library has no " << stage.refusal << std::endl; return 2;
         }
+    if (chain.learning() && n_gpus > 0) { std::cerr << "-X is not available with -G: the node library has no background model" << std::endl; return 2; }
+    if (chain.enabled[pcs_filter_chain::kBackgroundStage]) {      // the model's file, before any device is touched
+        std::string why;
+        if (!chain.load_background(why)) { std::cerr << "-X " << why << std::endl; return 2; }
+    }
     if (chain.objects() && !chain.enabled[pcs_filter_chain::kClusterStage]) {
         std::cerr << "-L writes the objects of the cluster filter: it needs -E <tolerance_mm,min_size[,max_size]>" << std::endl; return 2;
     }
@@ -350,7 +372,7 @@ int main(int argc, char** argv)
             pcs_device_malloc(ctx, &d_pay_counts, sizeof(int32_t) * (n_streams + 1)) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return 1; }
     }
 
-    // -O -K -M -E: the chain's buffers hold the largest cloud that can enter it
+    // -X -O -K -M -E: the chain's buffers hold the largest cloud that can enter it (and -X's model is created or imported)
     if (chain.any() && chain.allocate(ctx, source ? pcs_max_payload_shorts(ctx) : (size_t)n_streams * cam_cap_bytes / 2) != PCS_OK) {
         std::cerr << pcs_last_error(ctx) << std::endl; return 1;
     }
@@ -691,6 +713,7 @@ int main(int argc, char** argv)
         FILE* f = fopen(dump_path, "wb");
         if (f) { fwrite(stitched.data(), 1, (size_t)size_bytes + 4, f); fclose(f); }
     }
+    const int learn_status = chain.finish_learning(std::cout, std::cerr, timer);      // -X learn: the model into its file
     if (chain.objects()) {      // -L: the last frame-set's object table
         bool ok;
         if (chain.objects_file == "-") {
@@ -718,5 +741,5 @@ int main(int argc, char** argv)
     if (node) pcs_node_destroy(node);
     stitched.release();
     pcs_destroy(ctx);
-    return 0;
+    return learn_status;
 }

@@ -708,6 +708,7 @@ void pcs_destroy(pcs_ctx* c)
     if (!c) return;
     DeviceGuard guard(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    free_backgrounds(c);
     for (float* p : c->d_lut) if (p) (void)hipFree(p);
     if (c->s_slab) (void)hipFree(c->s_slab);
     if (c->dl_stream) (void)hipStreamSynchronize(c->dl_stream);

@@ -481,6 +481,39 @@ hipError_t  launch_plane_step(const PlaneJob& job, int step, int round, hipStrea
 hipError_t  launch_plane_count(const int16_t* d_in, uint32_t n_points, void* d_ws, size_t ws_bytes, uint32_t n_models,
                                unsigned long long* d_counts, hipStream_t st);
 
+// Background model and subtraction (pcs_background_*, pcs_kernels_background.hip; the definition: DESIGN.md section 3 "Background model
+// and subtraction"). The table is one allocation of background_table_bytes(max_cells) bytes, 256-byte aligned, carved by
+// background_table: the control block, keys[slots] (all ones: empty; probe from first_slot), seen[slots], stamp[slots];
+// slots = background_slots(max_cells) = 2048 ceil(2 max_cells / 2048). Each launch is its own call, so that the host layer can bracket
+// them one by one. learn: `frame` 1..65535 is the call's number; the record count is n_points, or *d_n_points clamped to 0..capacity
+// when that pointer is given, read on the device; capacity > 0 sizes the grid. flag: the same count rule; d_ws is the radius filter's
+// workspace (outlier_workspace_bytes(capacity)), whose control block receives the count and whose keep bits the launch writes, for
+// launch_outlier_compact_stage 7, 8, 9 behind it. stats: after stage 8, d_out_points is its kept count. gather: occupied slots as
+// (key low, key high, seen, 0) into d_staging[room] (16-byte aligned) through ctl->cursor, which the caller zeroes first and which ends
+// at the number of occupied slots. import: n_entries > 0 entries of 12 bytes (a validated PCB1 container's, 4-byte aligned).
+struct BackgroundCtl { uint32_t cells, overflow, cursor, reserved; };
+struct BackgroundTable {
+    unsigned long long* keys;
+    uint32_t*           seen;
+    uint32_t*           stamp;
+    BackgroundCtl*      ctl;
+    uint32_t            slots, max_cells;
+    int32_t             cell_mm;
+};
+uint32_t        background_slots(uint32_t max_cells);
+size_t          background_table_bytes(uint32_t max_cells);
+BackgroundTable background_table(void* d_table, int cell_mm, uint32_t max_cells);
+const char*     background_launch_name(int launch);      // of a subtract call: flag, tile count, tile scan, emit, stats
+hipError_t launch_background_clear(const BackgroundTable& t, hipStream_t st);
+hipError_t launch_background_learn(const BackgroundTable& t, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points,
+                                   uint32_t capacity, uint32_t frame, hipStream_t st);
+hipError_t launch_background_import(const BackgroundTable& t, const void* d_entries, uint32_t n_entries, hipStream_t st);
+hipError_t launch_background_flag(const BackgroundTable& t, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points,
+                                  uint32_t capacity, int min_seen, int dilate, int mode, void* d_ws, size_t ws_bytes, hipStream_t st);
+hipError_t launch_background_stats(const BackgroundTable& t, uint32_t capacity, void* d_ws, size_t ws_bytes, const int32_t* d_out_points,
+                                   uint32_t frames, int min_seen, int mode, long long* d_stats, hipStream_t st);
+hipError_t launch_background_gather(const BackgroundTable& t, void* d_staging, uint32_t room, hipStream_t st);
+
 // Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
 // index is the outlier filter's, cell edge max_dist_mm (launch_cell_index_stage over the target; `index` is its view, or nullptr for
 // an empty target: nobody matches). launch_align_match: one lane per source record, one 144-byte partial per

@@ -1,7 +1,7 @@
 // pcs_host.h — what the translation units of the C ABI share: the context itself and the helpers more than one of them calls.
 // pcs_capi.cpp: contexts, the a1 / a2 twins, the fused path, host forms, plumbing; pcs_capi_voxel.cpp: the voxel grid, partials, sinks;
 // pcs_capi_codec.cpp: the payload codec; and the payload-cloud family over the cell index — pcs_capi_outlier.cpp, pcs_capi_stat.cpp,
-// pcs_capi_normals.cpp, pcs_capi_align.cpp, pcs_capi_cluster.cpp, and pcs_capi_plane.cpp, which uses the family's compaction alone — whose common checks, slab policy, index build and staging live in pcs_capi_cloud.cpp.
+// pcs_capi_normals.cpp, pcs_capi_align.cpp, pcs_capi_cluster.cpp, and pcs_capi_plane.cpp and pcs_capi_background.cpp, which use the family's compaction alone — whose common checks, slab policy, index build and staging live in pcs_capi_cloud.cpp.
 // Internal to libpcs_hip.so; nothing here is exported.
 #ifndef PCS_HOST_H
 #define PCS_HOST_H
@@ -24,6 +24,8 @@ struct Certificate {
     double a_max[3] = {0, 0, 0};        // |P_i| upper bounds
     double p2_low = 0;                  // P2 lower bound (> 0) over valid depths
 };
+
+struct pcs_background;      // pcs_capi_background.cpp
 
 struct pcs_ctx {
     int                             device = 0;
@@ -151,6 +153,9 @@ struct pcs_ctx {
     // 8 bytes per record — one slab carved per call, grown on demand by ensure_ws
     void*                           s_normals_ws = nullptr; size_t s_normals_ws_cap = 0;
 
+    // background models created on this context and not destroyed yet (pcs_capi_background.cpp): pcs_destroy frees what is left
+    std::vector<pcs_background*>    backgrounds;
+
     std::string                     err;
 };
 
@@ -239,6 +244,9 @@ int ensure_ws(pcs_ctx* c, T*& p, size_t& cap, size_t need)
     if (rc == PCS_ERR_NOMEM && need != exact) rc = ensure(c, p, cap, exact);      // the headroom is a wish
     return rc;
 }
+
+// pcs_destroy's part of pcs_capi_background.cpp: the tables and objects of c->backgrounds.
+void free_backgrounds(pcs_ctx* c);
 
 // The voxel workspace of a context, at least `need` bytes: ensure_ws, and the control block's state forgotten when it moves.
 int ensure_voxel_ws(pcs_ctx* c, size_t need);

@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig
+from .types import BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, PayloadDesc, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -102,6 +102,20 @@ SYMBOLS = [
     ("pcs_plane_labels", C.c_int, [_VP, _VP, C.c_int, _P(PlaneParams), _VP, _P(C.c_int), _P(PlaneModel), _P(PlaneStats)]),
     ("pcs_plane_count_inliers_device", C.c_int, [_VP, _VP, C.c_int, _P(PlaneModel), C.c_int, _VP]),
     ("pcs_plane_from_points", C.c_int, [_VP, _VP, _VP, C.c_int, _P(PlaneModel)]),
+    ("pcs_background_create", C.c_int, [_VP, C.c_int, C.c_int, _P(_VP)]),
+    ("pcs_background_destroy", C.c_int, [_VP, _VP]),
+    ("pcs_background_reset", C.c_int, [_VP, _VP]),
+    ("pcs_background_learn_device", C.c_int, [_VP, _VP, _VP, C.c_int]),
+    ("pcs_background_learn_device_counted", C.c_int, [_VP, _VP, _VP, _VP, C.c_int]),
+    ("pcs_background_learn", C.c_int, [_VP, _VP, _VP, C.c_int]),
+    ("pcs_background_subtract_device", C.c_int, [_VP, _VP, _VP, C.c_int, _P(BackgroundParams), _VP, C.c_size_t, _VP, _VP]),
+    ("pcs_background_subtract_device_counted", C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _P(BackgroundParams), _VP, C.c_size_t, _VP, _VP]),
+    ("pcs_background_subtract", C.c_int, [_VP, _VP, _VP, C.c_int, _P(BackgroundParams), _VP, C.c_size_t, _P(C.c_int), _P(BackgroundStats)]),
+    ("pcs_background_info", C.c_int, [_VP, _VP, _P(BackgroundInfo)]),
+    ("pcs_background_export_bound", C.c_size_t, [C.c_int]),
+    ("pcs_background_export", C.c_int, [_VP, _VP, _VP, C.c_size_t, _P(C.c_size_t)]),
+    ("pcs_background_import", C.c_int, [_VP, _VP, C.c_size_t, C.c_int, _P(_VP)]),
+    ("pcs_background_validate", C.c_int, [_VP, C.c_size_t, _P(BackgroundInfo)]),
     ("pcs_align_sums_device", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]),
     ("pcs_align_sums", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _P(AlignSumsC), _VP]),
     ("pcs_align_solve", C.c_int, [_P(AlignSumsC), _P(C.c_double), _P(C.c_double)]),

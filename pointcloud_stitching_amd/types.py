@@ -55,6 +55,10 @@ PLANE_ITERATIONS_MAX, PLANE_MAX_PLANES = 4096, 8
 PLANE_MODE_REMOVE, PLANE_MODE_KEEP = 0, 1
 PLANE_STATS_FIELDS = ("considered", "planes", "inliers_total", "kept", "largest_plane", "degenerate_hypotheses")    # two reserved words behind them
 PLANE_MODEL_FIELDS = ("nx", "ny", "nz", "off", "threshold", "inliers")
+BACKGROUND_MODE_REMOVE, BACKGROUND_MODE_KEEP = 0, 1
+BACKGROUND_FRAMES_MAX = 65535
+BACKGROUND_STATS_FIELDS = ("considered", "kept", "background", "cells", "frames", "min_seen", "overflow")    # one reserved word behind them
+BACKGROUND_SUBTRACT_LAUNCHES = ("flag", "tile count", "tile scan", "emit", "stats")     # in kernel_times_ms order; "stats" only with a block
 
 
 def plane_stages(max_planes: int, labels: bool = False) -> tuple:
@@ -256,6 +260,32 @@ class PlaneStats(C.Structure):
 
     def as_dict(self) -> dict:
         return {name: int(getattr(self, name)) for name in PLANE_STATS_FIELDS}
+
+
+class BackgroundParams(C.Structure):
+    """pcs_background_params: four 32-bit words."""
+    _fields_ = [("min_seen", C.c_int32), ("dilate", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, min_seen: int, dilate: int = 1, mode: int = 0, reserved: int = 0) -> "BackgroundParams":
+        return cls(int(min_seen), int(dilate), int(mode), int(reserved))
+
+
+class BackgroundInfo(C.Structure):
+    """struct pcs_background_info: six 32-bit words."""
+    _fields_ = [("cell_mm", C.c_int32), ("max_cells", C.c_int32), ("cells", C.c_uint32), ("frames", C.c_uint32), ("overflow", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in ("cell_mm", "max_cells", "cells", "frames", "overflow")}
+
+
+class BackgroundStats(C.Structure):
+    """struct pcs_background_stats: eight int64."""
+    _fields_ = [(name, C.c_int64) for name in BACKGROUND_STATS_FIELDS] + [("reserved", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in BACKGROUND_STATS_FIELDS}
 
 
 class AlignSumsC(C.Structure):
