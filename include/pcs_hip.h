@@ -1068,6 +1068,91 @@ int pcs_background_export(pcs_ctx* ctx, pcs_background* bg, void* out, size_t ca
 int pcs_background_import(pcs_ctx* ctx, const void* bytes, size_t n_bytes, int max_cells, pcs_background** out);
 int pcs_background_validate(const void* bytes, size_t n_bytes, struct pcs_background_info* info);
 
+/* ---- object tracks: persistent identities across frame-sets (not in the reference) ------------------------------------------------ *
+ * An object's number k in pcs_cluster_objects_device* is "rank by first record": it changes whenever the record order does. A tracker
+ * is a PERSISTENT device object that gives every object an identity that survives from one frame-set to the next. The evidence is
+ * per record: which of the last frame-set's objects occupied the cell this record is in now. Everything is integer; no float anywhere.
+ * The inputs of one UPDATE are what pcs_cluster_objects_device* leaves on the device: the payload it clustered (n records of 5 shorts;
+ * shorts 0..2 are read, colour is not), object_of (n int32), *n_objects and the max_objects that call was given. m = *n_objects
+ * clamped to 0..max_objects. A record TAKES PART iff 0 <= object_of(i) < m; every other value is ignored.
+ *   CELL        floor(v / cell_mm) + 32768 per axis, cell_mm 1..1000: the background model's cell.
+ *   STATE       after update t: m_t; per object j < m_t an id (int64, >= 1) and an age (int32); the map P_t: cell -> the SMALLEST j
+ *                 among the taking-part records in that cell; next_id; frames. Fresh or reset: m = 0, an empty map, frames = 0,
+ *                 next_id = first_id (pcs_tracker_create: 1; pcs_tracker_reset: 1..2^62).
+ *   VOTES       votes(k, j) = the number of taking-part records i with object_of(i) = k and P_{t-1}(cell(i)) = j.
+ *   CHOICE      choice(k) = the j with the most votes(k, j) > 0, on a tie the smallest j; with no vote there is none.
+ *   KEEPER      keeper(j) = among the k with choice(k) = j the one with the most votes(k, j), on a tie the smallest k.
+ *   CONTINUED   k continues j iff choice(k) = j, keeper(j) = k and votes(k, j) >= min_votes (1..2^30): id(k) = id_{t-1}(j),
+ *                 age(k) = min(age_{t-1}(j) + 1, INT32_MAX), prev = j, votes = votes(k, j). A merge keeps the majority's identity;
+ *                 a split leaves the identity with the larger part.
+ *   BORN        every other k < m: id(k) = next_id + r, r its rank among the born by ascending k; age 0, prev -1, votes 0. Then
+ *                 next_id += born.
+ *   LOST        the number of j < m_{t-1} that no k continues.
+ *   OVERFLOW    (a) an update needs more than max_cells distinct (k, j) pairs: this update continues nothing, all m are born
+ *                 (statistics overflow bit 0). (b) an update's taking-part records occupy more than max_cells distinct cells: the
+ *                 NEXT update continues nothing (bit 1, reported by the update that suffers it). Which surplus cells or pairs got in
+ *                 is unspecified and cannot influence any output: the affected update reads neither. No hang, no write outside the
+ *                 tables.
+ * Output: tracks[k] for k < m (24 bytes each, reserved 0; nothing at or beyond entry m is written) and an optional block of eight
+ * int64: considered (taking-part records), voted (those whose cell was in P_{t-1}; 0 where that map had overflowed), objects (m),
+ * continued, born, lost, overflow, frames (after this update). Exact and deterministic: the same bytes on every run, whatever order
+ * the atomics arrive in; under a permutation of the records that keeps object_of consistent the outputs are unchanged. An update with
+ * m = 0 or with no record is still an update: frames + 1, the map emptied, every previous object lost. tests/np_tracks.py restates it.
+ * pcs_tracker_create: a tracker on the context's device: cell_mm 1..1000, max_cells 1..2^26, max_objects 1..PCS_CLUSTER_OBJECTS_MAX.
+ *   It owns its memory (not a context slab): three tables of 2048 ceil(2 max_cells / 2048) slots of 12 bytes (two cell maps used
+ *   alternately as P_{t-1} and P_t, and the pair table), 40 bytes per object of max_objects, 32 KB of striped counters and a
+ *   256-byte control block. It belongs to the context that
+ *   created it: pcs_tracker_destroy it first, or leave it to that context's pcs_destroy, which frees what is left.
+ *   pcs_tracker_reset: the fresh tracker again with next_id = first_id, one launch.
+ * pcs_tracker_update_device: asynchronous on the context's stream, no host round trip. d_object_of and d_n_objects are 4-byte
+ *   aligned, d_tracks (max_objects entries; NULL iff max_objects == 0) and d_stats (optional) 8-byte aligned; max_objects 0 .. the
+ *   tracker's. pcs_tracker_update_device_counted: the count is read from *d_n_points (device, 4-byte aligned) when the kernels run,
+ *   clamped to 0..max_points; records at or beyond the count are never read. pcs_tracker_update: host pointers, staged, synchronous;
+ *   n_objects by value.
+ * pcs_tracker_info: synchronous (waits for the context's stream). overflow: the last update's overflow word, and bit 2 where the
+ *   map that update built overflowed (the next update will continue nothing).
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the function and the argument), nothing launched, nothing written: a NULL
+ *   tracker, a tracker on another device than the context's, NULL params, min_votes out of range, a reserved word != 0, a negative
+ *   count, a NULL pointer (payload and object_of may be NULL with a count of 0), an odd payload address, max_objects outside
+ *   0 .. the tracker's, a misaligned object_of, n_objects, count, tracks or stats address, an output (tracks, stats) that shares a
+ *   byte with an input or with the other output (inputs are only read: they may overlap each other), a tracker one of whose updates
+ *   failed between its launches (PCS_ERR_HIP then; its tables are half built: pcs_tracker_reset it).
+ * Launches, every update, all three forms, whatever the counts: 4 (record pass, choose, claim, assign); create 1, reset 1. Nothing is
+ *   cleared by a launch of its own: the record pass zeroes what the folds behind it need, choose empties the pair table and the map
+ *   it has read, assign the control block and the counters. With pcs_kernel_timing enabled a call yields one interval per launch.
+ *   Measured: DESIGN.md section 10 (f17), profiles/track_probe.txt.                                                                  */
+#define PCS_TRACKER_MAX_CELLS_MAX   (1 << 26)
+#define PCS_TRACKER_MIN_VOTES_MAX   (1 << 30)
+#define PCS_TRACKER_FIRST_ID_MAX    ((int64_t)1 << 62)
+typedef struct pcs_tracker pcs_tracker;                     /* opaque; lives on the context's device */
+typedef struct pcs_track {                                  /* 24 bytes, 8-byte aligned */
+    int64_t id;
+    int32_t age, prev, votes, reserved;                     /* reserved is 0 */
+} pcs_track;
+typedef struct pcs_track_params {
+    int32_t min_votes, reserved[3];                         /* reserved words are 0 */
+} pcs_track_params;
+struct pcs_track_stats {
+    int64_t considered, voted, objects, continued, born, lost, overflow, frames;
+};
+struct pcs_tracker_info {        /* (a tag only: pcs_tracker_info is also the call's name) */
+    int32_t cell_mm, max_cells, max_objects, objects;
+    int64_t frames, next_id;
+    int32_t overflow, reserved;
+};
+int pcs_tracker_create(pcs_ctx* ctx, int cell_mm, int max_cells, int max_objects, pcs_tracker** out);
+int pcs_tracker_destroy(pcs_ctx* ctx, pcs_tracker* tr);
+int pcs_tracker_reset(pcs_ctx* ctx, pcs_tracker* tr, int64_t first_id);
+int pcs_tracker_update_device(pcs_ctx* ctx, pcs_tracker* tr, const int16_t* d_payload, int n_points, const int32_t* d_object_of,
+                              const int32_t* d_n_objects, int max_objects, const pcs_track_params* params, pcs_track* d_tracks,
+                              struct pcs_track_stats* d_stats);
+int pcs_tracker_update_device_counted(pcs_ctx* ctx, pcs_tracker* tr, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                      const int32_t* d_object_of, const int32_t* d_n_objects, int max_objects,
+                                      const pcs_track_params* params, pcs_track* d_tracks, struct pcs_track_stats* d_stats);
+int pcs_tracker_update(pcs_ctx* ctx, pcs_tracker* tr, const int16_t* payload, int n_points, const int32_t* object_of, int n_objects,
+                       int max_objects, const pcs_track_params* params, pcs_track* tracks, struct pcs_track_stats* stats);   /* host pointers, staged, synchronous */
+int pcs_tracker_info(pcs_ctx* ctx, pcs_tracker* tr, struct pcs_tracker_info* info);
+
 /* ---- extrinsics refinement: nearest-neighbour alignment sums, the rigid fit, the ICP loop (not in the reference) ---------------- *
  * transform[i] comes from four surveyed markers (calibration.py); these calls refine it from the data: move one camera's payload
  * onto another's where they overlap. DESIGN.md section 3 "Alignment sums" has the definition and what follows from it.

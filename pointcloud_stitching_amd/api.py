@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, Track, TRACK_DTYPE, TrackParams, TrackStats, TrackerInfo, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -157,6 +157,73 @@ class Background:
         n = C.c_size_t(0)
         self._call(self._ctx._lib.pcs_background_export, _ptr(buf), buf.nbytes, C.byref(n))
         return buf[:n.value].tobytes()
+
+
+class Tracker:
+    """An object tracker on a context's device (pcs_tracker_*): persistent identities for the objects of cluster_objects across
+    frame-sets. Created by PcsContext.tracker_create; destroy() it (or leave a `with` block) before the context closes, which frees
+    what is left."""
+
+    def __init__(self, ctx: "PcsContext", handle: int):
+        self._ctx = ctx
+        self._h = handle
+
+    @property
+    def handle(self) -> int:
+        return self._h or 0
+
+    def destroy(self) -> None:
+        if self._h and self._ctx._h:
+            self._ctx._check(self._ctx._lib.pcs_tracker_destroy(self._ctx._h, self._h))
+        self._h = None
+
+    close = destroy
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.destroy()
+
+    def _call(self, fn, *args) -> None:
+        self._ctx._check(fn(self._ctx._h, self._h, *args))
+
+    def reset(self, first_id: int = 1) -> None:
+        self._call(self._ctx._lib.pcs_tracker_reset, int(first_id))
+
+    def info(self) -> dict:
+        """cell_mm, max_cells, max_objects, objects, frames, next_id, overflow — synchronous."""
+        info = TrackerInfo()
+        self._call(self._ctx._lib.pcs_tracker_info, C.byref(info))
+        return info.as_dict()
+
+    def update(self, payload: np.ndarray, object_of: np.ndarray, n_objects: int, max_objects: int, min_votes: int = 1):
+        """Packed records (int16 [n,5]), their object_of (int32 [n]) and the object count -> (tracks as a TRACK_DTYPE array of
+        min(n_objects, max_objects) entries, the statistics block as a dict) (pcs_tracker_update: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        o = np.ascontiguousarray(object_of, np.int32).reshape(-1)
+        if o.shape[0] != p.shape[0]:
+            raise ValueError("object_of must hold one int32 per record")
+        tracks = np.zeros(max(int(max_objects), 1), TRACK_DTYPE)
+        stats = TrackStats()
+        params = TrackParams.make(min_votes)
+        self._call(self._ctx._lib.pcs_tracker_update, _ptr(p) if p.shape[0] else None, p.shape[0], _ptr(o) if o.shape[0] else None,
+                   int(n_objects), int(max_objects), C.byref(params), C.cast(_ptr(tracks), C.POINTER(Track)), C.byref(stats))
+        return tracks[:min(max(int(n_objects), 0), int(max_objects))].copy(), stats.as_dict()
+
+    def update_device(self, d_payload: int, n_points: int, d_object_of: int, d_n_objects: int, max_objects: int, params: TrackParams,
+                      d_tracks: int, d_stats: int = 0) -> None:
+        """Asynchronous; device pointers as ints: what cluster_objects_device left (payload, object_of, *n_objects, its max_objects) ->
+        d_tracks (max_objects entries of 24 bytes), d_stats (eight int64, optional). params may be None (refused)."""
+        self._call(self._ctx._lib.pcs_tracker_update_device, d_payload or None, int(n_points), d_object_of or None, d_n_objects or None,
+                   int(max_objects), C.byref(params) if params is not None else None, d_tracks or None, d_stats or None)
+
+    def update_device_counted(self, d_payload: int, d_n_points: int, max_points: int, d_object_of: int, d_n_objects: int, max_objects: int,
+                              params: TrackParams, d_tracks: int, d_stats: int = 0) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run."""
+        self._call(self._ctx._lib.pcs_tracker_update_device_counted, d_payload or None, d_n_points or None, int(max_points),
+                   d_object_of or None, d_n_objects or None, int(max_objects), C.byref(params) if params is not None else None,
+                   d_tracks or None, d_stats or None)
 
 
 def plane_from_points(p0, p1, p2, distance_mm: int) -> dict:
@@ -832,6 +899,12 @@ class PcsContext:
         h = C.c_void_p()
         self._check(self._lib.pcs_background_create(self._h, int(cell_mm), int(max_cells), C.byref(h)))
         return Background(self, h.value)
+
+    def tracker_create(self, cell_mm: int, max_cells: int, max_objects: int) -> Tracker:
+        """A fresh object tracker on this context's device (pcs_tracker_create)."""
+        h = C.c_void_p()
+        self._check(self._lib.pcs_tracker_create(self._h, int(cell_mm), int(max_cells), int(max_objects), C.byref(h)))
+        return Tracker(self, h.value)
 
     def background_import(self, container, max_cells: int) -> Background:
         """A model from a "PCB1" container (bytes or a uint8 array), validated first (pcs_background_import)."""

@@ -13,9 +13,15 @@
 // -L (pcs_objects.h) adds nothing to the order: with it the E stage calls the objects form of the cluster filter — plain or counted by
 // the same rule, the stage's usual output buffer, count word and statistics block in its `out` struct — so the cloud that leaves the
 // stage is what -E alone gives, and the object table and its count land in two device blocks of the chain's own.
+//
+// -J (pcs_tracks.h) rides on the same call: the table (at -L's default size if -L is not given) and object_of, and behind the stage's
+// call one pcs_tracker_update_device* over the cloud the stage read, on the same count rule. Nothing comes to the host for it;
+// write_tracks() copies the tracks and the table after the frame-set's launches and appends the frame-set's lines.
 #pragma once
 
 #include <cstring>
+#include <fstream>
+#include <iostream>
 #include <ostream>
 #include <string>
 #include <vector>
@@ -26,6 +32,7 @@
 #include "pcs_outlier.h"
 #include "pcs_plane.h"
 #include "pcs_statoutlier.h"
+#include "pcs_tracks.h"
 
 namespace pcs_filter_chain {
 
@@ -51,6 +58,16 @@ struct Params {
     pcs_cluster_params cluster{};
     // -L: max_objects 0 = not given; the table and its count word on the device (Chain::allocate)
     struct { int max_objects = 0; pcs_cluster_object* d_table = nullptr; int32_t* d_n = nullptr; } objects;
+    // -J: cell_mm 0 = not given; the tracker, and views of the chain's three blocks for it (Chain::allocate): object_of of the E stage's
+    // input, the tracks and the statistics block
+    struct {
+        int cell_mm = 0;
+        pcs_track_params params{};
+        pcs_tracker* tracker = nullptr;
+        int32_t* d_object_of = nullptr;
+        pcs_track* d_tracks = nullptr;
+        pcs_track_stats* d_stats = nullptr;
+    } tracks;
 };
 
 // -M's block: the statistics, then the models
@@ -133,8 +150,16 @@ inline const Stage kStages[] = {
              pcs_cluster_objects_out o{};
              o.objects = p.objects.d_table; o.max_objects = p.objects.max_objects; o.n_objects = p.objects.d_n;
              o.out = d_out; o.out_shorts = out_shorts; o.out_points = d_n_out; o.stats = d_stats;
-             return in.d_n ? pcs_cluster_objects_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, &o)
-                           : pcs_cluster_objects_device(ctx, in.d, in.n, &p.cluster, &o);
+             const auto& t = p.tracks;
+             o.object_of = t.d_object_of;
+             const int rc = in.d_n ? pcs_cluster_objects_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, &o)
+                                   : pcs_cluster_objects_device(ctx, in.d, in.n, &p.cluster, &o);
+             if (rc != PCS_OK || !t.tracker) return rc;
+             // -J: the objects of the cloud this stage read, tracked where they stand
+             return in.d_n ? pcs_tracker_update_device_counted(ctx, t.tracker, in.d, in.d_n, in.capacity, t.d_object_of, o.n_objects,
+                                                               o.max_objects, &t.params, t.d_tracks, t.d_stats)
+                           : pcs_tracker_update_device(ctx, t.tracker, in.d, in.n, t.d_object_of, o.n_objects, o.max_objects, &t.params,
+                                                       t.d_tracks, t.d_stats);
          }
          return in.d_n ? pcs_cluster_filter_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, d_out, out_shorts, d_n_out, d_stats)
                        : pcs_cluster_filter_device(ctx, in.d, in.n, &p.cluster, d_out, out_shorts, d_n_out, d_stats);
@@ -164,6 +189,13 @@ struct Chain {
     std::string objects_file;              // -L: where the table goes ("-": stdout); empty: no -L
     void* d_objects = nullptr;             // ... the table (params.objects.max_objects entries) and its count word
     void* d_n_objects = nullptr;
+    void* d_object_of = nullptr;           // -J: one int32 per record that can enter the chain, max_objects tracks, the statistics block
+    void* d_tracks = nullptr;
+    void* d_track_stats = nullptr;
+    // -J: where the lines go ("-": stdout), the stream, the frame-sets written and the run's totals for -t
+    std::string tracks_file;
+    std::ofstream tracks_stream;
+    long long tracks_frames = 0, tracks_born = 0, tracks_continued = 0, tracks_lost = 0;
     // -X learn: the option's words and the model allocate() creates; -X FILE: the file's bytes (load_background), imported by allocate()
     struct { std::string file; int cell_mm = 0, max_cells = 0; pcs_background* model = nullptr; } learn;
     std::vector<char> background_bytes;
@@ -211,7 +243,22 @@ struct Chain {
     {
         return pcs_objects::parse(arg, objects_file, params.objects.max_objects, why);
     }
-    bool objects() const { return params.objects.max_objects != 0; }
+    bool objects() const { return !objects_file.empty(); }
+
+    // -J's argument: the file, the cell and the vote threshold. false: `why` says what is wrong with it. Without -L the object table is
+    // still made, at -L's default size (finish_options, once every option has been read).
+    bool parse_tracks(const char* arg, std::string& why)
+    {
+        int min_votes = 0;
+        if (!pcs_tracks::parse(arg, tracks_file, params.tracks.cell_mm, min_votes, why)) return false;
+        params.tracks.params = pcs_track_params{min_votes, {0, 0, 0}};
+        return true;
+    }
+    bool tracks() const { return params.tracks.cell_mm != 0; }
+    void finish_options()
+    {
+        if (tracks() && !params.objects.max_objects) params.objects.max_objects = pcs_objects::kDefaultMaxObjects;
+    }
 
     // Buffers for clouds of up to out_shorts shorts: one per enabled stage, two at the most.
     int allocate(pcs_ctx* c, size_t shorts)
@@ -229,11 +276,22 @@ struct Chain {
             rc = pcs_background_import(ctx, background_bytes.data(), background_bytes.size(), (int)cells, &params.background.model);
         }
         if (rc == PCS_OK && learning()) rc = pcs_background_create(ctx, learn.cell_mm, learn.max_cells, &learn.model);
-        if (rc == PCS_OK && objects()) {
+        if (rc == PCS_OK && params.objects.max_objects) {
             rc = pcs_device_malloc(ctx, &d_objects, (size_t)params.objects.max_objects * sizeof(pcs_cluster_object));
             if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_n_objects, 64);
             params.objects.d_table = static_cast<pcs_cluster_object*>(d_objects);
             params.objects.d_n = static_cast<int32_t*>(d_n_objects);
+        }
+        if (rc == PCS_OK && tracks()) {      // max_cells: the records that can enter the chain
+            auto& t = params.tracks;
+            const size_t records = out_shorts / PCS_POINT_SHORTS;
+            const int max_cells = (int)(records < 1 ? 1 : records > (size_t)PCS_TRACKER_MAX_CELLS_MAX ? (size_t)PCS_TRACKER_MAX_CELLS_MAX : records);
+            rc = pcs_tracker_create(ctx, t.cell_mm, max_cells, params.objects.max_objects, &t.tracker);
+            if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_object_of, (records + 1) * sizeof(int32_t));
+            if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_tracks, (size_t)params.objects.max_objects * sizeof(pcs_track));
+            if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_track_stats, sizeof(pcs_track_stats));
+            t.d_object_of = static_cast<int32_t*>(d_object_of); t.d_tracks = static_cast<pcs_track*>(d_tracks);
+            t.d_stats = static_cast<pcs_track_stats*>(d_track_stats);
         }
         return rc;
     }
@@ -298,6 +356,39 @@ struct Chain {
         return true;
     }
 
+    // -J: the file opened and its header written, before the first frame-set. false: it cannot be written.
+    bool open_tracks()
+    {
+        if (tracks_file != "-") tracks_stream.open(tracks_file);
+        std::ostream& os = tracks_file == "-" ? std::cout : tracks_stream;
+        pcs_tracks::write_header(os);
+        os.flush();
+        return os.good();
+    }
+
+    // -J's lines of the last run(), appended; the run's totals kept for -t. false: a copy failed (pcs_last_error has it) or the file
+    // cannot be written (`why` says so).
+    bool write_tracks(std::string& why)
+    {
+        int32_t n_objects = 0;
+        pcs_track_stats st{};
+        if (pcs_memcpy_d2h(ctx, &n_objects, d_n_objects, sizeof n_objects) != PCS_OK ||
+            pcs_memcpy_d2h(ctx, &st, params.tracks.d_stats, sizeof st) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
+        const int written = n_objects < 0 ? 0 : n_objects < params.objects.max_objects ? n_objects : params.objects.max_objects;
+        std::vector<pcs_cluster_object> table((size_t)written);
+        std::vector<pcs_track> ids((size_t)written);
+        if (written && (pcs_memcpy_d2h(ctx, table.data(), d_objects, table.size() * sizeof table[0]) != PCS_OK ||
+                        pcs_memcpy_d2h(ctx, ids.data(), params.tracks.d_tracks, ids.size() * sizeof ids[0]) != PCS_OK ||
+                        pcs_synchronize(ctx) != PCS_OK))
+            return false;
+        std::ostream& os = tracks_file == "-" ? std::cout : tracks_stream;
+        pcs_tracks::write(os, tracks_frames++, ids.data(), table.data(), written);
+        os.flush();
+        tracks_born += st.born; tracks_continued += st.continued; tracks_lost += st.lost;
+        if (!os.good()) { why = "cannot write " + tracks_file; return false; }
+        return true;
+    }
+
     // -X learn: when the run ends: the model into its file, and with `say` the line. 0, or the status the program ends with (1) after a
     // message on `err`: an overflowed model, a failed call, a file that cannot be written.
     int finish_learning(std::ostream& os, std::ostream& err, bool say)
@@ -326,12 +417,18 @@ struct Chain {
         if (params.background.model) pcs_background_destroy(ctx, params.background.model);
         if (learn.model) pcs_background_destroy(ctx, learn.model);
         params.background.model = learn.model = nullptr;
+        if (params.tracks.tracker) pcs_tracker_destroy(ctx, params.tracks.tracker);
+        params.tracks.tracker = nullptr;
         auto drop = [this](void*& p) { if (p) pcs_device_free(ctx, p); p = nullptr; };
         for (void*& p : d_buf) drop(p);
         for (void*& p : d_count) drop(p);
         for (void*& p : d_block) drop(p);
         drop(d_objects);
         drop(d_n_objects);
+        drop(d_object_of);
+        drop(d_tracks);
+        drop(d_track_stats);
+        params.tracks.d_object_of = nullptr; params.tracks.d_tracks = nullptr; params.tracks.d_stats = nullptr;
     }
 };
 

@@ -86,6 +86,12 @@
 //                      frame-set <file> (`-`: stdout) gets one header line `# k label size lo_x lo_y lo_z hi_x hi_y hi_z sum_x sum_y
 //                      sum_z sum_r sum_g sum_b` and one line of raw integers per written object of that frame-set, at most max_objects
 //                      (1..65536, default 1024). Refused without -E and with -G (the node library has no object table).
+//              -J <file>[,<cell_mm>[,<min_votes>]]  (with -E) the same object in every frame-set: behind the E stage's objects call
+//                      (the table at -L's default size if -L is not given, and object_of) one pcs_tracker_update_device, plain or
+//                      counted by the chain's rule, over the cloud that stage read; max_cells is the chain's record capacity. After
+//                      EVERY frame-set <file> (`-`: stdout) gets one line of raw integers per object, by ascending k, under the header
+//                      `# frame k id age prev votes label size lo_x lo_y lo_z hi_x hi_y hi_z sum_x sum_y sum_z`. -t prints `Tracks:
+//                      <born> born, <continued> continued, <lost> lost` over the run. Refused without -E and with -G.
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
@@ -145,7 +151,7 @@ static void usage()
               << "                  as the reference's pcs-multicamera-optimized does (decode, pcl::transformPointCloud, re-encode)\n"
               << " -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box, millimetres in the world frame, inclusive: -i crops in the fused path, -c crops the\n"
               << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
-              << filters << pcs_objects::help()
+              << filters << pcs_objects::help() << pcs_tracks::help()
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
@@ -156,7 +162,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:X:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:X:J:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -206,6 +212,11 @@ int main(int argc, char** argv)
                 if (!chain.parse_objects(optarg, why)) { std::cerr << "-L " << optarg << ": " << why << std::endl; return 2; }
                 break;
             }
+            case 'J': {
+                std::string why;
+                if (!chain.parse_tracks(optarg, why)) { std::cerr << "-J " << optarg << ": " << why << std::endl; return 2; }
+                break;
+            }
             case 's': case 'v': case 'n':
                 std::cerr << "-" << (char)c << " drives the reference's PCL viewer / PLY writer, which this build does not include" << std::endl;
                 return 2;
@@ -214,6 +225,8 @@ int main(int argc, char** argv)
     }
     if (downsample < 1) { std::cerr << "downsample must be >= 1" << std::endl; return 2; }
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
+    chain.finish_options();
+    if (chain.tracks() && n_gpus > 0) { std::cerr << "-J is not available with -G: the node library has no object tracker" << std::endl; return 2; }
     if (chain.objects() && n_gpus > 0) { std::cerr << "-L is not available with -G: the node library has no object table" << std::endl; return 2; }
     for (int k = 0; k < pcs_filter_chain::kStageCount; k++)
         if (chain.enabled[k] && n_gpus > 0) {
@@ -227,6 +240,9 @@ int main(int argc, char** argv)
     }
     if (chain.objects() && !chain.enabled[pcs_filter_chain::kClusterStage]) {
         std::cerr << "-L writes the objects of the cluster filter: it needs -E <tolerance_mm,min_size[,max_size]>" << std::endl; return 2;
+    }
+    if (chain.tracks() && !chain.enabled[pcs_filter_chain::kClusterStage]) {
+        std::cerr << "-J tracks the objects of the cluster filter: it needs -E <tolerance_mm,min_size[,max_size]>" << std::endl; return 2;
     }
     if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
@@ -376,6 +392,7 @@ int main(int argc, char** argv)
     if (chain.any() && chain.allocate(ctx, source ? pcs_max_payload_shorts(ctx) : (size_t)n_streams * cam_cap_bytes / 2) != PCS_OK) {
         std::cerr << pcs_last_error(ctx) << std::endl; return 1;
     }
+    if (chain.tracks() && !chain.open_tracks()) { std::cerr << "-J: cannot write " << chain.tracks_file << std::endl; return 1; }
 
     // -V: device-resident rasters (with -i) and the voxel cloud
     std::vector<void*> d_depth, d_color;
@@ -445,6 +462,10 @@ int main(int argc, char** argv)
             memcpy(stitched.data(), &size_bytes, sizeof(int));                                             // :394-395
         }
         if (timer && !chain.report(std::cout)) { std::cerr << pcs_last_error(ctx) << std::endl; return false; }
+        if (chain.tracks()) {      // -J: this frame-set's lines
+            std::string why;
+            if (!chain.write_tracks(why)) { std::cerr << "-J: " << (why.empty() ? pcs_last_error(ctx) : why.c_str()) << std::endl; return false; }
+        }
         return true;
     };
 
@@ -725,6 +746,8 @@ int main(int argc, char** argv)
         }
         if (!ok) std::cerr << "-L: " << pcs_last_error(ctx) << std::endl;
     }
+    if (chain.tracks() && timer)
+        std::cout << "Tracks: " << chain.tracks_born << " born, " << chain.tracks_continued << " continued, " << chain.tracks_lost << " lost" << std::endl;
     for (int fd : cam_fd) ::close(fd);
     if (client_fd >= 0) ::close(client_fd);
     if (listen_fd >= 0) ::close(listen_fd);

@@ -709,6 +709,7 @@ void pcs_destroy(pcs_ctx* c)
     DeviceGuard guard(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_backgrounds(c);
+    free_trackers(c);
     for (float* p : c->d_lut) if (p) (void)hipFree(p);
     if (c->s_slab) (void)hipFree(c->s_slab);
     if (c->dl_stream) (void)hipStreamSynchronize(c->dl_stream);

@@ -514,6 +514,50 @@ hipError_t launch_background_stats(const BackgroundTable& t, uint32_t capacity, 
                                    uint32_t frames, int min_seen, int mode, long long* d_stats, hipStream_t st);
 hipError_t launch_background_gather(const BackgroundTable& t, void* d_staging, uint32_t room, hipStream_t st);
 
+// Object tracks (pcs_tracker_*, pcs_kernels_tracks.hip; the definition: DESIGN.md section 3 "Object tracks"). The tracker is one
+// allocation of tracker_bytes(max_cells, max_objects) bytes, 256-byte aligned, carved by tracker_view: the control block, two cell
+// maps (keys[slots], all ones: empty; val[slots], all ones: no object), the pair table (keys k << 32 | j, counts), id and age twice,
+// best[max_objects], keeper[max_objects] and the striped counters; slots = background_slots(max_cells). `parity` says which map and which id / age arrays
+// hold update t - 1: the host flips it after every update. An update is the four launches below in this order, each its own call so
+// that the host layer can bracket them; every one is launched for every update, whatever the counts. The record count is n_points,
+// or *d_n_points clamped to 0..capacity when that pointer is given, read on the device; m = *d_n_objects clamped to 0..max_objects.
+struct TrackCtl {
+    long long next_id;
+    uint32_t  m;                         // of the last update (0: fresh)
+    uint32_t  pair_overflow;             // the pair table ran full in the update in flight; zero between updates
+    uint32_t  cur_overflow;              // the map the update in flight builds ran full
+    uint32_t  prev_overflow;             // the map of the last update overflowed: the next continues nothing
+    uint32_t  last_overflow;             // the overflow word of the last update's statistics
+    uint32_t  reserved;
+};
+// The update's four counts (taking-part records, voted records, claimed cells, claimed pairs) are sums over kTrackStripes words 128
+// bytes apart each, so that no two waves' adds queue on one address; assign folds and zeroes them.
+constexpr uint32_t kTrackStripes = 64, kTrackStripeWords = 32, kTrackCounters = 4;
+constexpr uint32_t kTrackCounterWords = kTrackCounters * kTrackStripes * kTrackStripeWords;
+struct TrackerView {
+    unsigned long long* prev_keys;  uint32_t* prev_val;      // P(t-1): read by the record pass, emptied by choose
+    unsigned long long* cur_keys;   uint32_t* cur_val;       // P(t): empty when the update starts
+    unsigned long long* pair_keys;  uint32_t* pair_count;    // empty between updates
+    const long long*    prev_id;    const int32_t* prev_age;
+    long long*          cur_id;     int32_t*       cur_age;
+    unsigned long long* best;                                // [max_objects], zero between updates
+    unsigned long long* keeper;
+    TrackCtl*           ctl;
+    uint32_t*           counters;                            // [kTrackCounterWords], zero between updates
+    uint32_t            slots, max_cells, max_objects;
+    int32_t             cell_mm;
+};
+constexpr int kTrackLaunches = 4;            // record pass, choose, claim, assign
+size_t      tracker_bytes(uint32_t max_cells, uint32_t max_objects);
+TrackerView tracker_view(void* d_tracker, int cell_mm, uint32_t max_cells, uint32_t max_objects, int parity);
+hipError_t launch_track_clear(const TrackerView& t, long long first_id, hipStream_t st);
+hipError_t launch_track_records(const TrackerView& t, const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
+                                const int32_t* d_object_of, const int32_t* d_n_objects, uint32_t max_objects, hipStream_t st);
+hipError_t launch_track_choose(const TrackerView& t, hipStream_t st);
+hipError_t launch_track_claim(const TrackerView& t, const int32_t* d_n_objects, uint32_t max_objects, hipStream_t st);
+hipError_t launch_track_assign(const TrackerView& t, const int32_t* d_n_objects, uint32_t max_objects, uint32_t min_votes, long long frames,
+                               void* d_tracks, long long* d_stats, hipStream_t st);
+
 // Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
 // index is the outlier filter's, cell edge max_dist_mm (launch_cell_index_stage over the target; `index` is its view, or nullptr for
 // an empty target: nobody matches). launch_align_match: one lane per source record, one 144-byte partial per

@@ -26,6 +26,7 @@ struct Certificate {
 };
 
 struct pcs_background;      // pcs_capi_background.cpp
+struct pcs_tracker;         // pcs_capi_tracks.cpp
 
 struct pcs_ctx {
     int                             device = 0;
@@ -155,6 +156,8 @@ struct pcs_ctx {
 
     // background models created on this context and not destroyed yet (pcs_capi_background.cpp): pcs_destroy frees what is left
     std::vector<pcs_background*>    backgrounds;
+    // trackers created on this context and not destroyed yet (pcs_capi_tracks.cpp): likewise
+    std::vector<pcs_tracker*>       trackers;
 
     std::string                     err;
 };
@@ -247,6 +250,8 @@ int ensure_ws(pcs_ctx* c, T*& p, size_t& cap, size_t need)
 
 // pcs_destroy's part of pcs_capi_background.cpp: the tables and objects of c->backgrounds.
 void free_backgrounds(pcs_ctx* c);
+// pcs_destroy's part of pcs_capi_tracks.cpp: the tables and objects of c->trackers.
+void free_trackers(pcs_ctx* c);
 
 // The voxel workspace of a context, at least `need` bytes: ensure_ws, and the control block's state forgotten when it moves.
 int ensure_voxel_ws(pcs_ctx* c, size_t need);

@@ -59,6 +59,10 @@ BACKGROUND_MODE_REMOVE, BACKGROUND_MODE_KEEP = 0, 1
 BACKGROUND_FRAMES_MAX = 65535
 BACKGROUND_STATS_FIELDS = ("considered", "kept", "background", "cells", "frames", "min_seen", "overflow")    # one reserved word behind them
 BACKGROUND_SUBTRACT_LAUNCHES = ("flag", "tile count", "tile scan", "emit", "stats")     # in kernel_times_ms order; "stats" only with a block
+TRACK_STATS_FIELDS = ("considered", "voted", "objects", "continued", "born", "lost", "overflow", "frames")
+TRACK_UPDATE_LAUNCHES = ("records", "choose", "claim", "assign")     # in kernel_times_ms order: every update, every form
+TRACK_MIN_VOTES_MAX = 1 << 30
+TRACK_FIRST_ID_MAX = 1 << 62
 
 
 def plane_stages(max_planes: int, labels: bool = False) -> tuple:
@@ -286,6 +290,41 @@ class BackgroundStats(C.Structure):
 
     def as_dict(self) -> dict:
         return {name: int(getattr(self, name)) for name in BACKGROUND_STATS_FIELDS}
+
+
+class TrackParams(C.Structure):
+    """pcs_track_params: four 32-bit words."""
+    _fields_ = [("min_votes", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    @classmethod
+    def make(cls, min_votes: int = 1, reserved=(0, 0, 0)) -> "TrackParams":
+        return cls(int(min_votes), (C.c_int32 * 3)(*(int(v) for v in reserved)))
+
+
+class Track(C.Structure):
+    """pcs_track: 24 bytes."""
+    _fields_ = [("id", C.c_int64), ("age", C.c_int32), ("prev", C.c_int32), ("votes", C.c_int32), ("reserved", C.c_int32)]
+
+
+TRACK_DTYPE = np.dtype([("id", "<i8"), ("age", "<i4"), ("prev", "<i4"), ("votes", "<i4"), ("reserved", "<i4")])
+assert TRACK_DTYPE.itemsize == C.sizeof(Track) == 24
+
+
+class TrackStats(C.Structure):
+    """struct pcs_track_stats: eight int64."""
+    _fields_ = [(name, C.c_int64) for name in TRACK_STATS_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in TRACK_STATS_FIELDS}
+
+
+class TrackerInfo(C.Structure):
+    """struct pcs_tracker_info: 40 bytes."""
+    _fields_ = [("cell_mm", C.c_int32), ("max_cells", C.c_int32), ("max_objects", C.c_int32), ("objects", C.c_int32),
+                ("frames", C.c_int64), ("next_id", C.c_int64), ("overflow", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in ("cell_mm", "max_cells", "max_objects", "objects", "frames", "next_id", "overflow")}
 
 
 class AlignSumsC(C.Structure):

@@ -2,7 +2,8 @@
 // entry point every stage gets, with which pointers, counts and sizes, what comes out and what -t prints, over all 32 subsets of
 // -X -O -K -M -E and a host-count or device-count start (-X FILE over a fake of the model calls: the imported model and the option's
 // parameters reach the subtract call; -X learn: the cloud that enters is learned by the plain or the counted call and passes unchanged), and every subset with -E again with -L (the objects form of the cluster call: the same
-// cloud out, the table and its count in blocks of the chain's own, the `Objects:` line and the file's lines). A stand-alone program: no GPU, no library, nothing loaded into Python.
+// cloud out, the table and its count in blocks of the chain's own, the `Objects:` line and the file's lines), and -J over three subsets with and without -L
+// (the table either way, object_of out of the cluster call, one tracker update over the cloud that call read, the file's lines). A stand-alone program: no GPU, no library, nothing loaded into Python.
 //
 //   make -C pointcloud_stitching_amd/cli ../../tools/bin/filter_chain_check && tools/bin/filter_chain_check
 //   (.../filter_chain_check_asan: the same under the host sanitizers)
@@ -246,6 +247,44 @@ int pcs_cluster_objects_device_counted(pcs_ctx*, const int16_t* in, const int32_
 {
     return fake_objects({4, true, in, d_n, 0, max_points, p->tolerance_mm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr}, o);
 }
+// the object tracker (-J): a heap block that remembers what made it; an update is recorded, and writes what the file's lines are made of
+struct pcs_tracker { int cell_mm, max_cells, max_objects, updates; };
+static std::map<pcs_tracker*, int> g_trackers;
+struct TrackCall {
+    pcs_tracker* tr; bool counted; const int16_t* in; const int32_t* d_n; int n_points, max_points;
+    const int32_t *object_of, *d_n_objects; int max_objects, min_votes; pcs_track* tracks; pcs_track_stats* stats;
+};
+static std::vector<TrackCall> g_track_calls;
+static pcs_track fake_track(int k, int update) { return pcs_track{(1ll << 33) + k, update, k - 1, 7 * k, 0}; }
+static int fake_update(TrackCall c)
+{
+    g_track_calls.push_back(c);
+    for (int k = 0; k < kFakeObjects && k < c.max_objects; k++) c.tracks[k] = fake_track(k, c.tr->updates);
+    *c.stats = pcs_track_stats{40, 30, kFakeObjects, 3, 2, 1, 0, ++c.tr->updates};
+    return PCS_OK;
+}
+int pcs_tracker_create(pcs_ctx*, int cell_mm, int max_cells, int max_objects, pcs_tracker** out)
+{
+    *out = new pcs_tracker{cell_mm, max_cells, max_objects, 0};
+    g_trackers[*out] = 1;
+    return PCS_OK;
+}
+int pcs_tracker_destroy(pcs_ctx*, pcs_tracker* tr)
+{
+    if (!g_trackers.erase(tr)) { g_bad_frees++; return PCS_ERR_INVALID_ARG; }
+    delete tr;
+    return PCS_OK;
+}
+int pcs_tracker_update_device(pcs_ctx*, pcs_tracker* tr, const int16_t* in, int n, const int32_t* object_of, const int32_t* d_m, int max_objects,
+                              const pcs_track_params* p, pcs_track* tracks, pcs_track_stats* st)
+{
+    return fake_update({tr, false, in, nullptr, n, 0, object_of, d_m, max_objects, p->min_votes, tracks, st});
+}
+int pcs_tracker_update_device_counted(pcs_ctx*, pcs_tracker* tr, const int16_t* in, const int32_t* d_n, int max_points, const int32_t* object_of,
+                                      const int32_t* d_m, int max_objects, const pcs_track_params* p, pcs_track* tracks, pcs_track_stats* st)
+{
+    return fake_update({tr, true, in, d_n, 0, max_points, object_of, d_m, max_objects, p->min_votes, tracks, st});
+}
 }
 
 // ---- the check ---------------------------------------------------------------------------------------------------------------------
@@ -448,6 +487,81 @@ static void check_learn(int subset, Start start, int max_cells)
     g_learns.clear();
 }
 
+// -J over the stages of `subset` (E among them, X not), with -L (max_objects) or without (0): the table is made either way, the E stage
+// hands object_of out, and behind it one tracker update reads the cloud THAT stage read, counted iff that stage's call was; the
+// file gets the header once and every frame-set's lines; release() leaves nothing.
+static void check_tracks(int subset, Start start, int max_objects)
+{
+    snprintf(g_case, sizeof g_case, "tracks over subset %d, %s, -L %d", subset, kStartName[start], max_objects);
+    pcs_ctx ctx{0};
+    const int capacity = 41, n_in = start == kDeviceFewer ? 29 : capacity;
+    std::vector<int16_t> cloud((size_t)capacity * PCS_POINT_SHORTS);
+    for (int i = 0; i < capacity; i++)
+        for (int k = 0; k < PCS_POINT_SHORTS; k++) cloud[i * PCS_POINT_SHORTS + k] = (int16_t)(k ? 100 * i + k : i % 6);
+    int32_t count = n_in;
+    const Cloud in{cloud.data(), start == kHost ? nullptr : &count, start == kHost ? n_in : -12345, capacity};
+    Chain chain;
+    std::string why;
+    const char* const args[kStageCount] = {"", "11,2", "22,1000,30", "33,16,3,2,5", "44,3"};
+    int n_enabled = 0;
+    for (int s = 1; s < kStageCount; s++)
+        if (subset >> s & 1) { EXPECT(chain.parse(kStages[s].letter, args[s], why)); n_enabled++; }
+    const std::string file = "filter_chain_check_tracks.tmp";
+    EXPECT(!chain.tracks() && !chain.parse_tracks("t.txt,0", why) && why.find("cell_mm") != std::string::npos && !chain.tracks());
+    EXPECT(!chain.parse_tracks("t.txt,100,x", why) && !chain.parse_tracks(",100", why) && !chain.parse_tracks("t.txt,1,2,3", why));
+    EXPECT(chain.parse_tracks((file + ",250,7").c_str(), why) && chain.tracks() && chain.tracks_file == file);
+    EXPECT(chain.params.tracks.cell_mm == 250 && chain.params.tracks.params.min_votes == 7);
+    if (max_objects) EXPECT(chain.parse_objects(("objects.txt," + std::to_string(max_objects)).c_str(), why));
+    chain.finish_options();
+    const int table = max_objects ? max_objects : pcs_objects::kDefaultMaxObjects;      // without -L: the table at -L's default size
+    EXPECT(chain.params.objects.max_objects == table && chain.objects() == (max_objects != 0));
+    g_live.clear(); g_track_calls.clear();
+    EXPECT(chain.allocate(&ctx, (size_t)capacity * PCS_POINT_SHORTS) == PCS_OK);
+    pcs_tracker* const tr = chain.params.tracks.tracker;
+    EXPECT(g_trackers.size() == 1 && g_trackers.count(tr) && tr->cell_mm == 250 && tr->max_cells == capacity && tr->max_objects == table);
+    EXPECT(g_live.count(chain.d_object_of) && g_live[chain.d_object_of] >= (size_t)capacity * sizeof(int32_t));
+    EXPECT(g_live.count(chain.d_tracks) && g_live[chain.d_tracks] == (size_t)table * sizeof(pcs_track));
+    EXPECT(g_live.count(chain.d_track_stats) && g_live[chain.d_track_stats] == sizeof(pcs_track_stats));
+    EXPECT(g_live.count(chain.d_objects) && g_live[chain.d_objects] == (size_t)table * sizeof(pcs_cluster_object));
+    remove(file.c_str());
+    EXPECT(chain.open_tracks());
+    std::ostringstream want;
+    pcs_tracks::write_header(want);
+    for (int frame = 0; frame < 3; frame++) {
+        g_calls.clear();
+        const Cloud out = chain.run(&ctx, in);
+        EXPECT(chain.status == PCS_OK && (int)g_calls.size() == n_enabled && (int)g_track_calls.size() == frame + 1 && out.d_n);
+        const Call& e = g_calls.back();
+        const TrackCall& t = g_track_calls.back();
+        EXPECT(e.stage == 4 && e.objects == chain.d_objects && e.max_objects == table);
+        EXPECT(t.tr == tr && t.in == e.in && t.d_n == e.d_n && t.counted == e.counted);          // the cloud the E stage read, by the same rule
+        EXPECT(t.counted == (n_enabled > 1 || start != kHost));
+        if (t.counted) EXPECT(t.max_points == capacity); else EXPECT(t.n_points == n_in);
+        EXPECT(t.object_of == chain.d_object_of && t.d_n_objects == chain.d_n_objects && t.max_objects == table && t.min_votes == 7);
+        EXPECT(t.tracks == chain.d_tracks && t.stats == chain.d_track_stats);
+        EXPECT(chain.write_tracks(why) && g_track_calls.size() == (size_t)frame + 1);               // (writing launches nothing)
+        std::vector<pcs_cluster_object> objects;
+        std::vector<pcs_track> tracks;
+        for (int k = 0; k < kFakeObjects && k < table; k++) { objects.push_back(fake_object(k, *out.d_n)); tracks.push_back(fake_track(k, frame)); }
+        pcs_tracks::write(want, frame, tracks.data(), objects.data(), (int)tracks.size());
+        std::ostringstream lines;
+        EXPECT(chain.report(lines) && (lines.str().find("Objects:") != std::string::npos) == (max_objects != 0));
+    }
+    EXPECT(chain.tracks_frames == 3 && chain.tracks_born == 6 && chain.tracks_continued == 9 && chain.tracks_lost == 3);
+    std::ifstream f(file);
+    std::stringstream got;
+    got << f.rdbuf();
+    EXPECT(got.str() == want.str());
+    EXPECT(got.str().rfind("# frame k id age prev votes label size lo_x lo_y lo_z hi_x hi_y hi_z sum_x sum_y sum_z\n", 0) == 0);
+    if (table >= 2) EXPECT(got.str().find("\n2 1 8589934593 2 0 7 10 ") != std::string::npos);
+    chain.release();
+    EXPECT(g_live.empty() && g_trackers.empty() && g_bad_frees == 0);
+    chain.release();      // (nothing left to free)
+    EXPECT(g_bad_frees == 0);
+    chain.tracks_stream.close();
+    remove(file.c_str());
+}
+
 int main()
 {
     for (int subset = 0; subset < 32; subset++)
@@ -459,6 +573,9 @@ int main()
     for (int subset : {0, 2, 12, 30})
         for (Start start : {kHost, kDeviceFewer, kDeviceFull})
             for (int max_cells : {1000, 7}) check_learn(subset, start, max_cells);
+    for (int subset : {16, 18, 30})
+        for (Start start : {kHost, kDeviceFewer, kDeviceFull})
+            for (int max_objects : {0, 3, 1024}) check_tracks(subset, start, max_objects);
     printf(g_failed ? "filter_chain_check: %d check(s) FAILED\n" : "filter_chain_check: all checks passed, no report\n", g_failed);
     fflush(stdout);      // (a leak report at exit must not swallow the lines above)
     return g_failed ? 1 : 0;
