@@ -1153,6 +1153,54 @@ int pcs_tracker_update(pcs_ctx* ctx, pcs_tracker* tr, const int16_t* payload, in
                        int max_objects, const pcs_track_params* params, pcs_track* tracks, struct pcs_track_stats* stats);   /* host pointers, staged, synchronous */
 int pcs_tracker_info(pcs_ctx* ctx, pcs_tracker* tr, struct pcs_tracker_info* info);
 
+/* ---- object boxes: second moments, axes and extents per object (not in the reference) --------------------------------------------- *
+ * The object table says where an object is; a box says which way it lies. The inputs are what pcs_cluster_objects_device* leaves on
+ * the device and what pcs_tracker_update_device* takes: the payload (n records of 5 shorts; shorts 0..2 are read, colour is not),
+ * object_of (n int32), *n_objects and max_objects (0..PCS_CLUSTER_OBJECTS_MAX). m = *n_objects clamped to 0..max_objects. A record
+ * TAKES PART iff 0 <= object_of(i) < m; every other value is ignored.
+ * Output: boxes[k] for k < m, 128 bytes each, written whole; nothing at or beyond entry m is written.
+ *   SUMS        count, sum_xyz, m2 (xx, xy, xz, yy, yz, zz) over the members, exact in int64 (every sum stays below 2^58).
+ *   AXES        C = count M2 - S1 S1^T exactly in 128-bit integers, converted to double once; a cyclic Jacobi in a fixed order with
+ *                 the normals' stop rule and twelve-sweep bound; eigenvalues descending, a tie to the lower column; the component of
+ *                 largest magnitude of axis 0 and of axis 1 is positive (ties prefer z, then y, then x); axis 2 = axis 0 x axis 1;
+ *                 axis[a][c] = rint(16384 v_a[c]). rank = the number of eigenvalues > 1e-12 lambda_max, 0 when lambda_max <= 0 (one
+ *                 record, or all members equal: the axes are then the identity). No entry is "invalid": a line or a plane gets an
+ *                 orthonormal triple like any other object and rank says how many of its axes mean something.
+ *   EXTENTS     ext_lo[a] / ext_hi[a] = the minimum / maximum over the members of axis[a] . p in int32 (exact), units of mm / 16384:
+ *                 a function of the WRITTEN shorts, projections from the origin. The box centre along axis a is
+ *                 (ext_lo[a] + ext_hi[a]) / 2 / 16384.
+ *   NO MEMBER   an entry k < m that no record names: count 0, zero sums, identity axes, rank 0, ext_lo = ext_hi = 0.
+ * Deterministic: the same bytes on every run, whatever order the atomics arrive in; under a permutation of the records that keeps
+ * object_of consistent every entry is byte-identical. tests/np_object_boxes.py restates it.
+ * pcs_object_boxes_device: asynchronous on the context's stream, no host round trip. d_object_of and d_n_objects are 4-byte aligned,
+ *   d_boxes (max_objects entries; NULL iff max_objects == 0) 8-byte aligned. pcs_object_boxes_device_counted: the count is read from
+ *   *d_n_points (device, 4-byte aligned) when the kernels run, clamped to 0..max_points; records at or beyond the count are never
+ *   read. pcs_object_boxes: host pointers, staged, synchronous; n_objects by value. A count of 0 is a normal call in every form: it
+ *   writes the m empty entries.
+ * Workspace: 128 bytes per object of max_objects in a slab of the context, grown on demand.
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the function and the argument), nothing launched, nothing written: a count
+ *   outside 0 .. INT_MAX / 10, a NULL pointer (payload and object_of may be NULL with a count of 0, boxes with max_objects 0), an odd
+ *   payload address, a misaligned object_of, n_objects, count or boxes address, max_objects outside 0..PCS_CLUSTER_OBJECTS_MAX, boxes
+ *   sharing a byte with an input.
+ * Launches, every call, all three forms, whatever the counts: PCS_OBJECT_BOXES_LAUNCHES (clear, moments, axes, extents). With
+ *   pcs_kernel_timing enabled a call yields one interval per launch. Measured: DESIGN.md section 10 (f18).                           */
+#define PCS_OBJECT_BOXES_LAUNCHES 4
+typedef struct pcs_object_box {                             /* 128 bytes, 8-byte aligned */
+    int64_t count;
+    int64_t sum_xyz[3];
+    int64_t m2[6];                                          /* xx, xy, xz, yy, yz, zz */
+    int16_t axis[3][3];                                     /* axis[a] = rint(16384 unit vector a) */
+    int16_t rank;                                           /* 0..3 */
+    int32_t ext_lo[3], ext_hi[3];                           /* min / max of axis[a] . p, units of mm / 16384 */
+    int32_t reserved;                                       /* 0 */
+} pcs_object_box;
+int pcs_object_boxes_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const int32_t* d_object_of, const int32_t* d_n_objects,
+                            int max_objects, pcs_object_box* d_boxes);
+int pcs_object_boxes_device_counted(pcs_ctx* ctx, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                    const int32_t* d_object_of, const int32_t* d_n_objects, int max_objects, pcs_object_box* d_boxes);
+int pcs_object_boxes(pcs_ctx* ctx, const int16_t* payload, int n_points, const int32_t* object_of, int n_objects, int max_objects,
+                     pcs_object_box* boxes);               /* host pointers, staged, synchronous */
+
 /* ---- extrinsics refinement: nearest-neighbour alignment sums, the rigid fit, the ICP loop (not in the reference) ---------------- *
  * transform[i] comes from four surveyed markers (calibration.py); these calls refine it from the data: move one camera's payload
  * onto another's where they overlap. DESIGN.md section 3 "Alignment sums" has the definition and what follows from it.

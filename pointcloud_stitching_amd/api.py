@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, Track, TRACK_DTYPE, TrackParams, TrackStats, TrackerInfo, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, OBJECT_BOX_DTYPE, ObjectBox, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, Track, TRACK_DTYPE, TrackParams, TrackStats, TrackerInfo, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -892,6 +892,33 @@ class PcsContext:
         self._check(self._lib.pcs_cluster_objects_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
                                                                  C.byref(params) if params is not None else None,
                                                                  C.byref(out) if out is not None else None))
+
+    # -- object boxes (defined by this build; see include/pcs_hip.h) ---------------------------------
+    def object_boxes(self, payload: np.ndarray, object_of: np.ndarray, n_objects: int, max_objects: int = 1024) -> np.ndarray:
+        """Packed records (int16 [n,5]), their object_of (int32 [n]) and the object count -> the boxes: a structured array
+        (types.OBJECT_BOX_DTYPE) of min(n_objects, max_objects) entries with the count, the first and second moments, three axes,
+        the rank and the extents along the axes (pcs_object_boxes: host arrays, staged, synchronous)."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        o = np.ascontiguousarray(object_of, np.int32).reshape(-1)
+        if o.shape[0] != p.shape[0]:
+            raise ValueError(f"object_of has {o.shape[0]} entries for {p.shape[0]} records")
+        boxes = np.zeros(max(int(max_objects), 1), OBJECT_BOX_DTYPE)
+        self._check(self._lib.pcs_object_boxes(self._h, _ptr(p) if p.shape[0] else None, p.shape[0], _ptr(o) if o.shape[0] else None,
+                                               int(n_objects), int(max_objects), C.cast(_ptr(boxes), C.POINTER(ObjectBox))))
+        return boxes[:min(max(int(n_objects), 0), int(max_objects))].copy()
+
+    def object_boxes_device(self, d_payload: int, n_points: int, d_object_of: int, d_n_objects: int, max_objects: int, d_boxes: int) -> None:
+        """Asynchronous; device pointers as ints: the payload, object_of (int32 per record), *d_n_objects (int32), d_boxes
+        (max_objects entries of 128 bytes). See pcs_object_boxes_device."""
+        self._check(self._lib.pcs_object_boxes_device(self._h, d_payload or None, int(n_points), d_object_of or None, d_n_objects or None,
+                                                      int(max_objects), d_boxes or None))
+
+    def object_boxes_device_counted(self, d_payload: int, d_n_points: int, max_points: int, d_object_of: int, d_n_objects: int,
+                                    max_objects: int, d_boxes: int) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run. See
+        pcs_object_boxes_device_counted."""
+        self._check(self._lib.pcs_object_boxes_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
+                                                              d_object_of or None, d_n_objects or None, int(max_objects), d_boxes or None))
 
     # -- background model and subtraction (defined by this build; see include/pcs_hip.h) ------------
     def background_create(self, cell_mm: int, max_cells: int) -> Background:

@@ -17,6 +17,10 @@
 // -J (pcs_tracks.h) rides on the same call: the table (at -L's default size if -L is not given) and object_of, and behind the stage's
 // call one pcs_tracker_update_device* over the cloud the stage read, on the same count rule. Nothing comes to the host for it;
 // write_tracks() copies the tracks and the table after the frame-set's launches and appends the frame-set's lines.
+//
+// -W (pcs_boxes.h) stands beside it: the same table and object_of, and behind the stage's call (and the tracker's, where -J is given
+// too) one pcs_object_boxes_device* over the cloud the stage read, on the same count rule, into a device block of the chain's own.
+// write_boxes() copies the entries after the frame-set's launches and appends the frame-set's lines.
 #pragma once
 
 #include <cstring>
@@ -27,6 +31,7 @@
 #include <vector>
 
 #include "pcs_background.h"
+#include "pcs_boxes.h"
 #include "pcs_cluster.h"
 #include "pcs_objects.h"
 #include "pcs_outlier.h"
@@ -68,6 +73,9 @@ struct Params {
         pcs_track* d_tracks = nullptr;
         pcs_track_stats* d_stats = nullptr;
     } tracks;
+    // -W: on = given; views of the chain's blocks for it (Chain::allocate): object_of of the E stage's input (the tracker's where -J is
+    // given too) and the entries
+    struct { bool on = false; int32_t* d_object_of = nullptr; pcs_object_box* d_boxes = nullptr; } boxes;
 };
 
 // -M's block: the statistics, then the models
@@ -151,15 +159,21 @@ inline const Stage kStages[] = {
              o.objects = p.objects.d_table; o.max_objects = p.objects.max_objects; o.n_objects = p.objects.d_n;
              o.out = d_out; o.out_shorts = out_shorts; o.out_points = d_n_out; o.stats = d_stats;
              const auto& t = p.tracks;
-             o.object_of = t.d_object_of;
-             const int rc = in.d_n ? pcs_cluster_objects_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, &o)
-                                   : pcs_cluster_objects_device(ctx, in.d, in.n, &p.cluster, &o);
-             if (rc != PCS_OK || !t.tracker) return rc;
+             const auto& b = p.boxes;
+             o.object_of = t.d_object_of ? t.d_object_of : b.d_object_of;
+             int rc = in.d_n ? pcs_cluster_objects_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, &o)
+                             : pcs_cluster_objects_device(ctx, in.d, in.n, &p.cluster, &o);
              // -J: the objects of the cloud this stage read, tracked where they stand
-             return in.d_n ? pcs_tracker_update_device_counted(ctx, t.tracker, in.d, in.d_n, in.capacity, t.d_object_of, o.n_objects,
-                                                               o.max_objects, &t.params, t.d_tracks, t.d_stats)
-                           : pcs_tracker_update_device(ctx, t.tracker, in.d, in.n, t.d_object_of, o.n_objects, o.max_objects, &t.params,
-                                                       t.d_tracks, t.d_stats);
+             if (rc == PCS_OK && t.tracker)
+                 rc = in.d_n ? pcs_tracker_update_device_counted(ctx, t.tracker, in.d, in.d_n, in.capacity, t.d_object_of, o.n_objects,
+                                                                 o.max_objects, &t.params, t.d_tracks, t.d_stats)
+                             : pcs_tracker_update_device(ctx, t.tracker, in.d, in.n, t.d_object_of, o.n_objects, o.max_objects, &t.params,
+                                                         t.d_tracks, t.d_stats);
+             // -W: ... and boxed where they stand
+             if (rc == PCS_OK && b.on)
+                 rc = in.d_n ? pcs_object_boxes_device_counted(ctx, in.d, in.d_n, in.capacity, o.object_of, o.n_objects, o.max_objects, b.d_boxes)
+                             : pcs_object_boxes_device(ctx, in.d, in.n, o.object_of, o.n_objects, o.max_objects, b.d_boxes);
+             return rc;
          }
          return in.d_n ? pcs_cluster_filter_device_counted(ctx, in.d, in.d_n, in.capacity, &p.cluster, d_out, out_shorts, d_n_out, d_stats)
                        : pcs_cluster_filter_device(ctx, in.d, in.n, &p.cluster, d_out, out_shorts, d_n_out, d_stats);
@@ -189,13 +203,18 @@ struct Chain {
     std::string objects_file;              // -L: where the table goes ("-": stdout); empty: no -L
     void* d_objects = nullptr;             // ... the table (params.objects.max_objects entries) and its count word
     void* d_n_objects = nullptr;
-    void* d_object_of = nullptr;           // -J: one int32 per record that can enter the chain, max_objects tracks, the statistics block
+    void* d_object_of = nullptr;           // -J, -W: one int32 per record that can enter the chain; -J: max_objects tracks, the statistics block
     void* d_tracks = nullptr;
     void* d_track_stats = nullptr;
     // -J: where the lines go ("-": stdout), the stream, the frame-sets written and the run's totals for -t
     std::string tracks_file;
     std::ofstream tracks_stream;
     long long tracks_frames = 0, tracks_born = 0, tracks_continued = 0, tracks_lost = 0;
+    // -W: the entries (max_objects of them), where the lines go ("-": stdout), the stream, the frame-sets written and the run's totals for -t
+    void* d_boxes = nullptr;
+    std::string boxes_file;
+    std::ofstream boxes_stream;
+    long long boxes_frames = 0, boxes_objects = 0, boxes_rank3 = 0;
     // -X learn: the option's words and the model allocate() creates; -X FILE: the file's bytes (load_background), imported by allocate()
     struct { std::string file; int cell_mm = 0, max_cells = 0; pcs_background* model = nullptr; } learn;
     std::vector<char> background_bytes;
@@ -255,9 +274,15 @@ struct Chain {
         return true;
     }
     bool tracks() const { return params.tracks.cell_mm != 0; }
+    // -W's argument: the file. false: `why` says what is wrong with it. Without -L the object table is made as for -J.
+    bool parse_boxes(const char* arg, std::string& why)
+    {
+        return params.boxes.on = pcs_boxes::parse(arg, boxes_file, why);
+    }
+    bool boxes() const { return params.boxes.on; }
     void finish_options()
     {
-        if (tracks() && !params.objects.max_objects) params.objects.max_objects = pcs_objects::kDefaultMaxObjects;
+        if ((tracks() || boxes()) && !params.objects.max_objects) params.objects.max_objects = pcs_objects::kDefaultMaxObjects;
     }
 
     // Buffers for clouds of up to out_shorts shorts: one per enabled stage, two at the most.
@@ -282,12 +307,16 @@ struct Chain {
             params.objects.d_table = static_cast<pcs_cluster_object*>(d_objects);
             params.objects.d_n = static_cast<int32_t*>(d_n_objects);
         }
+        const size_t records = out_shorts / PCS_POINT_SHORTS;
+        if (rc == PCS_OK && (tracks() || boxes())) rc = pcs_device_malloc(ctx, &d_object_of, (records + 1) * sizeof(int32_t));
+        if (rc == PCS_OK && boxes()) {
+            rc = pcs_device_malloc(ctx, &d_boxes, (size_t)params.objects.max_objects * sizeof(pcs_object_box));
+            params.boxes.d_object_of = static_cast<int32_t*>(d_object_of); params.boxes.d_boxes = static_cast<pcs_object_box*>(d_boxes);
+        }
         if (rc == PCS_OK && tracks()) {      // max_cells: the records that can enter the chain
             auto& t = params.tracks;
-            const size_t records = out_shorts / PCS_POINT_SHORTS;
             const int max_cells = (int)(records < 1 ? 1 : records > (size_t)PCS_TRACKER_MAX_CELLS_MAX ? (size_t)PCS_TRACKER_MAX_CELLS_MAX : records);
             rc = pcs_tracker_create(ctx, t.cell_mm, max_cells, params.objects.max_objects, &t.tracker);
-            if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_object_of, (records + 1) * sizeof(int32_t));
             if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_tracks, (size_t)params.objects.max_objects * sizeof(pcs_track));
             if (rc == PCS_OK) rc = pcs_device_malloc(ctx, &d_track_stats, sizeof(pcs_track_stats));
             t.d_object_of = static_cast<int32_t*>(d_object_of); t.d_tracks = static_cast<pcs_track*>(d_tracks);
@@ -389,6 +418,35 @@ struct Chain {
         return true;
     }
 
+    // -W: the file opened and its header written, before the first frame-set. false: it cannot be written.
+    bool open_boxes()
+    {
+        if (boxes_file != "-") boxes_stream.open(boxes_file);
+        std::ostream& os = boxes_file == "-" ? std::cout : boxes_stream;
+        pcs_boxes::write_header(os);
+        os.flush();
+        return os.good();
+    }
+
+    // -W's lines of the last run(), appended; the run's totals kept for -t. false: a copy failed (pcs_last_error has it) or the file
+    // cannot be written (`why` says so).
+    bool write_boxes(std::string& why)
+    {
+        int32_t n_objects = 0;
+        if (pcs_memcpy_d2h(ctx, &n_objects, d_n_objects, sizeof n_objects) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
+        const int written = n_objects < 0 ? 0 : n_objects < params.objects.max_objects ? n_objects : params.objects.max_objects;
+        std::vector<pcs_object_box> entries((size_t)written);
+        if (written && (pcs_memcpy_d2h(ctx, entries.data(), d_boxes, entries.size() * sizeof entries[0]) != PCS_OK || pcs_synchronize(ctx) != PCS_OK))
+            return false;
+        std::ostream& os = boxes_file == "-" ? std::cout : boxes_stream;
+        pcs_boxes::write(os, boxes_frames++, entries.data(), written);
+        os.flush();
+        boxes_objects += written;
+        for (const pcs_object_box& b : entries) boxes_rank3 += b.rank == 3;
+        if (!os.good()) { why = "cannot write " + boxes_file; return false; }
+        return true;
+    }
+
     // -X learn: when the run ends: the model into its file, and with `say` the line. 0, or the status the program ends with (1) after a
     // message on `err`: an overflowed model, a failed call, a file that cannot be written.
     int finish_learning(std::ostream& os, std::ostream& err, bool say)
@@ -428,6 +486,8 @@ struct Chain {
         drop(d_object_of);
         drop(d_tracks);
         drop(d_track_stats);
+        drop(d_boxes);
+        params.boxes.d_object_of = nullptr; params.boxes.d_boxes = nullptr;
         params.tracks.d_object_of = nullptr; params.tracks.d_tracks = nullptr; params.tracks.d_stats = nullptr;
     }
 };

@@ -92,6 +92,11 @@
 //                      EVERY frame-set <file> (`-`: stdout) gets one line of raw integers per object, by ascending k, under the header
 //                      `# frame k id age prev votes label size lo_x lo_y lo_z hi_x hi_y hi_z sum_x sum_y sum_z`. -t prints `Tracks:
 //                      <born> born, <continued> continued, <lost> lost` over the run. Refused without -E and with -G.
+//              -W <file>  (with -E) which way an object lies: behind the E stage's objects call (and -J's update, where given) one
+//                      pcs_object_boxes_device, plain or counted by the chain's rule, over the cloud that stage read and its object_of.
+//                      After EVERY frame-set <file> (`-`: stdout) gets one line of raw integers per object, by ascending k: frame, k
+//                      and the entry's 27 integers in the struct's order, under one header line; a line joins -J's on (frame, k). -t
+//                      prints `Boxes: <objects> objects, <r> of rank 3` over the run. Refused without -E and with -G.
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
@@ -151,7 +156,7 @@ static void usage()
               << "                  as the reference's pcs-multicamera-optimized does (decode, pcl::transformPointCloud, re-encode)\n"
               << " -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box, millimetres in the world frame, inclusive: -i crops in the fused path, -c crops the\n"
               << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
-              << filters << pcs_objects::help() << pcs_tracks::help()
+              << filters << pcs_objects::help() << pcs_tracks::help() << pcs_boxes::help()
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
@@ -162,7 +167,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:X:J:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:X:J:W:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -217,6 +222,11 @@ int main(int argc, char** argv)
                 if (!chain.parse_tracks(optarg, why)) { std::cerr << "-J " << optarg << ": " << why << std::endl; return 2; }
                 break;
             }
+            case 'W': {
+                std::string why;
+                if (!chain.parse_boxes(optarg, why)) { std::cerr << "-W " << optarg << ": " << why << std::endl; return 2; }
+                break;
+            }
             case 's': case 'v': case 'n':
                 std::cerr << "-" << (char)c << " drives the reference's PCL viewer / PLY writer, which this build does not include" << std::endl;
                 return 2;
@@ -227,6 +237,7 @@ int main(int argc, char** argv)
     if (crop && n_gpus > 0) { std::cerr << "-B is not available with -G: the node library has no crop box setter" << std::endl; return 2; }
     chain.finish_options();
     if (chain.tracks() && n_gpus > 0) { std::cerr << "-J is not available with -G: the node library has no object tracker" << std::endl; return 2; }
+    if (chain.boxes() && n_gpus > 0) { std::cerr << "-W is not available with -G: the node library has no object boxes" << std::endl; return 2; }
     if (chain.objects() && n_gpus > 0) { std::cerr << "-L is not available with -G: the node library has no object table" << std::endl; return 2; }
     for (int k = 0; k < pcs_filter_chain::kStageCount; k++)
         if (chain.enabled[k] && n_gpus > 0) {
@@ -243,6 +254,9 @@ int main(int argc, char** argv)
     }
     if (chain.tracks() && !chain.enabled[pcs_filter_chain::kClusterStage]) {
         std::cerr << "-J tracks the objects of the cluster filter: it needs -E <tolerance_mm,min_size[,max_size]>" << std::endl; return 2;
+    }
+    if (chain.boxes() && !chain.enabled[pcs_filter_chain::kClusterStage]) {
+        std::cerr << "-W boxes the objects of the cluster filter: it needs -E <tolerance_mm,min_size[,max_size]>" << std::endl; return 2;
     }
     if (compressed && !cameras) { std::cerr << "-z decodes the frames of edge servers: it needs -c <edge list>" << std::endl; return 2; }
     if (source && cameras) { std::cerr << "give at most one of -i <src> or -c <edge list>" << std::endl; usage(); return 2; }
@@ -393,6 +407,7 @@ int main(int argc, char** argv)
         std::cerr << pcs_last_error(ctx) << std::endl; return 1;
     }
     if (chain.tracks() && !chain.open_tracks()) { std::cerr << "-J: cannot write " << chain.tracks_file << std::endl; return 1; }
+    if (chain.boxes() && !chain.open_boxes()) { std::cerr << "-W: cannot write " << chain.boxes_file << std::endl; return 1; }
 
     // -V: device-resident rasters (with -i) and the voxel cloud
     std::vector<void*> d_depth, d_color;
@@ -465,6 +480,10 @@ int main(int argc, char** argv)
         if (chain.tracks()) {      // -J: this frame-set's lines
             std::string why;
             if (!chain.write_tracks(why)) { std::cerr << "-J: " << (why.empty() ? pcs_last_error(ctx) : why.c_str()) << std::endl; return false; }
+        }
+        if (chain.boxes()) {       // -W: this frame-set's lines
+            std::string why;
+            if (!chain.write_boxes(why)) { std::cerr << "-W: " << (why.empty() ? pcs_last_error(ctx) : why.c_str()) << std::endl; return false; }
         }
         return true;
     };
@@ -748,6 +767,7 @@ int main(int argc, char** argv)
     }
     if (chain.tracks() && timer)
         std::cout << "Tracks: " << chain.tracks_born << " born, " << chain.tracks_continued << " continued, " << chain.tracks_lost << " lost" << std::endl;
+    if (chain.boxes() && timer) std::cout << "Boxes: " << chain.boxes_objects << " objects, " << chain.boxes_rank3 << " of rank 3" << std::endl;
     for (int fd : cam_fd) ::close(fd);
     if (client_fd >= 0) ::close(client_fd);
     if (listen_fd >= 0) ::close(listen_fd);

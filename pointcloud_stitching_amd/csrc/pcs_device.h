@@ -558,6 +558,22 @@ hipError_t launch_track_claim(const TrackerView& t, const int32_t* d_n_objects, 
 hipError_t launch_track_assign(const TrackerView& t, const int32_t* d_n_objects, uint32_t max_objects, uint32_t min_votes, long long frames,
                                void* d_tracks, long long* d_stats, hipStream_t st);
 
+// Object boxes (pcs_object_boxes_device*, pcs_kernels_boxes.hip; the definition: DESIGN.md section 3 "Object boxes"). The workspace
+// is kBoxWsWords int64 per object of max_objects (the ten sums of an object; 8-byte aligned). A call is the four launches below in
+// this order, every one launched whatever the counts. The record count is n_points, or *d_n_points clamped to 0..capacity when that
+// pointer is given, read on the device; m = *d_n_objects clamped to 0..max_objects. Extents are folded into d_boxes itself, whose
+// entries the axes launch wrote whole.
+constexpr uint32_t kBoxWsWords = 16;
+constexpr int kBoxLaunches = 4;              // clear, moments, axes, extents
+inline size_t boxes_workspace_bytes(uint32_t max_objects) { return (size_t)max_objects * kBoxWsWords * sizeof(long long); }
+hipError_t launch_boxes_clear(const int32_t* d_n_objects, uint32_t max_objects, void* d_ws, hipStream_t st);
+hipError_t launch_boxes_moments(const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
+                                const int32_t* d_object_of, const int32_t* d_n_objects, uint32_t max_objects, void* d_ws, hipStream_t st);
+hipError_t launch_boxes_axes(const int32_t* d_n_objects, uint32_t max_objects, const void* d_ws, pcs_object_box* d_boxes, hipStream_t st);
+hipError_t launch_boxes_extents(const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
+                                const int32_t* d_object_of, const int32_t* d_n_objects, uint32_t max_objects, pcs_object_box* d_boxes,
+                                hipStream_t st);
+
 // Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
 // index is the outlier filter's, cell edge max_dist_mm (launch_cell_index_stage over the target; `index` is its view, or nullptr for
 // an empty target: nobody matches). launch_align_match: one lane per source record, one 144-byte partial per

@@ -159,6 +159,10 @@ struct pcs_ctx {
     // trackers created on this context and not destroyed yet (pcs_capi_tracks.cpp): likewise
     std::vector<pcs_tracker*>       trackers;
 
+    // object boxes (pcs_capi_boxes.cpp): the ten sums per object of one call, boxes_workspace_bytes(max_objects), grown on demand by
+    // ensure_ws; the host form's staged object_of, count word and entries ride behind them
+    void*                           s_boxes_ws = nullptr; size_t s_boxes_ws_cap = 0;
+
     std::string                     err;
 };
 

@@ -62,6 +62,7 @@ BACKGROUND_SUBTRACT_LAUNCHES = ("flag", "tile count", "tile scan", "emit", "stat
 TRACK_STATS_FIELDS = ("considered", "voted", "objects", "continued", "born", "lost", "overflow", "frames")
 TRACK_UPDATE_LAUNCHES = ("records", "choose", "claim", "assign")     # in kernel_times_ms order: every update, every form
 TRACK_MIN_VOTES_MAX = 1 << 30
+OBJECT_BOXES_LAUNCHES = ("clear", "moments", "axes", "extents")      # in kernel_times_ms order: every call, every form
 TRACK_FIRST_ID_MAX = 1 << 62
 
 
@@ -308,6 +309,19 @@ class Track(C.Structure):
 
 TRACK_DTYPE = np.dtype([("id", "<i8"), ("age", "<i4"), ("prev", "<i4"), ("votes", "<i4"), ("reserved", "<i4")])
 assert TRACK_DTYPE.itemsize == C.sizeof(Track) == 24
+
+
+class ObjectBox(C.Structure):
+    """pcs_object_box: 128 bytes."""
+    _fields_ = [("count", C.c_int64), ("sum_xyz", C.c_int64 * 3), ("m2", C.c_int64 * 6), ("axis", (C.c_int16 * 3) * 3), ("rank", C.c_int16),
+                ("ext_lo", C.c_int32 * 3), ("ext_hi", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+OBJECT_BOX_DTYPE = np.dtype({"names": ["count", "sum_xyz", "m2", "axis", "rank", "ext_lo", "ext_hi", "reserved"],
+                             "formats": ["<i8", ("<i8", 3), ("<i8", 6), ("<i2", (3, 3)), "<i2", ("<i4", 3), ("<i4", 3), "<i4"],
+                             "offsets": [0, 8, 32, 80, 98, 100, 112, 124], "itemsize": 128})
+assert OBJECT_BOX_DTYPE.itemsize == C.sizeof(ObjectBox) == 128
+assert all(OBJECT_BOX_DTYPE.fields[name][1] == getattr(ObjectBox, name).offset for name in OBJECT_BOX_DTYPE.names)
 
 
 class TrackStats(C.Structure):

@@ -3,7 +3,9 @@
 // -X -O -K -M -E and a host-count or device-count start (-X FILE over a fake of the model calls: the imported model and the option's
 // parameters reach the subtract call; -X learn: the cloud that enters is learned by the plain or the counted call and passes unchanged), and every subset with -E again with -L (the objects form of the cluster call: the same
 // cloud out, the table and its count in blocks of the chain's own, the `Objects:` line and the file's lines), and -J over three subsets with and without -L
-// (the table either way, object_of out of the cluster call, one tracker update over the cloud that call read, the file's lines). A stand-alone program: no GPU, no library, nothing loaded into Python.
+// (the table either way, object_of out of the cluster call, one tracker update over the cloud that call read, the file's lines), and -W
+// with and without -J and -L (one boxes call behind the cluster call and the tracker's, over the same cloud, object_of and count word,
+// into a block of the chain's own; the file's lines; the run's totals). A stand-alone program: no GPU, no library, nothing loaded into Python.
 //
 //   make -C pointcloud_stitching_amd/cli ../../tools/bin/filter_chain_check && tools/bin/filter_chain_check
 //   (.../filter_chain_check_asan: the same under the host sanitizers)
@@ -20,7 +22,7 @@ using namespace pcs_filter_chain;
 
 static int g_failed = 0;
 #define EXPECT(cond) do { if (!(cond)) { printf("FAILED line %d (%s): %s\n", __LINE__, g_case, #cond); g_failed++; } } while (0)
-static char g_case[64] = "";
+static char g_case[96] = "";
 
 // ---- the fakes: "device" memory is host memory -------------------------------------------------------------------------------------
 struct pcs_ctx { int unused; };
@@ -284,6 +286,42 @@ int pcs_tracker_update_device_counted(pcs_ctx*, pcs_tracker* tr, const int16_t* 
                                       const int32_t* d_m, int max_objects, const pcs_track_params* p, pcs_track* tracks, pcs_track_stats* st)
 {
     return fake_update({tr, true, in, d_n, 0, max_points, object_of, d_m, max_objects, p->min_votes, tracks, st});
+}
+}
+// object boxes (-W): a call is recorded, with how many tracker updates and cluster calls stood in front of it, and writes what the
+// file's lines are made of
+struct BoxCall {
+    bool counted; const int16_t* in; const int32_t* d_n; int n_points, max_points;
+    const int32_t *object_of, *d_n_objects; int max_objects; pcs_object_box* boxes; size_t calls_before, updates_before;
+};
+static std::vector<BoxCall> g_box_calls;
+static pcs_object_box fake_box(int k, int call)
+{
+    pcs_object_box b{};
+    b.count = 100 + k; b.sum_xyz[0] = -7ll * k; b.sum_xyz[1] = 1ll << 40; b.sum_xyz[2] = call;
+    for (int q = 0; q < 6; q++) b.m2[q] = (1ll << 47) - q * k;
+    for (int a = 0; a < 3; a++)
+        for (int c = 0; c < 3; c++) b.axis[a][c] = (int16_t)(a == c ? 16384 : -(3 * a + c));
+    b.rank = (int16_t)(k % 2 ? 3 : 2);
+    for (int a = 0; a < 3; a++) { b.ext_lo[a] = -536870912 + a; b.ext_hi[a] = 536854528 - k; }
+    return b;
+}
+static int fake_boxes(BoxCall c)
+{
+    c.calls_before = g_calls.size(); c.updates_before = g_track_calls.size();
+    g_box_calls.push_back(c);
+    for (int k = 0; k < kFakeObjects && k < c.max_objects; k++) c.boxes[k] = fake_box(k, (int)g_box_calls.size() - 1);
+    return PCS_OK;
+}
+extern "C" {
+int pcs_object_boxes_device(pcs_ctx*, const int16_t* in, int n, const int32_t* object_of, const int32_t* d_m, int max_objects, pcs_object_box* boxes)
+{
+    return fake_boxes({false, in, nullptr, n, 0, object_of, d_m, max_objects, boxes, 0, 0});
+}
+int pcs_object_boxes_device_counted(pcs_ctx*, const int16_t* in, const int32_t* d_n, int max_points, const int32_t* object_of, const int32_t* d_m,
+                                    int max_objects, pcs_object_box* boxes)
+{
+    return fake_boxes({true, in, d_n, 0, max_points, object_of, d_m, max_objects, boxes, 0, 0});
 }
 }
 
@@ -562,6 +600,100 @@ static void check_tracks(int subset, Start start, int max_objects)
     remove(file.c_str());
 }
 
+// -W over the stages of `subset` (E among them, X not), with -J or without, with -L (max_objects) or without (0): the table and
+// object_of are made either way; behind the E stage's call, and behind the tracker's update where -J is given, one boxes call reads
+// the cloud THAT stage read, counted iff that stage's call was, with the stage's object_of and count word; the file gets the header
+// once and every frame-set's lines; release() leaves nothing.
+static void check_boxes(int subset, Start start, int max_objects, bool with_tracks)
+{
+    snprintf(g_case, sizeof g_case, "boxes over subset %d, %s, -L %d, -J %d", subset, kStartName[start], max_objects, (int)with_tracks);
+    pcs_ctx ctx{0};
+    const int capacity = 41, n_in = start == kDeviceFewer ? 29 : capacity;
+    std::vector<int16_t> cloud((size_t)capacity * PCS_POINT_SHORTS);
+    for (int i = 0; i < capacity; i++)
+        for (int k = 0; k < PCS_POINT_SHORTS; k++) cloud[i * PCS_POINT_SHORTS + k] = (int16_t)(k ? 100 * i + k : i % 6);
+    int32_t count = n_in;
+    const Cloud in{cloud.data(), start == kHost ? nullptr : &count, start == kHost ? n_in : -12345, capacity};
+    Chain chain;
+    std::string why;
+    const char* const args[kStageCount] = {"", "11,2", "22,1000,30", "33,16,3,2,5", "44,3"};
+    int n_enabled = 0;
+    for (int s = 1; s < kStageCount; s++)
+        if (subset >> s & 1) { EXPECT(chain.parse(kStages[s].letter, args[s], why)); n_enabled++; }
+    const std::string file = "filter_chain_check_boxes.tmp", tracks_file = "filter_chain_check_boxes_tracks.tmp";
+    EXPECT(!chain.boxes() && !chain.parse_boxes("", why) && why.find("empty") != std::string::npos && !chain.boxes());
+    EXPECT(!chain.parse_boxes("b.txt,5", why) && !chain.parse_boxes("-E", why) && !chain.parse_boxes(",", why) && !chain.boxes());
+    EXPECT(chain.parse_boxes("-", why) && chain.boxes() && chain.boxes_file == "-");
+    EXPECT(chain.parse_boxes(file.c_str(), why) && chain.boxes() && chain.boxes_file == file);
+    if (with_tracks) EXPECT(chain.parse_tracks((tracks_file + ",250,7").c_str(), why));
+    if (max_objects) EXPECT(chain.parse_objects(("objects.txt," + std::to_string(max_objects)).c_str(), why));
+    chain.finish_options();
+    const int table = max_objects ? max_objects : pcs_objects::kDefaultMaxObjects;      // without -L: the table at -L's default size
+    EXPECT(chain.params.objects.max_objects == table && chain.objects() == (max_objects != 0) && chain.tracks() == with_tracks);
+    g_live.clear(); g_track_calls.clear(); g_box_calls.clear();
+    EXPECT(chain.allocate(&ctx, (size_t)capacity * PCS_POINT_SHORTS) == PCS_OK);
+    EXPECT(g_trackers.size() == (with_tracks ? 1u : 0u));
+    EXPECT(g_live.count(chain.d_object_of) && g_live[chain.d_object_of] >= (size_t)capacity * sizeof(int32_t));
+    EXPECT(g_live.count(chain.d_boxes) && g_live[chain.d_boxes] == (size_t)table * sizeof(pcs_object_box));
+    EXPECT(g_live.count(chain.d_objects) && g_live[chain.d_objects] == (size_t)table * sizeof(pcs_cluster_object));
+    EXPECT(with_tracks ? g_live.count(chain.d_tracks) == 1 : chain.d_tracks == nullptr && chain.d_track_stats == nullptr);
+    remove(file.c_str());
+    EXPECT(chain.open_boxes());
+    if (with_tracks) EXPECT(chain.open_tracks());
+    std::ostringstream want;
+    pcs_boxes::write_header(want);
+    long long rank3 = 0;
+    for (int frame = 0; frame < 3; frame++) {
+        g_calls.clear();
+        const Cloud out = chain.run(&ctx, in);
+        EXPECT(chain.status == PCS_OK && (int)g_calls.size() == n_enabled && (int)g_box_calls.size() == frame + 1 && out.d_n);
+        EXPECT((int)g_track_calls.size() == (with_tracks ? frame + 1 : 0));
+        const Call& e = g_calls.back();
+        const BoxCall& b = g_box_calls.back();
+        EXPECT(e.stage == 4 && e.objects == chain.d_objects && e.max_objects == table);
+        EXPECT(b.calls_before == (size_t)n_enabled && b.updates_before == g_track_calls.size());    // behind the E stage's call and the tracker's
+        EXPECT(b.in == e.in && b.d_n == e.d_n && b.counted == e.counted);                          // the cloud the E stage read, by the same rule
+        EXPECT(b.counted == (n_enabled > 1 || start != kHost));
+        if (b.counted) EXPECT(b.max_points == capacity); else EXPECT(b.n_points == n_in);
+        EXPECT(b.object_of == chain.d_object_of && b.d_n_objects == chain.d_n_objects && b.max_objects == table && b.boxes == chain.d_boxes);
+        if (with_tracks) EXPECT(g_track_calls.back().object_of == b.object_of && g_track_calls.back().in == b.in);
+        EXPECT(chain.write_boxes(why) && g_box_calls.size() == (size_t)frame + 1);                  // (writing launches nothing)
+        if (with_tracks) EXPECT(chain.write_tracks(why));
+        std::vector<pcs_object_box> entries;
+        for (int k = 0; k < kFakeObjects && k < table; k++) { entries.push_back(fake_box(k, frame)); rank3 += entries.back().rank == 3; }
+        pcs_boxes::write(want, frame, entries.data(), (int)entries.size());
+    }
+    const int written = kFakeObjects < table ? kFakeObjects : table;
+    EXPECT(chain.boxes_frames == 3 && chain.boxes_objects == 3 * written && chain.boxes_rank3 == rank3);
+    std::ifstream f(file);
+    std::stringstream got;
+    got << f.rdbuf();
+    EXPECT(got.str() == want.str());
+    EXPECT(got.str().rfind("# frame k count sum_x sum_y sum_z m_xx m_xy m_xz m_yy m_yz m_zz a0_x a0_y a0_z a1_x a1_y a1_z a2_x a2_y a2_z rank "
+                           "lo_0 lo_1 lo_2 hi_0 hi_1 hi_2 reserved\n", 0) == 0);
+    if (table >= 2)
+        EXPECT(got.str().find("\n2 1 101 -7 1099511627776 2 140737488355328 140737488355327 140737488355326 140737488355325 140737488355324 "
+                              "140737488355323 16384 -1 -2 -3 16384 -5 -6 -7 16384 3 -536870912 -536870911 -536870910 536854527 536854527 "
+                              "536854527 0\n") != std::string::npos);
+    {   // every line: 29 integers
+        std::string line;
+        std::getline(got, line);
+        while (std::getline(got, line)) {
+            int fields = 1;
+            for (char ch : line) fields += ch == ' ';
+            EXPECT(fields == 29);
+        }
+    }
+    chain.release();
+    EXPECT(g_live.empty() && g_trackers.empty() && g_bad_frees == 0);
+    chain.release();      // (nothing left to free)
+    EXPECT(g_bad_frees == 0);
+    chain.boxes_stream.close();
+    chain.tracks_stream.close();
+    remove(file.c_str());
+    remove(tracks_file.c_str());
+}
+
 int main()
 {
     for (int subset = 0; subset < 32; subset++)
@@ -576,6 +708,10 @@ int main()
     for (int subset : {16, 18, 30})
         for (Start start : {kHost, kDeviceFewer, kDeviceFull})
             for (int max_objects : {0, 3, 1024}) check_tracks(subset, start, max_objects);
+    for (int subset : {16, 18, 30})
+        for (Start start : {kHost, kDeviceFewer, kDeviceFull})
+            for (int max_objects : {0, 3, 1024})
+                for (bool with_tracks : {false, true}) check_boxes(subset, start, max_objects, with_tracks);
     printf(g_failed ? "filter_chain_check: %d check(s) FAILED\n" : "filter_chain_check: all checks passed, no report\n", g_failed);
     fflush(stdout);      // (a leak report at exit must not swallow the lines above)
     return g_failed ? 1 : 0;
