@@ -1201,6 +1201,66 @@ int pcs_object_boxes_device_counted(pcs_ctx* ctx, const int16_t* d_payload, cons
 int pcs_object_boxes(pcs_ctx* ctx, const int16_t* payload, int n_points, const int32_t* object_of, int n_objects, int max_objects,
                      pcs_object_box* boxes);               /* host pointers, staged, synchronous */
 
+/* ---- plan-view maps: an orthographic raster of the cloud along a coordinate axis (not in the reference) ---------------------------- *
+ * Every other output of the centre side is a table; this one is a picture: what is occupied and how high it is, seen along an axis.
+ * DESIGN.md section 3 "Plan-view maps" has the definition; all of it is integer arithmetic on the records' shorts.
+ * Input: n records of PCS_POINT_SHORTS shorts (x, y, z, R | G << 8, B) at any 2-byte phase; i = a record's position. The call knows
+ *   nothing of invalid depth: a dense payload's zero-depth pixels sit on their camera's origin and pile into one cell (give
+ *   PCS_FLAG_DROP_INVALID / -Z or a crop box first).
+ * pcs_plan_params: up_axis a in 0..2 and up_sign s in {+1, -1}: the map axes are u = (a + 1) % 3 and v = (a + 2) % 3, a record's
+ *   height is h = s p[a]. cell_mm c in 1..32767. origin_u, origin_v in -32768..32767: the low corner of cell (0, 0). width W and
+ *   height H in 1..PCS_PLAN_SIDE_MAX with W H <= PCS_PLAN_CELLS_MAX. band_lo <= band_hi inside int16: a record TAKES PART iff
+ *   band_lo <= p[a] <= band_hi (the raw coordinate, both ends inclusive). reserved words 0.
+ * Mapping: cu = floor((p[u] - origin_u) / c), cv = floor((p[v] - origin_v) / c); the record is ON THE MAP iff 0 <= cu < W and
+ *   0 <= cv < H; its cell is cv W + cu.
+ * Output, W H cells each, nothing written outside them:
+ *   count   uint32: the in-band, on-map records of the cell.
+ *   top     int16: p[a] (raw) of the cell's top record, the member of greatest h, among equal h the one of LOWEST index.
+ *   bottom  int16: p[a] of the member of least h, among equal h the one of lowest index.
+ *   rgb     3 bytes R, G, B: the top record's colour bytes.
+ *   An empty cell has count 0, top = bottom = 0 and rgb = 0, 0, 0: count is what says "empty".
+ *   stats   considered (= n), in_band, mapped, occupied (cells with count > 0), fullest (the largest count), reserved 0.
+ * Deterministic: counts and extremes over integers with an index tie-break; the bytes depend on the input bytes alone.
+ *   tests/np_plan_view.py restates it.
+ * pcs_plan_view_device: asynchronous on the context's stream, no host round trip; every pointer a device pointer, all five of
+ *   pcs_plan_maps required: count 4-byte aligned, top and bottom 2-byte, stats 8-byte; the payload 2-byte aligned (NULL only with a
+ *   count of 0). pcs_plan_view_device_counted: the count is read from *d_n_points (device, 4-byte aligned) when the kernels run,
+ *   clamped to 0..max_points; records at or beyond it are never read. pcs_plan_view: host pointers, staged, synchronous. A count of
+ *   0 is a normal call in every form: it writes the empty map.
+ * Workspace: 16 bytes per cell in a slab of the context, grown on demand (the host form's rasters ride behind it).
+ * Refused with PCS_ERR_INVALID_ARG (pcs_last_error names the function and the argument), nothing launched, nothing written: a
+ *   parameter out of range or a reserved word that is not 0, a count outside 0 .. INT_MAX / 10, a NULL or misaligned pointer, an
+ *   output sharing a byte with an input or with another output.
+ * Launches, every call, all three forms, whatever the counts: PCS_PLAN_VIEW_LAUNCHES (clear, accumulate, resolve). With
+ *   pcs_kernel_timing enabled a call yields one interval per launch. Measured: DESIGN.md section 10 (f19).                           */
+#define PCS_PLAN_VIEW_LAUNCHES 3
+#define PCS_PLAN_SIDE_MAX 4096
+#define PCS_PLAN_CELLS_MAX (1 << 22)
+typedef struct pcs_plan_params {                            /* 48 bytes */
+    int32_t up_axis, up_sign;
+    int32_t cell_mm;
+    int32_t origin_u, origin_v;
+    int32_t width, height;
+    int32_t band_lo, band_hi;
+    int32_t reserved[3];                                    /* 0 */
+} pcs_plan_params;
+struct pcs_plan_stats {                                     /* 64 bytes, 8-byte aligned */
+    int64_t considered, in_band, mapped, occupied, fullest;
+    int64_t reserved[3];                                    /* 0 */
+};
+typedef struct pcs_plan_maps {                              /* a host struct of pointers, all required */
+    uint32_t* count;
+    int16_t*  top;
+    int16_t*  bottom;
+    uint8_t*  rgb;
+    struct pcs_plan_stats* stats;
+} pcs_plan_maps;
+int pcs_plan_view_device(pcs_ctx* ctx, const int16_t* d_payload, int n_points, const pcs_plan_params* params, const pcs_plan_maps* maps);
+int pcs_plan_view_device_counted(pcs_ctx* ctx, const int16_t* d_payload, const int32_t* d_n_points, int max_points,
+                                 const pcs_plan_params* params, const pcs_plan_maps* maps);
+int pcs_plan_view(pcs_ctx* ctx, const int16_t* payload, int n_points, const pcs_plan_params* params,
+                  const pcs_plan_maps* host_maps);         /* host pointers, staged, synchronous */
+
 /* ---- extrinsics refinement: nearest-neighbour alignment sums, the rigid fit, the ICP loop (not in the reference) ---------------- *
  * transform[i] comes from four surveyed markers (calibration.py); these calls refine it from the data: move one camera's payload
  * onto another's where they overlap. DESIGN.md section 3 "Alignment sums" has the definition and what follows from it.

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _libmod
-from .types import (BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, OBJECT_BOX_DTYPE, ObjectBox, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, Track, TRACK_DTYPE, TrackParams, TrackStats, TrackerInfo, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
+from .types import (BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReport, AlignPlaneReportC, AlignPlaneSums, AlignPlaneSumsC, AlignReport, AlignReportC, AlignSums, AlignSumsC, CloudDesc, CLUSTER_OBJECT_DTYPE, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, NORMAL_SHORTS, OBJECT_BOX_DTYPE, ObjectBox, PlanMaps, PlanParams, PlanStats, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, STATUS_NAMES, Track, TRACK_DTYPE, TrackParams, TrackStats, TrackerInfo, POINT_SHORTS, POINT_BYTES, HEADER_SHORTS,
                     REF_BUF_SIZE, stream_array)
 
 
@@ -919,6 +919,31 @@ class PcsContext:
         pcs_object_boxes_device_counted."""
         self._check(self._lib.pcs_object_boxes_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
                                                               d_object_of or None, d_n_objects or None, int(max_objects), d_boxes or None))
+
+    # -- plan-view maps (defined by this build; see include/pcs_hip.h) --------------------------------
+    def plan_view(self, payload: np.ndarray, params: PlanParams):
+        """Packed records (int16 [n,5]) -> (count uint32 [H,W], top int16 [H,W], bottom int16 [H,W], rgb uint8 [H,W,3], stats dict):
+        the plan-view maps of pcs_plan_view (host arrays, staged, synchronous). Row cv, column cu."""
+        p = np.ascontiguousarray(payload, np.int16).reshape(-1, POINT_SHORTS)
+        h, w = max(int(params.height), 1), max(int(params.width), 1)
+        count, top, bottom = np.zeros((h, w), np.uint32), np.zeros((h, w), np.int16), np.zeros((h, w), np.int16)
+        rgb, stats = np.zeros((h, w, 3), np.uint8), PlanStats()
+        maps = PlanMaps(_ptr(count), _ptr(top), _ptr(bottom), _ptr(rgb), C.addressof(stats))
+        self._check(self._lib.pcs_plan_view(self._h, _ptr(p) if p.shape[0] else None, p.shape[0], C.byref(params), C.byref(maps)))
+        return count, top, bottom, rgb, stats.as_dict()
+
+    def plan_view_device(self, d_payload: int, n_points: int, params: PlanParams, maps: PlanMaps) -> None:
+        """Asynchronous; device pointers as ints inside `maps` (types.PlanMaps.make): count (uint32 per cell), top, bottom (int16),
+        rgb (3 bytes), stats (64 bytes). See pcs_plan_view_device."""
+        self._check(self._lib.pcs_plan_view_device(self._h, d_payload or None, int(n_points), C.byref(params) if params is not None else None,
+                                                   C.byref(maps) if maps is not None else None))
+
+    def plan_view_device_counted(self, d_payload: int, d_n_points: int, max_points: int, params: PlanParams, maps: PlanMaps) -> None:
+        """The record count is read from device memory (d_n_points, clamped to 0..max_points) when the kernels run. See
+        pcs_plan_view_device_counted."""
+        self._check(self._lib.pcs_plan_view_device_counted(self._h, d_payload or None, d_n_points or None, int(max_points),
+                                                           C.byref(params) if params is not None else None,
+                                                           C.byref(maps) if maps is not None else None))
 
     # -- background model and subtraction (defined by this build; see include/pcs_hip.h) ------------
     def background_create(self, cell_mm: int, max_cells: int) -> Background:

@@ -21,6 +21,10 @@
 // -W (pcs_boxes.h) stands beside it: the same table and object_of, and behind the stage's call (and the tracker's, where -J is given
 // too) one pcs_object_boxes_device* over the cloud the stage read, on the same count rule, into a device block of the chain's own.
 // write_boxes() copies the entries after the frame-set's launches and appends the frame-set's lines.
+//
+// -H (pcs_planview.h) is no stage and drops nothing: behind run(), ahead of -V, plan_view() reads the cloud that leaves the chain (the
+// last enabled stage's output, or what entered if none is on) with one pcs_plan_view_device*, on the same count rule, into a device
+// block of the chain's own. write_plan() copies the rasters after the run's last frame-set and writes the three files.
 #pragma once
 
 #include <cstring>
@@ -36,6 +40,7 @@
 #include "pcs_objects.h"
 #include "pcs_outlier.h"
 #include "pcs_plane.h"
+#include "pcs_planview.h"
 #include "pcs_statoutlier.h"
 #include "pcs_tracks.h"
 
@@ -215,6 +220,10 @@ struct Chain {
     std::string boxes_file;
     std::ofstream boxes_stream;
     long long boxes_frames = 0, boxes_objects = 0, boxes_rank3 = 0;
+    // -H: the option's words, the device block that holds the four rasters and the statistics block (views of it in plan_maps), and
+    // whether a frame-set went through
+    struct { bool on = false; std::string prefix; pcs_plan_params params{}; pcs_plan_maps maps{}; bool ran = false; } plan;
+    void* d_plan = nullptr;
     // -X learn: the option's words and the model allocate() creates; -X FILE: the file's bytes (load_background), imported by allocate()
     struct { std::string file; int cell_mm = 0, max_cells = 0; pcs_background* model = nullptr; } learn;
     std::vector<char> background_bytes;
@@ -223,7 +232,7 @@ struct Chain {
     bool any() const
     {
         for (bool e : enabled) if (e) return true;
-        return learning();
+        return learning() || plan.on;
     }
 
     // -X's argument, either form. false: `why` says what is wrong with it.
@@ -280,6 +289,13 @@ struct Chain {
         return params.boxes.on = pcs_boxes::parse(arg, boxes_file, why);
     }
     bool boxes() const { return params.boxes.on; }
+    // -H's argument: the prefix and the map. false: `why` says what is wrong with it.
+    bool parse_plan(const char* arg, std::string& why)
+    {
+        if (plan.on) { why = "the option was given twice"; return false; }
+        return plan.on = pcs_planview::parse(arg, plan.prefix, plan.params, why);
+    }
+    bool plan_view() const { return plan.on; }
     void finish_options()
     {
         if ((tracks() || boxes()) && !params.objects.max_objects) params.objects.max_objects = pcs_objects::kDefaultMaxObjects;
@@ -313,6 +329,16 @@ struct Chain {
             rc = pcs_device_malloc(ctx, &d_boxes, (size_t)params.objects.max_objects * sizeof(pcs_object_box));
             params.boxes.d_object_of = static_cast<int32_t*>(d_object_of); params.boxes.d_boxes = static_cast<pcs_object_box*>(d_boxes);
         }
+        if (rc == PCS_OK && plan.on) {       // one block: count, top, bottom, rgb, statistics, each at 256 bytes
+            const size_t cells = (size_t)plan.params.width * plan.params.height;
+            auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+            const size_t at_top = up(4 * cells), at_bottom = at_top + up(2 * cells), at_rgb = at_bottom + up(2 * cells), at_stats = at_rgb + up(3 * cells);
+            rc = pcs_device_malloc(ctx, &d_plan, at_stats + 256);
+            uint8_t* const b = static_cast<uint8_t*>(d_plan);
+            if (rc == PCS_OK)
+                plan.maps = pcs_plan_maps{reinterpret_cast<uint32_t*>(b), reinterpret_cast<int16_t*>(b + at_top), reinterpret_cast<int16_t*>(b + at_bottom),
+                                          b + at_rgb, reinterpret_cast<pcs_plan_stats*>(b + at_stats)};
+        }
         if (rc == PCS_OK && tracks()) {      // max_cells: the records that can enter the chain
             auto& t = params.tracks;
             const int max_cells = (int)(records < 1 ? 1 : records > (size_t)PCS_TRACKER_MAX_CELLS_MAX ? (size_t)PCS_TRACKER_MAX_CELLS_MAX : records);
@@ -341,6 +367,49 @@ struct Chain {
             in = Cloud{d_out, d_n_out, 0, in.capacity};
         }
         return in;
+    }
+
+    // -H: the maps of `out`, the cloud run() returned, on the chain's count rule. Launches only; copies nothing to the host.
+    int run_plan(pcs_ctx* c, const Cloud& out)
+    {
+        plan.ran = true;
+        return out.d_n ? pcs_plan_view_device_counted(c, out.d, out.d_n, out.capacity, &plan.params, &plan.maps)
+                       : pcs_plan_view_device(c, out.d, out.n, &plan.params, &plan.maps);
+    }
+
+    // -H's -t line of the last run_plan(). false: a copy failed (pcs_last_error has it).
+    bool report_plan(std::ostream& os) const
+    {
+        pcs_plan_stats st{};
+        if (pcs_memcpy_d2h(ctx, &st, plan.maps.stats, sizeof st) != PCS_OK || pcs_synchronize(ctx) != PCS_OK) return false;
+        pcs_planview::report(os, plan.params, st);
+        return true;
+    }
+
+    // -H's three files from the last run_plan() (an empty map if no frame-set went through). false: a copy failed (pcs_last_error has
+    // it) or a file cannot be written (`why` names it).
+    bool write_plan(std::string& why) const
+    {
+        const int w = plan.params.width, h = plan.params.height;
+        const size_t cells = (size_t)w * h;
+        std::vector<uint32_t> count(cells, 0u);
+        std::vector<int16_t> top(cells, 0);
+        std::vector<uint8_t> rgb(3 * cells, 0);
+        if (plan.ran && (pcs_memcpy_d2h(ctx, count.data(), plan.maps.count, 4 * cells) != PCS_OK ||
+                         pcs_memcpy_d2h(ctx, top.data(), plan.maps.top, 2 * cells) != PCS_OK ||
+                         pcs_memcpy_d2h(ctx, rgb.data(), plan.maps.rgb, 3 * cells) != PCS_OK || pcs_synchronize(ctx) != PCS_OK))
+            return false;
+        const char* const names[3] = {".rgb.ppm", ".top.pgm", ".count.pgm"};
+        for (int k = 0; k < 3; k++) {
+            const std::string file = plan.prefix + names[k];
+            std::ofstream f(file, std::ios::binary);
+            if (k == 0) pcs_planview::write_rgb_ppm(f, w, h, rgb.data());
+            else if (k == 1) pcs_planview::write_top_pgm(f, plan.params, count.data(), top.data());
+            else pcs_planview::write_count_pgm(f, w, h, count.data());
+            f.flush();
+            if (!f.good()) { why = "cannot write " + file; return false; }
+        }
+        return true;
     }
 
     // The -t lines of the last run(), in stage order. false: a copy failed (pcs_last_error has it).
@@ -487,6 +556,8 @@ struct Chain {
         drop(d_tracks);
         drop(d_track_stats);
         drop(d_boxes);
+        drop(d_plan);
+        plan.maps = pcs_plan_maps{};
         params.boxes.d_object_of = nullptr; params.boxes.d_boxes = nullptr;
         params.tracks.d_object_of = nullptr; params.tracks.d_tracks = nullptr; params.tracks.d_stats = nullptr;
     }

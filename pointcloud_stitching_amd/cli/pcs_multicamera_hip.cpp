@@ -97,6 +97,11 @@
 //                      After EVERY frame-set <file> (`-`: stdout) gets one line of raw integers per object, by ascending k: frame, k
 //                      and the entry's 27 integers in the struct's order, under one header line; a line joins -J's on (frame, k). -t
 //                      prints `Boxes: <objects> objects, <r> of rank 3` over the run. Refused without -E and with -G.
+//              -H <prefix>,<up>,<cell_mm>,<W>x<H>[,<u0>,<v0>[,<lo>,<hi>]]  plan-view maps (pcs_planview.h): no stage, drops nothing. Each
+//                      frame-set one pcs_plan_view_device, plain or counted by the chain's rule, over the cloud that LEAVES the chain
+//                      (the stitched cloud if no stage is on), ahead of -V. After the last frame-set <prefix>.rgb.ppm, <prefix>.top.pgm
+//                      and <prefix>.count.pgm are written: file row r is map row cv = r, no flip. -t prints `Plan view: <n> considered,
+//                      <b> in band, <m> on the map, <o> occupied of <W> x <H> cells, fullest <f>` per frame-set. Refused with -G.
 //     with neither -i nor -c the cameras are 8 synthetic 1280x720 streams on this node (there are no live cameras here).
 #include <chrono>
 #include <cstdio>
@@ -156,7 +161,7 @@ static void usage()
               << "                  as the reference's pcs-multicamera-optimized does (decode, pcl::transformPointCloud, re-encode)\n"
               << " -B <xlo,xhi,ylo,yhi,zlo,zhi>  crop box, millimetres in the world frame, inclusive: -i crops in the fused path, -c crops the\n"
               << "                  received payloads (after -T; -d then keeps every d-th KEPT record per camera); not with -G\n"
-              << filters << pcs_objects::help() << pcs_tracks::help() << pcs_boxes::help()
+              << filters << pcs_objects::help() << pcs_tracks::help() << pcs_boxes::help() << pcs_planview::help()
               << " -z               with -c: every edge sends a compressed frame (pcs-camera-optimized -z: a PCZ1 container); each is validated\n"
               << "                  and decoded on the GPU before the stitch; what is served on -p stays raw\n"
               << " -P               with -G and -i synth:<W>x<H>: device-resident frame loop, two frame-sets in flight (submit / wait)\n"
@@ -167,7 +172,7 @@ int main(int argc, char** argv)
 {
     signal(SIGPIPE, SIG_IGN);
     int c;
-    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:X:J:W:")) != -1) {
+    while ((c = getopt(argc, argv, "hftsvd:nc:N:g:p:r:o:qG:i:V:ZR:PT:B:zO:K:E:M:L:X:J:W:H:")) != -1) {
         switch (c) {
             case 't': timer = true; break;
             case 'd': downsample = atoi(optarg); break;
@@ -227,6 +232,11 @@ int main(int argc, char** argv)
                 if (!chain.parse_boxes(optarg, why)) { std::cerr << "-W " << optarg << ": " << why << std::endl; return 2; }
                 break;
             }
+            case 'H': {
+                std::string why;
+                if (!chain.parse_plan(optarg, why)) { std::cerr << "-H " << optarg << ": " << why << std::endl; return 2; }
+                break;
+            }
             case 's': case 'v': case 'n':
                 std::cerr << "-" << (char)c << " drives the reference's PCL viewer / PLY writer, which this build does not include" << std::endl;
                 return 2;
@@ -238,6 +248,7 @@ int main(int argc, char** argv)
     chain.finish_options();
     if (chain.tracks() && n_gpus > 0) { std::cerr << "-J is not available with -G: the node library has no object tracker" << std::endl; return 2; }
     if (chain.boxes() && n_gpus > 0) { std::cerr << "-W is not available with -G: the node library has no object boxes" << std::endl; return 2; }
+    if (chain.plan_view() && n_gpus > 0) { std::cerr << "-H is not available with -G: the node library has no plan view" << std::endl; return 2; }
     if (chain.objects() && n_gpus > 0) { std::cerr << "-L is not available with -G: the node library has no object table" << std::endl; return 2; }
     for (int k = 0; k < pcs_filter_chain::kStageCount; k++)
         if (chain.enabled[k] && n_gpus > 0) {
@@ -458,6 +469,7 @@ int main(int argc, char** argv)
     auto filter_to_stitched = [&](const Cloud& in) -> bool {
         const Cloud c = chain.run(ctx, in);
         if (chain.status != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return false; }
+        if (chain.plan_view() && chain.run_plan(ctx, c) != PCS_OK) { std::cerr << pcs_last_error(ctx) << std::endl; return false; }     // -H
         if (voxel_leaf) {
             auto run_voxel = [&]() {
                 int16_t* out = static_cast<int16_t*>(d_vox);
@@ -477,6 +489,7 @@ int main(int argc, char** argv)
             memcpy(stitched.data(), &size_bytes, sizeof(int));                                             // :394-395
         }
         if (timer && !chain.report(std::cout)) { std::cerr << pcs_last_error(ctx) << std::endl; return false; }
+        if (timer && chain.plan_view() && !chain.report_plan(std::cout)) { std::cerr << pcs_last_error(ctx) << std::endl; return false; }
         if (chain.tracks()) {      // -J: this frame-set's lines
             std::string why;
             if (!chain.write_tracks(why)) { std::cerr << "-J: " << (why.empty() ? pcs_last_error(ctx) : why.c_str()) << std::endl; return false; }
@@ -765,6 +778,11 @@ int main(int argc, char** argv)
         }
         if (!ok) std::cerr << "-L: " << pcs_last_error(ctx) << std::endl;
     }
+    int plan_status = 0;
+    if (chain.plan_view()) {    // -H: the last frame-set's maps
+        std::string why;
+        if (!chain.write_plan(why)) { std::cerr << "-H: " << (why.empty() ? pcs_last_error(ctx) : why.c_str()) << std::endl; plan_status = 1; }
+    }
     if (chain.tracks() && timer)
         std::cout << "Tracks: " << chain.tracks_born << " born, " << chain.tracks_continued << " continued, " << chain.tracks_lost << " lost" << std::endl;
     if (chain.boxes() && timer) std::cout << "Boxes: " << chain.boxes_objects << " objects, " << chain.boxes_rank3 << " of rank 3" << std::endl;
@@ -784,5 +802,5 @@ int main(int argc, char** argv)
     if (node) pcs_node_destroy(node);
     stitched.release();
     pcs_destroy(ctx);
-    return learn_status;
+    return learn_status ? learn_status : plan_status;
 }

@@ -739,6 +739,7 @@ void pcs_destroy(pcs_ctx* c)
     if (c->s_align_ws) (void)hipFree(c->s_align_ws);
     if (c->s_normals_ws) (void)hipFree(c->s_normals_ws);
     if (c->s_boxes_ws) (void)hipFree(c->s_boxes_ws);
+    if (c->s_plan_ws) (void)hipFree(c->s_plan_ws);
     if (c->d_codec_bytes) (void)hipFree(c->d_codec_bytes);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/pcs_hip.h"
+#include "pcs_plan_math.h"
 
 namespace pcs {
 
@@ -573,6 +574,20 @@ hipError_t launch_boxes_axes(const int32_t* d_n_objects, uint32_t max_objects, c
 hipError_t launch_boxes_extents(const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity,
                                 const int32_t* d_object_of, const int32_t* d_n_objects, uint32_t max_objects, pcs_object_box* d_boxes,
                                 hipStream_t st);
+
+// Plan-view maps (pcs_plan_view_device*, pcs_kernels_plan.hip; the definition: DESIGN.md section 3 "Plan-view maps"; the arithmetic:
+// pcs_plan_math.h). The workspace is one 64-bit key per cell for the top and one for the bottom, each carved at 256 bytes (8-byte
+// aligned); the count raster is accumulated in place and the statistics block folded in place (eight int64). A call is the three
+// launches below in this order, every one launched whatever the counts. The record count is n_points, or *d_n_points clamped to
+// 0..capacity when that pointer is given, read on the device. P.magic = plan_magic(P.cell_mm).
+constexpr int kPlanLaunches = 3;             // clear, accumulate, resolve
+size_t plan_workspace_bytes(uint32_t cells);
+hipError_t launch_plan_clear(uint32_t n_points, const int32_t* d_n_points, uint32_t capacity, const PlanArgs& P, void* d_ws, uint32_t* d_count,
+                             long long* d_stats, hipStream_t st);
+hipError_t launch_plan_accumulate(const int16_t* d_in, uint32_t n_points, const int32_t* d_n_points, uint32_t capacity, const PlanArgs& P,
+                                  void* d_ws, uint32_t* d_count, long long* d_stats, hipStream_t st);
+hipError_t launch_plan_resolve(const int16_t* d_in, uint32_t capacity, const PlanArgs& P, const void* d_ws, const uint32_t* d_count,
+                               int16_t* d_top, int16_t* d_bottom, uint8_t* d_rgb, long long* d_stats, hipStream_t st);
 
 // Alignment sums (pcs_align_sums_device, pcs_kernels_align.hip; the definition: DESIGN.md section 3 "Alignment sums"). The target's
 // index is the outlier filter's, cell edge max_dist_mm (launch_cell_index_stage over the target; `index` is its view, or nullptr for

@@ -163,6 +163,12 @@ struct pcs_ctx {
     // ensure_ws; the host form's staged object_of, count word and entries ride behind them
     void*                           s_boxes_ws = nullptr; size_t s_boxes_ws_cap = 0;
 
+    // plan-view maps (pcs_capi_plan.cpp): the two keys per cell of one call, plan_workspace_bytes(cells), grown on demand by
+    // ensure_ws; the host form's rasters and statistics block ride behind them. plan_cell_checked: the cell edge whose multiply-shift
+    // division the host has swept (0: none yet)
+    void*                           s_plan_ws = nullptr; size_t s_plan_ws_cap = 0;
+    int32_t                         plan_cell_checked = 0;
+
     std::string                     err;
 };
 

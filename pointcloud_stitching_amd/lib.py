@@ -10,7 +10,7 @@ import os
 import subprocess
 from typing import Optional
 
-from .types import BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, ObjectBox, PayloadDesc, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, Track, TrackParams, TrackStats, TrackerInfo
+from .types import BackgroundInfo, BackgroundParams, BackgroundStats, AlignParams, AlignPlaneParams, AlignPlaneReportC, AlignPlaneSumsC, AlignReportC, AlignSumsC, CloudDesc, ClusterObject, ClusterObjectsOut, ClusterParams, ClusterStatsC, CompressedInfo, Config, DepthFilterConfig, NormalParams, ObjectBox, PayloadDesc, PlanMaps, PlanParams, PlaneModel, PlaneParams, PlaneStats, SpatialFilterConfig, StatOutlierParams, StatOutlierStatsC, StreamConfig, Track, TrackParams, TrackStats, TrackerInfo
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(_PKG, "csrc")
@@ -126,6 +126,9 @@ SYMBOLS = [
     ("pcs_object_boxes_device", C.c_int, [_VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP]),
     ("pcs_object_boxes_device_counted", C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int, _VP]),
     ("pcs_object_boxes", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _P(ObjectBox)]),
+    ("pcs_plan_view_device", C.c_int, [_VP, _VP, C.c_int, _P(PlanParams), _P(PlanMaps)]),
+    ("pcs_plan_view_device_counted", C.c_int, [_VP, _VP, _VP, C.c_int, _P(PlanParams), _P(PlanMaps)]),
+    ("pcs_plan_view", C.c_int, [_VP, _VP, C.c_int, _P(PlanParams), _P(PlanMaps)]),
     ("pcs_align_sums_device", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]),
     ("pcs_align_sums", C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _P(AlignSumsC), _VP]),
     ("pcs_align_solve", C.c_int, [_P(AlignSumsC), _P(C.c_double), _P(C.c_double)]),

@@ -64,6 +64,10 @@ TRACK_UPDATE_LAUNCHES = ("records", "choose", "claim", "assign")     # in kernel
 TRACK_MIN_VOTES_MAX = 1 << 30
 OBJECT_BOXES_LAUNCHES = ("clear", "moments", "axes", "extents")      # in kernel_times_ms order: every call, every form
 TRACK_FIRST_ID_MAX = 1 << 62
+PLAN_STATS_FIELDS = ("considered", "in_band", "mapped", "occupied", "fullest")
+PLAN_VIEW_LAUNCHES = ("clear", "accumulate", "resolve")              # in kernel_times_ms order: every call, every form
+PLAN_SIDE_MAX = 4096
+PLAN_CELLS_MAX = 1 << 22
 
 
 def plane_stages(max_planes: int, labels: bool = False) -> tuple:
@@ -322,6 +326,41 @@ OBJECT_BOX_DTYPE = np.dtype({"names": ["count", "sum_xyz", "m2", "axis", "rank",
                              "offsets": [0, 8, 32, 80, 98, 100, 112, 124], "itemsize": 128})
 assert OBJECT_BOX_DTYPE.itemsize == C.sizeof(ObjectBox) == 128
 assert all(OBJECT_BOX_DTYPE.fields[name][1] == getattr(ObjectBox, name).offset for name in OBJECT_BOX_DTYPE.names)
+
+
+class PlanParams(C.Structure):
+    """pcs_plan_params: twelve int32 words."""
+    _fields_ = [("up_axis", C.c_int32), ("up_sign", C.c_int32), ("cell_mm", C.c_int32), ("origin_u", C.c_int32), ("origin_v", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("band_lo", C.c_int32), ("band_hi", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    @classmethod
+    def make(cls, up_axis: int, up_sign: int, cell_mm: int, width: int, height: int, origin_u=None, origin_v=None, band_lo: int = -32768,
+             band_hi: int = 32767, reserved=(0, 0, 0)) -> "PlanParams":
+        """Without an origin the map is centred on 0: -(width * cell_mm) // 2 per axis (the CLI's rule)."""
+        u0 = -((int(width) * int(cell_mm)) // 2) if origin_u is None else int(origin_u)
+        v0 = -((int(height) * int(cell_mm)) // 2) if origin_v is None else int(origin_v)
+        return cls(int(up_axis), int(up_sign), int(cell_mm), u0, v0, int(width), int(height), int(band_lo), int(band_hi),
+                   (C.c_int32 * 3)(*(int(r) for r in reserved)))
+
+
+class PlanStats(C.Structure):
+    """struct pcs_plan_stats: eight int64."""
+    _fields_ = [(name, C.c_int64) for name in PLAN_STATS_FIELDS] + [("reserved", C.c_int64 * 3)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in PLAN_STATS_FIELDS}
+
+
+class PlanMaps(C.Structure):
+    """pcs_plan_maps: a host struct of five pointers (device pointers for the device forms), all required."""
+    _fields_ = [("count", C.c_void_p), ("top", C.c_void_p), ("bottom", C.c_void_p), ("rgb", C.c_void_p), ("stats", C.c_void_p)]
+
+    @classmethod
+    def make(cls, count: int = 0, top: int = 0, bottom: int = 0, rgb: int = 0, stats: int = 0) -> "PlanMaps":
+        return cls(count or None, top or None, bottom or None, rgb or None, stats or None)
+
+
+assert C.sizeof(PlanParams) == 48 and C.sizeof(PlanStats) == 64 and C.sizeof(PlanMaps) == 5 * C.sizeof(C.c_void_p)
 
 
 class TrackStats(C.Structure):

@@ -5,7 +5,9 @@
 // cloud out, the table and its count in blocks of the chain's own, the `Objects:` line and the file's lines), and -J over three subsets with and without -L
 // (the table either way, object_of out of the cluster call, one tracker update over the cloud that call read, the file's lines), and -W
 // with and without -J and -L (one boxes call behind the cluster call and the tracker's, over the same cloud, object_of and count word,
-// into a block of the chain's own; the file's lines; the run's totals). A stand-alone program: no GPU, no library, nothing loaded into Python.
+// into a block of the chain's own; the file's lines; the run's totals), and -H over four subsets, the empty one among them (no stage: one
+// plan-view call over the cloud that LEAVES the chain, counted iff that cloud has a device count, into one block of the chain's own; the
+// -t line and the three files). A stand-alone program: no GPU, no library, nothing loaded into Python.
 //
 //   make -C pointcloud_stitching_amd/cli ../../tools/bin/filter_chain_check && tools/bin/filter_chain_check
 //   (.../filter_chain_check_asan: the same under the host sanitizers)
@@ -327,6 +329,36 @@ int pcs_object_boxes_device_counted(pcs_ctx*, const int16_t* in, const int32_t* 
 
 // ---- the check ---------------------------------------------------------------------------------------------------------------------
 enum Start { kHost, kDeviceFewer, kDeviceFull };
+// plan-view maps (-H): a call is recorded with how many stage calls stood in front of it, and fills the rasters with what the files show
+struct PlanCall {
+    bool counted; const int16_t* in; const int32_t* d_n; int n_points, max_points; pcs_plan_params params; pcs_plan_maps maps; size_t calls_before;
+};
+static std::vector<PlanCall> g_plan_calls;
+static int fake_plan(PlanCall c)
+{
+    c.calls_before = g_calls.size();
+    const int cells = c.params.width * c.params.height, call = (int)g_plan_calls.size();
+    for (int i = 0; i < cells; i++) {
+        c.maps.count[i] = i % 3 == 2 ? 0u : (uint32_t)(70000 * (i % 2) + i + call);
+        c.maps.top[i] = (int16_t)(i % 3 == 2 ? 0 : 300 * i - 32768 + call);
+        c.maps.bottom[i] = (int16_t)-i;
+        for (int k = 0; k < 3; k++) c.maps.rgb[3 * i + k] = (uint8_t)(i % 3 == 2 ? 0 : 16 * i + k + call);
+    }
+    *c.maps.stats = pcs_plan_stats{c.counted ? *c.d_n : c.n_points, 1000 + call, 900 + call, cells - cells / 3, 70000, {0, 0, 0}};
+    g_plan_calls.push_back(c);
+    return PCS_OK;
+}
+extern "C" {
+int pcs_plan_view_device(pcs_ctx*, const int16_t* in, int n, const pcs_plan_params* p, const pcs_plan_maps* m)
+{
+    return fake_plan({false, in, nullptr, n, 0, *p, *m, 0});
+}
+int pcs_plan_view_device_counted(pcs_ctx*, const int16_t* in, const int32_t* d_n, int max_points, const pcs_plan_params* p, const pcs_plan_maps* m)
+{
+    return fake_plan({true, in, d_n, 0, max_points, *p, *m, 0});
+}
+}
+
 static const char* const kStartName[] = {"host count", "device count below capacity", "device count at capacity"};
 static const int kTag[kStageCount] = {5, 11, 22, 33, 44};      // min_seen, radius_mm, mean_k, distance_mm, tolerance_mm
 
@@ -694,6 +726,80 @@ static void check_boxes(int subset, Start start, int max_objects, bool with_trac
     remove(tracks_file.c_str());
 }
 
+// -H over the stages of `subset` (X not among them), the empty subset included: any() is true for -H alone; one block holds the four
+// rasters and the statistics block; behind run() one plan-view call reads the cloud run() RETURNED, counted iff that cloud has a device
+// count; the -t line and the three files are the header's own writers over what the last call left; release() leaves nothing.
+static void check_plan(int subset, Start start)
+{
+    snprintf(g_case, sizeof g_case, "plan view over subset %d, %s", subset, kStartName[start]);
+    pcs_ctx ctx{0};
+    const int capacity = 41, n_in = start == kDeviceFewer ? 29 : capacity;
+    std::vector<int16_t> cloud((size_t)capacity * PCS_POINT_SHORTS);
+    for (int i = 0; i < capacity; i++)
+        for (int k = 0; k < PCS_POINT_SHORTS; k++) cloud[i * PCS_POINT_SHORTS + k] = (int16_t)(k ? 100 * i + k : i % 6);
+    int32_t count = n_in;
+    const Cloud in{cloud.data(), start == kHost ? nullptr : &count, start == kHost ? n_in : -12345, capacity};
+    Chain chain;
+    std::string why;
+    const char* const args[kStageCount] = {"", "11,2", "22,1000,30", "33,16,3,2,5", "44,3"};
+    int n_enabled = 0;
+    for (int s = 1; s < kStageCount; s++)
+        if (subset >> s & 1) { EXPECT(chain.parse(kStages[s].letter, args[s], why)); n_enabled++; }
+    EXPECT(chain.any() == (n_enabled > 0) && !chain.plan_view());
+    EXPECT(!chain.parse_plan("m,+z,10", why) && !chain.parse_plan("m,up,10,4x4", why) && !chain.parse_plan("m,+z,0,4x4", why) && !chain.plan_view());
+    const std::string prefix = "filter_chain_check_plan.tmp";
+    EXPECT(chain.parse_plan((prefix + ",-y,25,7x5,-80,-60,-100,900").c_str(), why) && chain.plan_view() && chain.any());
+    EXPECT(!chain.parse_plan((prefix + ",+z,10,4x4").c_str(), why) && why.find("twice") != std::string::npos);
+    const pcs_plan_params& P = chain.plan.params;
+    EXPECT(P.up_axis == 1 && P.up_sign == -1 && P.cell_mm == 25 && P.width == 7 && P.height == 5 && P.origin_u == -80 && P.origin_v == -60 &&
+           P.band_lo == -100 && P.band_hi == 900 && !P.reserved[0] && !P.reserved[1] && !P.reserved[2]);
+    chain.finish_options();
+    g_live.clear(); g_plan_calls.clear();
+    EXPECT(chain.allocate(&ctx, (size_t)capacity * PCS_POINT_SHORTS) == PCS_OK);
+    const pcs_plan_maps& m = chain.plan.maps;
+    const uint8_t* base = static_cast<const uint8_t*>(chain.d_plan);
+    EXPECT(g_live.count(chain.d_plan) && g_live[chain.d_plan] == 5 * 256 && (const uint8_t*)m.count == base && (const uint8_t*)m.top == base + 256 &&
+           (const uint8_t*)m.bottom == base + 512 && m.rgb == base + 768 && (const uint8_t*)m.stats == base + 1024);
+    for (int frame = 0; frame < 2; frame++) {
+        g_calls.clear();
+        const Cloud out = chain.run(&ctx, in);
+        EXPECT(chain.status == PCS_OK && (int)g_calls.size() == n_enabled && (int)g_plan_calls.size() == frame);      // run() itself makes no map
+        EXPECT(chain.run_plan(&ctx, out) == PCS_OK && (int)g_plan_calls.size() == frame + 1);
+        const PlanCall& c = g_plan_calls.back();
+        EXPECT(c.calls_before == (size_t)n_enabled && c.in == out.d && c.d_n == out.d_n && c.counted == (out.d_n != nullptr));
+        EXPECT(c.counted == (n_enabled > 0 || start != kHost));
+        if (!n_enabled) EXPECT(c.in == cloud.data());                                                                  // no stage: the cloud that entered
+        if (c.counted) EXPECT(c.max_points == capacity); else EXPECT(c.n_points == n_in);
+        EXPECT(memcmp(&c.params, &P, sizeof P) == 0 && memcmp(&c.maps, &m, sizeof m) == 0);
+        std::ostringstream line, want_line;
+        EXPECT(chain.report_plan(line) && g_plan_calls.size() == (size_t)frame + 1);
+        want_line << "Plan view: " << (c.counted ? *c.d_n : n_in) << " considered, " << 1000 + frame << " in band, " << 900 + frame
+                  << " on the map, 24 occupied of 7 x 5 cells, fullest 70000\n";
+        EXPECT(line.str() == want_line.str());
+    }
+    EXPECT(chain.write_plan(why) && g_plan_calls.size() == 2);                                                         // (writing launches nothing)
+    std::ostringstream rgb, top, cnt;
+    pcs_planview::write_rgb_ppm(rgb, 7, 5, m.rgb);
+    pcs_planview::write_top_pgm(top, P, m.count, m.top);
+    pcs_planview::write_count_pgm(cnt, 7, 5, m.count);
+    const std::string want[3] = {rgb.str(), top.str(), cnt.str()};
+    const char* const suffix[3] = {".rgb.ppm", ".top.pgm", ".count.pgm"};
+    for (int k = 0; k < 3; k++) {
+        std::ifstream f(prefix + suffix[k], std::ios::binary);
+        std::stringstream got;
+        got << f.rdbuf();
+        EXPECT(got.str() == want[k] && got.str().size() == (k == 0 ? 11u + 105u : 13u + 70u));
+        remove((prefix + suffix[k]).c_str());
+    }
+    // the last call: cell 0 has count 1 and top -32767, seen along -y h = 32767, grey 65535; cell 1 top -32467, grey 65235 = 0xFED3, its count
+    // saturated; cell 2 is empty
+    EXPECT(want[1].substr(13, 6) == std::string("\xFF\xFF\xFE\xD3\x00\x00", 6) && want[2].substr(13, 6) == std::string("\x00\x01\xFF\xFF\x00\x00", 6));
+    chain.release();
+    EXPECT(g_live.empty() && g_bad_frees == 0 && !chain.d_plan && !chain.plan.maps.count);
+    chain.release();      // (nothing left to free)
+    EXPECT(g_bad_frees == 0);
+}
+
 int main()
 {
     for (int subset = 0; subset < 32; subset++)
@@ -712,6 +818,8 @@ int main()
         for (Start start : {kHost, kDeviceFewer, kDeviceFull})
             for (int max_objects : {0, 3, 1024})
                 for (bool with_tracks : {false, true}) check_boxes(subset, start, max_objects, with_tracks);
+    for (int subset : {0, 2, 16, 30})
+        for (Start start : {kHost, kDeviceFewer, kDeviceFull}) check_plan(subset, start);
     printf(g_failed ? "filter_chain_check: %d check(s) FAILED\n" : "filter_chain_check: all checks passed, no report\n", g_failed);
     fflush(stdout);      // (a leak report at exit must not swallow the lines above)
     return g_failed ? 1 : 0;
